@@ -16,6 +16,10 @@ roofline  : algorithmic bytes of one H*v in the reference's storage format (SURV
 cpu_baseline (N=1 only): the CPU oracle (a port of the reference algorithm, NOT the reference
             binary) timed on a bounded sample of the same matrices: the reference's MPI row
             decomposition on all host cores (OpenMP threads; the reported value) and the serial loop.
+--dump-outputs DIR: after the timed steps, DIR/alpha.npy and DIR/beta.npy (float64, warmup + steps entries each) hold
+            the Lanczos coefficients of the timed recurrence, i.e. what a caller of edigpu_lanczos_tridiag receives.
+            The benchmark entry points return timings only, so the recurrence is run once more, untimed, through that
+            public entry point from the start vector the timed loop draws on the device (same seed, same length).
 """
 from __future__ import annotations
 
@@ -187,6 +191,39 @@ def cpu_baseline_direct(w, budget_s: float = 15.0):
                       f"1 thread, rows 1..{rows1}: {dt1 * 1e3:.0f} ms per product"}
 
 
+BENCH_SEED = 12345   # the start-vector seed of edigpu_lanczos_bench (rank r of the sharded bench: BENCH_SEED + r)
+
+
+def bench_start_vector(n: int, seed: int):
+    """The n doubles lz_fill_random (csrc/kernels_lanczos.hip, k_fill_random) writes: splitmix64 of
+    seed ^ i * 0xD1B54A32D192ED03, top 53 bits scaled to [-0.5, 0.5)."""
+    import numpy as np
+    u = np.uint64
+    x = np.arange(n, dtype=np.uint64)
+    x *= u(0xD1B54A32D192ED03)
+    x ^= u(seed)
+    x += u(0x9E3779B97F4A7C15)
+    x ^= x >> u(30)
+    x *= u(0xBF58476D1CE4E5B9)
+    x ^= x >> u(27)
+    x *= u(0x94D049BB133111EB)
+    x ^= x >> u(31)
+    x >>= u(11)
+    v = x.astype(np.float64)
+    v *= 1.0 / 9007199254740992.0
+    v -= 0.5
+    return v
+
+
+def dump_outputs(dirname: str, alpha, beta) -> None:
+    import numpy as np
+    if 8 * (len(alpha) + len(beta)) > 64 << 20:
+        raise SystemExit("bench.py: --dump-outputs holds at most 64 MB (warmup + steps <= 4 194 304)")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("alpha", alpha), ("beta", beta)):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def run_single(args):
     import torch  # noqa: F401  (first: one HIP runtime per process, see edipack_amd/capi.py)
     from edipack_amd import capi
@@ -256,6 +293,10 @@ def run_single(args):
         r["frac"] = r["traffic_frac"]
     if not args.no_cpu and h.kind != 2:
         out["cpu_baseline"] = cpu_baseline(h, w.name, args.cpu_seconds)
+    if args.dump_outputs:
+        v0 = bench_start_vector(h.nloc * (2 if h.is_complex else 1), BENCH_SEED)
+        alpha, beta, _ = h.lanczos_tridiag(v0.view(h.dtype), args.warmup + args.steps, threshold=0.0)
+        dump_outputs(args.dump_outputs, alpha, beta)
     dim_gpu = h.dim
     h.destroy()
     if not args.no_cpu and out.get("cpu_baseline") is None:
@@ -438,7 +479,15 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-resident", action="store_true", help="skip the HBM-resident (Ns=16 ladder) H*v measurement")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the Lanczos coefficients of the timed recurrence as DIR/alpha.npy "
+                         "and DIR/beta.npy (float64; single-GPU path)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
+                              or os.environ.get("EDIGPU_FORCE_MULTI")):
+        ap.error("--dump-outputs is implemented for the single-GPU path (--gpus 1) only")
     # EDIGPU_FORCE_MULTI=1: take the N > 1 code path with a single rank (RCCL world of one; with
     # EDIGPU_FORCE_COLLECTIVES=1 the collectives are issued too) -- a one-GPU rehearsal of the nccl calls
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

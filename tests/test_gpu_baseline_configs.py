@@ -53,6 +53,34 @@ def test_cfg3_literal_matches_oracle(gpu):
     hg.destroy()
 
 
+def test_bench_dump_outputs_match_oracle(gpu, tmp_path):
+    """bench.py --dump-outputs on cfg3: one JSON line timing exactly --steps steps, and alpha / beta of the timed
+    recurrence (warmup + steps of each) equal the oracle's tridiagonalisation of the start vector the library's bench
+    loop draws on the device."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from oracle import oracle as O
+    from edipack_amd.synthetic import WORKLOADS, synthetic_model
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg3", "--steps", "20", "--warmup", "3",
+                        "--no-cpu", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 20 and d["warmup"] == 3 and d["ms_per_step"] > 0
+    a, b = np.load(tmp_path / "alpha.npy"), np.load(tmp_path / "beta.npy")
+    assert a.dtype == b.dtype == np.float64 and a.shape == b.shape == (23,)
+    w = WORKLOADS["cfg3"]
+    ho = O.HNormal(_oracle_model(synthetic_model(w)), *w.sector)
+    a_ref, b_ref, nd_ref = ho.lanc_tridiag(bench.bench_start_vector(ho.dim, bench.BENCH_SEED), 23, threshold=0.0)
+    assert nd_ref == 23
+    assert rel_err(a, a_ref) < 1e-10 and rel_err(b, b_ref) < 1e-10
+
+
 def test_cfg4_literal_matches_oracle(gpu):
     from oracle import oracle as O
     from edipack_amd.hamiltonian import SectorHamiltonian

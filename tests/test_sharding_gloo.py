@@ -22,6 +22,9 @@ from edipack_amd.sharding import ShardPlan
 from tests.torch_sharded_loop import ShardedLanczos, TransposedLanczos
 from tests.common import make_models
 
+# the shard plan and the exchange maps come from libedigpu.so's host-only entry points
+pytestmark = pytest.mark.usefixtures("built")
+
 
 def _free_port():
     with socket.socket() as s:
