@@ -35,6 +35,7 @@
 
 #include "exchange_index.hpp"
 #include "kernels.hpp"
+#include "sb_core.hpp"
 
 namespace edigpu {
 
@@ -508,10 +509,11 @@ static int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardG
     g.xlen = (int64_t)c->world * g.q * g.pw;
     if (g.pcol < 1 || g.halo > g.pcol) g.transposed = false;  // blocks narrower than the halo: all-gather form
   }
-  if (g.transposed && g.nblk == 1 && sb_shardable(s) && g.q >= 1 && g.q <= 0xFFFF && !getenv("EDIGPU_SHARD_GENERIC")) {
+  // (rows per rank for which the columns kernel's owner rank g / q is not exact: the column-block exchange)
+  if (g.transposed && g.nblk == 1 && sb_shardable(s) && sb::shard_exact(c->world, g.q) && !getenv("EDIGPU_SHARD_GENERIC")) {
     g.block = true;
     g.npmax = sb_shard_panels(s, c->world);
-    g.bplen = (int64_t)c->world * g.npmax * g.q * 16;
+    g.bplen = sb::shard_slot(c->world, g.npmax, g.q);
   }
   if (g.nblk > 1 && (s->sub_a || (s->kind == 0 && !g.transposed))) {
     // like spMatVec_mpi_normal_main (ED_HAMILTONIAN_NORMAL_STORED_HxV.f90:841-904) and spMatVec_mpi_superc_main /
@@ -584,7 +586,7 @@ static int comm_workspace(edigpu_comm_s* c, const ShardGeom& g, int nlanc) {
 static int sharded_hv_panels(edigpu_sector* s, edigpu_comm_s* c, const ShardGeom& g, hipStream_t st, const double* v,
                              const double** rowhalf, const double** colhalf) {
   const bool alone = c->world == 1 && !force_collectives(c);
-  const size_t per = (size_t)g.npmax * g.q * 16;
+  const size_t per = (size_t)sb::shard_slot(1, g.npmax, g.q);
   if (!alone) {
     EDIGPU_HIP(hipEventRecord(c->ev_ready, st));
     EDIGPU_HIP(hipStreamWaitEvent(c->side, c->ev_ready, 0));
@@ -596,7 +598,7 @@ static int sharded_hv_panels(edigpu_sector* s, edigpu_comm_s* c, const ShardGeom
   const int p0 = c->rank * g.npmax, np = std::max(0, std::min(g.npmax, s->ib->npanels - p0));
   // (panels past the sector's last one are never computed: their slots must not hand stale numbers back)
   if (np < g.npmax) EDIGPU_HIP(hipMemsetAsync(c->bp[2], 0, (size_t)g.bplen * sizeof(double), st));
-  if (launch_sb_cols_shard(s, p0, np, g.q, g.npmax, alone ? v : c->bp[1], c->bp[2], st)) return 1;
+  if (launch_sb_cols_shard(s, p0, np, g.q, g.npmax, c->world, alone ? v : c->bp[1], c->bp[2], st)) return 1;
   *rowhalf = c->bp[3];
   *colhalf = c->bp[2];
   if (!alone) {

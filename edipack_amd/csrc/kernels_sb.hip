@@ -212,8 +212,10 @@ int launch_sb_lanczos(const edigpu_sector* s, const double* P, double* Q, double
 __global__ void __launch_bounds__(256) k_shard_to_panels(const double* __restrict__ src, double* __restrict__ dst, const int32_t* __restrict__ colof,
                                                          int64_t dim_up, int64_t count, int64_t q, int npanels, int64_t n) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
-    const int64_t p = e / (q * 16), rem = e - p * q * 16, i = rem >> 4;
-    const int c = p < npanels ? colof[p * 16 + (rem & 15)] : -1;
+    int64_t p, i;
+    int l;
+    sb::shard_pos(e, q, p, i, l);
+    const int c = p < npanels ? colof[p * 16 + l] : -1;
     dst[e] = (c >= 0 && i < count) ? src[i * dim_up + c] : 0.0;
   }
 }
@@ -223,8 +225,7 @@ __global__ void __launch_bounds__(256) k_shard_from_panels_add(const double* __r
                                                                const int32_t* __restrict__ pos, int64_t dim_up, int64_t q, int64_t n) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const int64_t i = e / dim_up, c = e - i * dim_up;
-    const int p = pos[c];
-    const int64_t at = ((int64_t)(p >> 4) * q + i) * 16 + (p & 15);
+    const int64_t at = sb::shard_at(pos[c], i, q);
     dst[e] = a[at] + b[at];
   }
 }
@@ -263,10 +264,11 @@ int launch_sb_rows_shard(const edigpu_sector* s, int64_t row0, int64_t count, in
 
 // out = (Hdw (x) 1 + Hnd) v on the panels [p0, p0 + np) this rank owns, all rows; v, out: what the all-to-all delivers /
 // returns (every rank's rows in its slot of npmax * q * 16 doubles)
-int launch_sb_cols_shard(const edigpu_sector* s, int p0, int np, int64_t q, int npmax, const double* v, double* out, hipStream_t st) {
+int launch_sb_cols_shard(const edigpu_sector* s, int p0, int np, int64_t q, int npmax, int world, const double* v, double* out,
+                         hipStream_t st) {
   if (np <= 0) return 0;
-  if (q < 1 || q > 0xFFFF) {
-    set_error("launch_sb_cols_shard: rows per rank");
+  if (!sb::shard_exact(world, q)) {  // (shard_geometry admits no such shard form)
+    set_error("launch_sb_cols_shard: no exact owner rank for these rows per rank");
     return 1;
   }
   SbArgs a;
@@ -274,8 +276,8 @@ int launch_sb_cols_shard(const edigpu_sector* s, int p0, int np, int64_t q, int 
   a.npanels = np;
   a.p0 = p0;
   a.q16 = q * 16;
-  a.kslot = (int64_t)npmax * q * 16 - q * 16;
-  a.qmagic = (uint32_t)(((uint64_t)1 << 32) / (uint64_t)q + 1);
+  a.kslot = sb::shard_slot(1, npmax, q) - q * 16;
+  a.qmagic = sb::shard_magic(q);
   return cols(s->ib, a, 2, v, out, st, nullptr);
 }
 

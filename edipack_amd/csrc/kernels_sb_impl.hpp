@@ -56,7 +56,8 @@ struct SbArgs {
   const uint8_t* nd_up;
   // row shards (edigpu_shard.hip): the rows kernel works on the rank's rows [row0, row0 + dim_dw) of the sector; the columns
   // kernel (SH) on its panels [p0, p0 + npanels) with every rank's q rows of a panel in that rank's slot of the buffer:
-  // row g of local panel pl at pl * q * 16 + g * 16 + (g / q) * kslot doubles (qmagic: g / q = (g * qmagic) >> 32)
+  // row g of local panel pl at pl * q * 16 + g * 16 + (g / q) * kslot doubles (qmagic: sb::shard_magic, g / q =
+  // sb::shard_owner(g, qmagic))
   int64_t row0;
   int p0;
   uint32_t qmagic;
@@ -424,7 +425,7 @@ __global__ void __launch_bounds__((CW == 2 ? SB_COLS_NT2 : 512), (CW == 2 ? 2 : 
     const int slot0 = a.chunk_slot[c], nsl = a.chunk_slot[c + 1] - slot0;
     // doubles from the panel's base to row g (SH: + the slot of the rank that owns the row)
     auto roff = [&](int g) -> int64_t {
-      if constexpr (SH) return (int64_t)g * 16 + (int64_t)__umulhi((uint32_t)g, a.qmagic) * a.kslot;
+      if constexpr (SH) return sb::shard_roff(g, a.qmagic, a.kslot);
       else return (int64_t)g * 16;
     };
     const double* __restrict__ vp = v + (SH ? (int64_t)(panel - a.p0) * a.q16 : (int64_t)panel * a.ps);

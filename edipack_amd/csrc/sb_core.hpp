@@ -396,5 +396,52 @@ IB_HD void cols_block_nd(const double* chunk, int own_rel, int col, int nterms, 
   }
 }
 
+// ---- row shards: the shard form of the padded panel layout (kernels_sb.hip, edigpu_shard.hip) --------------------------
+// world ranks, q rows per rank (rank r owns the rows [r q, r q + q)), npmax panels per rank.  A rank's vector holds its q
+// rows of every panel: element ((p q) + i) 16 + l is row i of panel p, lane l.  The all-to-all hands rank d, from every
+// rank s, s's rows of d's panels in slot s: npmax q 16 doubles at shard_slot(s, npmax, q).
+
+// owner rank of row g: g / q as (g * magic) >> 32 with magic = floor(2^32 / q) + 1 for q >= 2.  That 32-bit magic does not
+// exist for q == 1 (it would wrap to 1): magic 0 stands for "owner = g" there, added without a branch (a select on the
+// uniform magic became a scalar branch at every use).  Exact for every g < world q whenever shard_exact(world, q) holds;
+// shard_geometry admits the shard form only then.
+IB_HD uint32_t shard_magic(int64_t q) { return q == 1 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint64_t)q + 1); }
+
+IB_HD uint32_t shard_owner(uint32_t g, uint32_t magic) {
+  const uint32_t all = magic == 0 ? 0xFFFFFFFFu : 0u;  // (g: the product below is 0 then)
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umulhi(g, magic) + (g & all);
+#else
+  return (uint32_t)(((uint64_t)g * magic) >> 32) + (g & all);
+#endif
+}
+
+// (g magic) >> 32 = g / q + g e / (q 2^32) with e = q - 2^32 mod q: exact while the second term stays below the distance of
+// g / q to the next integer, >= 1 / q, for every g < world q -- i.e. (world q - 1) e < 2^32 (the largest g is q - 1 mod q)
+IB_HD bool shard_exact(int64_t world, int64_t q) {
+  if (world < 1 || q < 1 || q > 0xFFFF) return false;
+  if (q == 1) return true;
+  const uint64_t e = (uint64_t)q - (((uint64_t)1 << 32) % (uint64_t)q);
+  return (uint64_t)(world * q - 1) * e < ((uint64_t)1 << 32);
+}
+
+// doubles from a rank's buffer to slot s (the all-to-all's unit)
+IB_HD int64_t shard_slot(int64_t s, int64_t npmax, int64_t q) { return s * npmax * q * 16; }
+
+// element of the shard form of row i of padded column position p (panel p / 16, lane p % 16)
+IB_HD int64_t shard_at(int p, int64_t i, int64_t q) { return ((int64_t)(p >> 4) * q + i) * 16 + (p & 15); }
+
+// inverse of shard_at: element e -> panel, row, lane
+IB_HD void shard_pos(int64_t e, int64_t q, int64_t& panel, int64_t& row, int& lane) {
+  panel = e / (q * 16);
+  const int64_t rem = e - panel * q * 16;
+  row = rem >> 4;
+  lane = (int)(rem & 15);
+}
+
+// sb_cols_kernel<SH>: doubles from a local panel's base (pl q 16 in the buffer) to row g of the sector, in the slot of
+// its owner: (g - o q) 16 + o npmax q 16 = g 16 + o kslot with kslot = (npmax - 1) q 16
+IB_HD int64_t shard_roff(int g, uint32_t magic, int64_t kslot) { return (int64_t)g * 16 + (int64_t)shard_owner((uint32_t)g, magic) * kslot; }
+
 }  // namespace sb
 }  // namespace edigpu

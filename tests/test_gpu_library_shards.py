@@ -8,6 +8,8 @@ the same C loop, pack / unpack kernels, halo columns and padded tails as under R
 """
 import multiprocessing as mp
 import os
+import queue
+import time
 
 import numpy as np
 import pytest
@@ -300,6 +302,21 @@ def test_library_comm_rccl_world_of_one(gpu, monkeypatch, force):
     comm.destroy()
 
 
+GEOMETRY_SEQ = [
+    ("superc", "hybrid", 2, 2, 0, False, "auto"),        # all-gather, small
+    ("normal", "normal", 2, 3, (4, 4), False, "auto"),   # transposed, larger chunk
+    ("nonsu2", "hybrid", 2, 3, 5, False, "auto"),        # all-gather again, larger than the first
+    ("normal", "hybrid", 3, 3, (3, 2), False, "allgather"),
+    ("superc", "hybrid", 2, 3, 0, False, "auto"),
+    ("normal", "normal", 2, 3, (4, 4), False, "allgather"),
+    # padded panels, the recurrence kept in that layout: a larger sector, then a smaller one whose padding lies
+    # where the larger one left numbers (the loop clears its buffers when it starts)
+    ("normal", "hybrid", 3, 5, (4, 3), False, "block"),
+    ("normal", "normal", 2, 3, (4, 4), False, "block"),
+    ("normal", "hybrid", 3, 5, (4, 3), False, "auto"),
+]
+
+
 def test_one_communicator_serves_sectors_of_changing_geometry(gpu, monkeypatch):
     """A communicator is shared across sectors: all-gather shards (superc / nonsu2, explicit arrays) and transposed
     whole sectors of different sizes in turn.  Its workspace buffers grow one by one (the gathered-vector buffer used to
@@ -309,18 +326,7 @@ def test_one_communicator_serves_sectors_of_changing_geometry(gpu, monkeypatch):
     monkeypatch.setenv("EDIGPU_FORCE_COLLECTIVES", "1")
     from edipack_amd.sharding import LibraryComm, library_sharded_sector
     comm = LibraryComm(0, 1, unique_id=LibraryComm.unique_id())
-    seq = [("superc", "hybrid", 2, 2, 0, False, "auto"),        # all-gather, small
-           ("normal", "normal", 2, 3, (4, 4), False, "auto"),   # transposed, larger chunk
-           ("nonsu2", "hybrid", 2, 3, 5, False, "auto"),        # all-gather again, larger than the first
-           ("normal", "hybrid", 3, 3, (3, 2), False, "allgather"),
-           ("superc", "hybrid", 2, 3, 0, False, "auto"),
-           ("normal", "normal", 2, 3, (4, 4), False, "allgather"),
-           # padded panels, the recurrence kept in that layout: a larger sector, then a smaller one whose padding lies
-           # where the larger one left numbers (the loop clears its buffers when it starts)
-           ("normal", "hybrid", 3, 5, (4, 3), False, "block"),
-           ("normal", "normal", 2, 3, (4, 4), False, "block"),
-           ("normal", "hybrid", 3, 5, (4, 3), False, "auto")]
-    for mode, bath, norb, nbath, sector, direct, exchange in seq:
+    for mode, bath, norb, nbath, sector, direct, exchange in GEOMETRY_SEQ:
         ho, pm, v = _reference(mode, bath, norb, nbath, sector)
         for k, val in (("EDIGPU_IB", "1"), ("EDIGPU_IB_MIN", "0"), ("EDIGPU_IB_ROWS", "24")):
             if exchange == "block":
@@ -337,6 +343,205 @@ def test_one_communicator_serves_sectors_of_changing_geometry(gpu, monkeypatch):
         assert comm.exchange_bench(h, 3)[0] in (-1, 1)          # RCCL (world of one: no communicator object, reported as 1)
         h.destroy()
     comm.destroy()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# wider worlds: 4 - 10 ranks on the one GPU, the geometries 1 - 3 ranks never reach (q == 1 rows per rank with two
+# panels each, ranks without panels or without rows, ragged ranks of both kinds)
+# ---------------------------------------------------------------------------------------------------------
+def _run_world(target, world, args, timeout=240):
+    """Start `world` spawned ranks running target(rank, world, *args, queue) one world at a time and collect one result
+    per rank (last field: the error text or None).  On a rank error, a rank that died or the deadline, every child is
+    terminated and joined before the test fails: no rank is left waiting in the shared-memory barrier holding the GPU.
+    Never retried."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=target, args=(r, world) + tuple(args) + (q,)) for r in range(world)]
+    res, why = [], None
+    try:
+        for p in procs:
+            p.start()
+        deadline = time.monotonic() + timeout
+        while len(res) < world and why is None:
+            try:
+                r = q.get(timeout=2)
+                res.append(r)
+                if r[-1] is not None:
+                    why = r[-1]
+            except queue.Empty:
+                dead = [p.exitcode for p in procs if p.exitcode not in (None, 0)]
+                if dead:
+                    why = f"a rank exited with status {dead[0]}"
+                elif time.monotonic() > deadline:
+                    why = f"{world - len(res)} rank(s) gave no result in {timeout} s"
+        for p in procs:
+            p.join(timeout=60 if why is None else 1)
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+        for p in procs:
+            p.join(timeout=30)
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=10)
+    assert why is None, why
+    return sorted(res, key=lambda r: r[0])
+
+
+def _block_env(on):
+    for k, val in (("EDIGPU_IB", "1"), ("EDIGPU_IB_MIN", "0"), ("EDIGPU_IB_ROWS", "24")):
+        if on:
+            os.environ[k] = val
+        else:
+            os.environ.pop(k, None)
+
+
+def _wide_rank_main(rank, world, name, case, eig, q):
+    try:
+        import torch  # noqa: F401  (one HIP runtime per process)
+        from edipack_amd import capi
+        from edipack_amd.sharding import LibraryComm, library_sharded_sector
+        capi.init(0)
+        mode, bath, norb, nbath, sector, direct, exchange = case
+        ho, pm, v = _reference(mode, bath, norb, nbath, sector)
+        comm = LibraryComm(rank, world, shm_name=name, slot_bytes=1 << 22)
+        _block_env(exchange == "block")
+        h, first, count = library_sharded_sector(pm, sector, comm, direct=direct, exchange="auto")
+        info = list(comm.shard_info(h))
+        ix = _shard_index(ho, mode, first, count, False)
+        hv = comm.apply(h, v[ix])
+        a, b, nd, n2 = comm.tridiag(h, v[ix], 20)
+        e = None
+        if eig:
+            ev, x, nconv, nmv = comm.eigh_multi(h, 3, len(ix), v0_shard=v[ix], tol=1e-11)
+            e1, x1, _ = comm.eigh(h, len(ix), v0_shard=v[ix], tol=1e-11)
+            e = (ev, x, nconv, nmv, e1, x1)
+        h.destroy()
+        comm.destroy()
+        q.put((rank, info, ix, hv, a, b, nd, n2, e, None))
+    except Exception as e:  # pragma: no cover
+        import traceback
+        q.put((rank, None, None, None, None, None, 0, 0.0, None, traceback.format_exc() + str(e)))
+
+
+WIDE = [
+    # case, world, shard_info every rank must report (kind, q, npmax | pcol, halo; None: any), eigenpairs too
+    # padded panels (kind 2): Ns = 10, DimDw = 10, 17 panels -- a rank per down row with two panels each (the owner rank
+    # g / q of the columns kernel had no 32-bit magic for q == 1 and sent every row to rank 0's slot)
+    (("normal", "normal", 2, 4, (5, 1), False, "block"), 10, (2, 1, 2, 0), True),
+    # Ns = 8, DimDw = 70, 5 panels: ragged rows and panels (18 x 3 + 16 rows; rank 3 owns no panel), 14 x 5, and 9 x 7 + 7
+    # with ranks 5 - 7 owning no panel
+    (("normal", "normal", 2, 3, (4, 4), False, "block"), 4, (2, 18, 2, 0), False),
+    (("normal", "normal", 2, 3, (4, 4), False, "block"), 5, (2, 14, 1, 0), True),
+    (("normal", "normal", 2, 3, (4, 4), False, "block"), 8, (2, 9, 1, 0), False),
+    # DimDw = 8 over 10 ranks: ranks 8 and 9 own no row (and no panel)
+    (("normal", "normal", 2, 3, (4, 1), False, "block"), 10, (2, 1, 1, 0), False),
+    # column-block exchange with halo columns (kind 1): DimDw = 15, DimUp = 20
+    (("normal", "hybrid", 3, 3, (3, 2), False, "auto"), 4, (1, 4, 5, None), False),
+    (("normal", "hybrid", 3, 3, (3, 2), False, "auto"), 5, (1, 3, 4, None), False),
+    # superc all-gather (kind 0)
+    (("superc", "hybrid", 2, 3, 0, False, "auto"), 5, (0, 51, None, None), False),
+]
+
+
+@pytest.mark.parametrize("case,world,geom,eig", WIDE,
+                         ids=[f"{c[0][0]}-{c[0][1]}{c[0][2]}x{c[0][3]}-{c[0][6]}-w{c[1]}" for c in WIDE])
+def test_library_shards_wide_worlds(gpu, case, world, geom, eig):
+    """The product and the 20-step recurrence (and for two geometries the lowest eigenpairs) with 4 - 10 ranks sharing
+    the GPU over the shared-memory transport, against the oracle.  Every rank must report the geometry the case names:
+    a silent fall-back to another exchange fails the test."""
+    mode, bath, norb, nbath, sector, direct, exchange = case
+    ho, _, v = _reference(mode, bath, norb, nbath, sector)
+    ref = ho.matvec(v)
+    a_ref, b_ref, _ = ho.lanc_tridiag(v, 20)
+    name = f"edigpu_wide_{os.getpid()}_{world}_{abs(hash(case)) % 100000}"
+    res = _run_world(_wide_rank_main, world, (name, case, eig))
+    got = np.zeros_like(ref)
+    for rank, info, ix, hv, a, b, nd, n2, e, _ in res:
+        assert all(g is None or g == i for g, i in zip(geom, info)), (rank, info, geom)
+        if geom[0] == 1:
+            assert info[3] >= 1                                                # halo columns
+        got[ix] = hv
+        assert nd == 20 and abs(n2 - np.real(np.vdot(v, v))) < 1e-10 * abs(n2)
+        assert rel_err(a, a_ref) < 1e-10 and rel_err(b, b_ref) < 1e-10
+    assert rel_err(got, ref) < 1e-12
+    if not eig:
+        return
+    dense = ho.dense()
+    w_ref = np.linalg.eigvalsh(dense)
+    X = np.zeros((3, ho.dim))
+    x1 = np.zeros(ho.dim)
+    e0 = res[0][8]
+    for rank, _, ix, _, _, _, _, _, (ev, x, nconv, nmv, e1, xs), _ in res:
+        assert nconv == 3 and nmv > 0
+        assert np.allclose(ev, e0[0], rtol=0, atol=0) and abs(e1 - e0[4]) == 0.0     # the same on every rank
+        X[:, ix] = x
+        x1[ix] = xs
+    ev, scale = e0[0], max(1.0, np.abs(w_ref).max())
+    assert np.max(np.abs(ev - w_ref[:3])) < 1e-10 * scale
+    assert abs(e0[4] - w_ref[0]) < 1e-10 * scale
+    for i in range(3):
+        assert np.linalg.norm(dense @ X[i] - ev[i] * X[i]) < 1e-8 * scale
+    assert np.linalg.norm(X @ X.T - np.eye(3)) < 1e-9
+    assert np.linalg.norm(dense @ x1 - e0[4] * x1) < 1e-7 * scale and abs(np.linalg.norm(x1) - 1.0) < 1e-10
+
+
+# the changing-geometry sequence at world 4, ending with padded-panel sectors of ragged ranks followed by smaller ones:
+# (4, 4) -- 18 x 3 + 16 rows, rank 3 without a panel -- then (4, 3) -- 14 rows per rank, 2 + 2 + 1 + 0 panels -- then
+# (4, 1) -- 2 rows per rank; each smaller sector's padding (rows count .. q, the slots of ranks without panels) lies where
+# the larger one left numbers
+GEOMETRY_SEQ_W4 = GEOMETRY_SEQ + [
+    ("normal", "normal", 2, 3, (4, 4), False, "block"),
+    ("normal", "hybrid", 3, 5, (4, 3), False, "block"),
+    ("normal", "normal", 2, 3, (4, 1), False, "block"),
+]
+GEOMETRY_W4 = {(2, 3, (4, 4)): (18, 2), (3, 5, (4, 3)): (14, 2), (2, 3, (4, 1)): (2, 2)}   # (q, npmax)
+
+
+def _seq_rank_main(rank, world, name, q):
+    try:
+        import torch  # noqa: F401
+        from edipack_amd import capi
+        from edipack_amd.sharding import LibraryComm, library_sharded_sector
+        capi.init(0)
+        comm = LibraryComm(rank, world, shm_name=name, slot_bytes=1 << 22)
+        out = []
+        for mode, bath, norb, nbath, sector, direct, exchange in GEOMETRY_SEQ_W4:
+            ho, pm, v = _reference(mode, bath, norb, nbath, sector)
+            _block_env(exchange == "block")
+            h, first, count = library_sharded_sector(pm, sector, comm, direct=direct,
+                                                     exchange="auto" if exchange == "block" else exchange)
+            info = list(comm.shard_info(h))
+            ix = _shard_index(ho, mode, first, count, False)
+            hv = comm.apply(h, v[ix])
+            a, b, nd, _ = comm.tridiag(h, v[ix], 12)
+            h.destroy()
+            out.append((info, ix, hv, a, b, nd))
+        comm.destroy()
+        q.put((rank, out, None))
+    except Exception as e:  # pragma: no cover
+        import traceback
+        q.put((rank, None, traceback.format_exc() + str(e)))
+
+
+def test_one_communicator_changing_geometry_world4(gpu):
+    """test_one_communicator_serves_sectors_of_changing_geometry on a shared-memory world of 4: the communicator's
+    buffers serve all-gather shards, column blocks and padded panels in turn, every exchange really crosses ranks."""
+    res = _run_world(_seq_rank_main, 4, (f"edigpu_seq4_{os.getpid()}",))
+    for k, (mode, bath, norb, nbath, sector, direct, exchange) in enumerate(GEOMETRY_SEQ_W4):
+        ho, _, v = _reference(mode, bath, norb, nbath, sector)
+        ref = ho.matvec(v)
+        a_ref, b_ref, _ = ho.lanc_tridiag(v, 12)
+        got = np.zeros_like(ref)
+        for rank, out, _ in res:
+            info, ix, hv, a, b, nd = out[k]
+            assert (info[0] == 2) == (exchange == "block"), (k, rank, info)
+            if exchange == "block":
+                assert tuple(info[1:3]) == GEOMETRY_W4[(norb, nbath, sector)], (k, rank, info)
+            got[ix] = hv
+            assert nd == 12 and rel_err(a, a_ref) < 1e-10 and rel_err(b, b_ref) < 1e-10, (k, rank)
+        assert rel_err(got, ref) < 1e-12, k
 
 
 def _full_rank_main(rank, world, name, wl, nlanc, q):

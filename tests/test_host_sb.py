@@ -120,3 +120,62 @@ def test_refusals(shim):
     _, pm = make_models("normal", "replica", 2, 2, seed=3)
     rc, _, _, msg = _check(shim, pm, 3, 3, 1, 480)
     assert rc == 1 and "bath-bath" in msg
+
+
+# ---------------------------------------------------------------------------------------------------------
+# row shards (csrc/edigpu_shard.hip, the transposed exchange on padded panels): the shard form, the columns kernel's
+# owner-rank arithmetic and the all-to-all, emulated rank by rank on the host
+# ---------------------------------------------------------------------------------------------------------
+def test_shard_owner_rank_is_exact_where_admitted(shim):
+    """sb::shard_owner(g) == g // q at the first and last row of every rank, for every q in [1, 0xFFFF] and world in
+    [1, 64] that sb::shard_exact admits; shard_exact refuses a pair (q >= 2) exactly when the 32-bit magic goes wrong at
+    one of those rows (the old formula: off by one from q = 23254 at world 8, 33096 at 4, 46508 at 2)."""
+    out = (C.c_int64 * 5)()
+    shim.host_sb_owner_check(64, 0xFFFF, out)
+    admitted, evals, wrong, disagree, refused = list(out)
+    assert wrong == 0 and disagree == 0, list(out)
+    assert evals > 50_000_000 and admitted + refused == 64 * 0xFFFF
+    ex = shim.host_sb_shard_exact
+    ex.argtypes, ex.restype = [C.c_int64, C.c_int64], C.c_int
+    assert all(ex(w, 1) for w in range(1, 65))                  # q == 1: served by the helper, not refused
+    assert ex(8, 23253) and not ex(8, 23254) and ex(4, 33095) and not ex(4, 33096) and ex(2, 46507) and not ex(2, 46508)
+    assert ex(64, 12870 // 64 + 1) and ex(2, 12870 // 2)       # the local-block sectors of today (DimDw <= 12870)
+    assert not ex(1, 0x10000) and not ex(0, 1) and not ex(1, 0)
+
+
+def _check_shard(lib, pm, nup, ndw, nb0, max_rows, world, nt=128, nbt=8, nw=2, gs=8):
+    info = (C.c_int32 * 8)()
+    diff = C.c_double(-1.0)
+    m = pm.to_c()
+    rc = lib.host_sb_check_shard(C.byref(m), nup, ndw, nb0, max_rows, nt, nbt, nw, gs, world, info, C.byref(diff))
+    return rc, list(info), diff.value, lib.host_sb_error().decode()
+
+
+SHARD_CASES = [
+    # bath, norb, nbath, sector, world, chunk rows, (q, npmax, ranks without rows, ranks without panels)
+    ("normal", 2, 3, (4, 4), 1, 24, (70, 5, 0, 0)),            # regression: the worlds of the GPU tests
+    ("normal", 2, 3, (4, 4), 2, 24, (35, 3, 0, 0)),
+    ("normal", 2, 3, (4, 4), 3, 24, (24, 2, 0, 0)),
+    ("normal", 2, 4, (4, 5), 5, 24, (51, 3, 0, 0)),            # ragged rows (252 = 4 x 51 + 48), ragged panels (14 = 4 x 3 + 2)
+    ("normal", 2, 3, (4, 4), 8, 24, (9, 1, 0, 3)),             # more ranks than panels
+    ("normal", 2, 3, (4, 1), 10, 24, (1, 1, 2, 5)),            # more ranks than rows (DimDw = 8)
+    ("normal", 2, 4, (5, 1), 10, 24, (1, 2, 0, 1)),            # a rank per row with two panels each: the q == 1 magic
+    ("normal", 2, 4, (5, 1), 12, 24, (1, 2, 2, 3)),
+    ("normal", 2, 4, (4, 1), 10, 24, (1, 2, 0, 3)),
+    ("hybrid", 3, 5, (4, 4), 4, 20, (18, 2, 0, 1)),            # three orbitals, Hnd terms (Jx = Jp != 0)
+]
+
+
+@pytest.mark.parametrize("bath,norb,nbath,sec,world,rows,geom", SHARD_CASES,
+                         ids=[f"{c[0]}{c[1]}x{c[2]}-{c[3][0]}{c[3][1]}-w{c[4]}" for c in SHARD_CASES])
+def test_sharded_local_block_product_matches_explicit_arrays(shim, bath, norb, nbath, sec, world, rows, geom):
+    """The whole sharded product of the transposed exchange on padded panels -- a rank's rows in the shard form, the
+    rows kernel on them, the all-to-all, the columns kernel on the rank's panels through the owner-rank arithmetic
+    (rows staged and partner rows read one by one), the exchange back, the sum -- emulated rank by rank on the host, ==
+    the explicit arrays.  Buffers the library leaves uncleared start as NaN, so a read of padding shows."""
+    _, pm = make_models("normal", bath, norb, nbath, seed=41)
+    rc, info, diff, msg = _check_shard(shim, pm, sec[0], sec[1], 5 - norb, rows, world)
+    assert rc == 0, msg
+    assert info[0] == 1 and diff < 1e-13, (info, diff)
+    assert tuple(info[1:3]) + tuple(info[4:6]) == geom, info
+    assert info[6] > 0                                          # Hnd terms inside the panels
