@@ -80,6 +80,7 @@ static int upload_csr(DevCsr& d, int64_t nrow, const int64_t* rowptr, const int3
 
 static void free_ell(DevEll& e) {
   dev_free(e.pk);
+  dev_free(e.pk16);
   dev_free(e.coef);
   dev_free(e.col);
   dev_free(e.val);
@@ -164,6 +165,25 @@ static int upload_ell(DevEll& e, const HostCsr& a, bool lds) {
     }
     if (dev_upload(&e.pk, pk.data(), pk.size())) return 1;
     if (dev_upload(&e.coef, tc.data(), tc.size())) return 1;
+    // 16-bit image for staged rows whose zero slot lies within 15 bits of byte offset (DimUp <= 4095): entry = byte
+    // offset | sign << 15, two consecutive slots of a column in one word (slot 2q low, 2q + 1 high), words column-major
+    // [slot pair][column]: a lane's 16-byte load brings 2 slots of its 4 adjacent columns, a wave's load is one
+    // contiguous 1 KiB piece, and the table is half the size of the 32-bit one.  An odd width is padded with a dead
+    // slot (zero slot of the row, amplitude tc[nt] = 0).  EDIGPU_ELL16=0 keeps such sectors on the 32-bit image.
+    const char* e16 = getenv("EDIGPU_ELL16");
+    if (lds && (uint64_t)a.nrow * 8u <= 0x7FFFu && !(e16 && atoi(e16) == 0)) {
+      const uint32_t dead = (uint32_t)a.nrow * 8u;
+      const int np = (nt + 1) / 2;
+      std::vector<uint32_t> pk16((size_t)np * e.pitch, dead | dead << 16);
+      for (int k = 0; k < nt; k++)
+        for (int64_t i = 0; i < a.nrow; i++) {
+          const uint32_t p = pk[(size_t)k * e.pitch + i];
+          const uint32_t h = (p & 0x7FFFu) | (p >> 31) << 15;
+          uint32_t& wd = pk16[(size_t)(k >> 1) * e.pitch + i];
+          wd = (k & 1) ? (wd & 0xFFFFu) | h << 16 : (wd & 0xFFFF0000u) | h;
+        }
+      if (dev_upload(&e.pk16, pk16.data(), pk16.size())) return 1;
+    }
     return 0;
   }
   if (packable) {
@@ -736,10 +756,8 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
       if (s->up_ell.typed && s->up_ell.pk) {
         s->row_split = parts;
       } else {
-        dev_free(s->up_ell.pk);
-        dev_free(s->up_ell.coef);
-        dev_free(s->up_ell.col);
-        dev_free(s->up_ell.val);
+        free_ell(s->up_ell);
+        s->up_ell = DevEll();
       }
     }
   }
@@ -3573,10 +3591,7 @@ int edigpu_destroy(edigpu_handle s) {
   dev_free(s->d_ndcoef);
   dev_free(s->d_jup);
   dev_free(s->d_jdw);
-  dev_free(s->up_ell.pk);
-  dev_free(s->up_ell.coef);
-  dev_free(s->up_ell.col);
-  dev_free(s->up_ell.val);
+  free_ell(s->up_ell);
   free_csr(s->dw);
   free_csr(s->nd);
   free_csr(s->loc);

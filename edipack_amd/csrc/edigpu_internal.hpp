@@ -74,6 +74,9 @@ struct DevEll {
   // packed image (preferred): 24-bit column | 7-bit coefficient id | sign; coef[128] table
   uint32_t* pk = nullptr;
   double* coef = nullptr;
+  // typed LDS image of a row of at most 4095 columns, beside pk: 16-bit entries (15-bit byte offset | sign << 15), two
+  // consecutive slots of a column per word, (width + 1) / 2 * pitch words (upload_ell)
+  uint32_t* pk16 = nullptr;
   // plain image (fallback when > 127 distinct |values| or nrow >= 2^24)
   int32_t* col = nullptr;   // width*pitch, padding: col=row, val=0
   double* val = nullptr;

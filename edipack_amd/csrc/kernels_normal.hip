@@ -14,7 +14,8 @@
 //     is a gather inside a row and is served from LDS.  Hup is held as ELL, column-major,
 //     one packed 32-bit word per slot (24-bit column, 7-bit coefficient id, sign) so that a
 //     lane fetches the slots of its 4 adjacent columns with one 16-byte load, shared by the
-//     TD rows.  The diagonal is streamed (explicit Hd) or regenerated from three small tables
+//     TD rows; rows of at most 4095 columns also have a 16-bit form of it (E16: two slots of
+//     4 columns per 16-byte load, half the table bytes).  The diagonal is streamed (explicit Hd) or regenerated from three small tables
 //     (sectors built by the library).
 //
 //  B. normal_dw_panel_kernel -- (Hdw (x) 1) + Hnd as a column-panel sweep.  A panel of <= 64
@@ -68,8 +69,13 @@ __device__ inline double lds_abs_read(uint32_t byte_addr) { return *reinterpret_
 //   per part [split_first, split_first + split_count); a launch adds the hops whose SOURCE column lies in its part
 //   to every output column (entries pointing elsewhere are redirected to the zero slot), the first launch also
 //   the diagonal, the later ones accumulate into hv.  All gathers come from the LDS instead of global memory.
+// E16: the typed LDS image with 16-bit entries (a.ell_pk16: rows of at most 4095 columns; two slots of a column per
+//   word), half the table bytes of the 32-bit one; same slots in the same order, so the same result bit for bit.
+// KP (FUSE = 3 on the 16-bit image, one row per workgroup: at most 2 * NT * kE columns): a thread stages the columns it
+//   computes and keeps their P values in registers for the epilogue, so P is read once, not twice.  It needs the 16-bit
+//   image for its registers: 60 VGPRs with two slots in flight, 88 (five waves per SIMD, no gain) on the 32-bit one.
 template <int NT, int TD, bool USE_LDS, bool LOCAL, bool ND, bool PACKED, bool VEC, bool HDF, int FUSE,
-          bool SPLIT = false>
+          bool SPLIT = false, bool E16 = false, bool KP = false>
 __global__ void __launch_bounds__(NT)
     normal_rows_kernel(NormalArgs a, const double* v_local, const double* __restrict__ v_full,
                        double* hv) {
@@ -107,8 +113,38 @@ __global__ void __launch_bounds__(NT)
   // source of the staged rows: the vector itself, or Q (scaled by 1/beta) in the fused rotate
   const double* __restrict__ v_src = (FUSE >= 2) ? hv : v_local;
 
+  constexpr bool KEEPP = KP && FUSE == 3 && TD == 1 && USE_LDS && LOCAL && !SPLIT;
+  double pkeep[2][kE];
+
   if (LOCAL && PACKED && tid < 128) coef_s[tid] = a.ell_coef[tid];
-  if (LOCAL && USE_LDS) {
+  if (KEEPP) {
+    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)vs != 0u) __builtin_trap();
+    if (tid == 0) vs[sc] = 0.0;
+#pragma unroll
+    for (int ps = 0; ps < 2; ps++) {
+      const int64_t col0 = (int64_t)ps * NT * kE + (int64_t)tid * kE;
+      bool ok[kE];
+#pragma unroll
+      for (int e = 0; e < kE; e++) ok[e] = col0 + e < DimUp;
+      const int64_t cs = ok[0] ? col0 : 0;  // a valid address for the index arithmetic of idle lanes
+      double q[kE];
+      load4<VEC>(v_src, vix(r0, cs), ok, q);
+      load4<VEC>(v_local, vix(r0, cs), ok, pkeep[ps]);
+#pragma unroll
+      for (int e = 0; e < kE; e++) {
+        q[e] -= alpha * pkeep[ps][e];
+        q[e] *= ibeta;
+      }
+      if (VEC) {
+        if (ok[0]) *reinterpret_cast<double2*>(vs + col0) = make_double2(q[0], q[1]);
+        if (ok[2]) *reinterpret_cast<double2*>(vs + col0 + 2) = make_double2(q[2], q[3]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < kE; e++)
+          if (ok[e]) vs[col0 + e] = q[e];
+      }
+    }
+  } else if (LOCAL && USE_LDS) {
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)vs != 0u) __builtin_trap();
     if (tid < TD) vs[tid * S + sc] = 0.0;
     // stage the TD rows: 4 independent loads in flight per thread and row
@@ -212,7 +248,44 @@ __global__ void __launch_bounds__(NT)
       // amplitude; an entry is (byte offset in the staged row) | sign << 31, dead entries name the
       // row's zero slot.  Per gather: v_and, ds_read_b64, v_bitop3 (sign), v_fma_f64.
       const bool fast = PACKED && USE_LDS && a.ell_typed != 0;
-      if (fast) {
+      if (E16) {
+        // 16-bit entries: the KU slots in flight are two 16-byte loads (slot pairs k0 / k0 + 2), a word = the entries
+        // of slots 2q (low half) and 2q + 1 (high half) of one column.  Pairs past the table: clamped address,
+        // amplitude 0; the dead slot that pads an odd width reads the zero slot with amplitude 0.
+        const uint32_t* __restrict__ epk = a.ell_pk16 + col0;
+        const int epitch = (int)a.ell_pitch;
+        const int np = (a.ell_w + 1) >> 1;
+        // measured on config 2: 4 slots in flight beat 2 (43.7 against 46.6 us, plain product); with P kept in registers
+        // only 2 fit the 64 VGPRs of 8 waves per SIMD (fused step 70.5 us against 74.2 with 4 slots at 88 VGPRs)
+        constexpr int KU = KEEPP ? 2 : 4;
+        for (int k0 = 0; k0 < a.ell_w; k0 += KU) {
+          uint4 pk2[KU / 2];
+          double tk[KU];
+#pragma unroll
+          for (int u = 0; u < KU / 2; u++) {
+            const int q = (k0 >> 1) + u < np ? (k0 >> 1) + u : np - 1;
+            pk2[u] = *reinterpret_cast<const uint4*>(epk + q * epitch);
+          }
+#pragma unroll
+          for (int u = 0; u < KU; u++) tk[u] = coef_s[k0 + u < 127 ? k0 + u : 127];  // LDS broadcast
+#pragma unroll
+          for (int u = 0; u < KU; u++) {
+            const uint32_t p[kE] = {pk2[u >> 1].x, pk2[u >> 1].y, pk2[u >> 1].z, pk2[u >> 1].w};
+#pragma unroll
+            for (int r = 0; r < TD; r++)
+              if (TD == 1 || r < nr) {
+#pragma unroll
+                for (int e = 0; e < kE; e++) {
+                  const uint32_t off = (u & 1) ? (p[e] >> 16) & 0x7FFFu : p[e] & 0x7FFFu;
+                  const uint32_t sgn = (u & 1) ? p[e] & 0x80000000u : (p[e] & 0x8000u) << 16;
+                  double x = lds_abs_read((uint32_t)(r * rowB) + off);
+                  x = __hiloint2double(__double2hiint(x) ^ (int)sgn, __double2loint(x));
+                  acc[r][e] = fma(tk[u], x, acc[r][e]);
+                }
+              }
+          }
+        }
+      } else if (fast) {
         const uint32_t* __restrict__ epk = a.ell_pk + col0;
         const int epitch = (int)a.ell_pitch;
         for (int k0 = 0; k0 < a.ell_w; k0 += KU) {
@@ -248,7 +321,7 @@ __global__ void __launch_bounds__(NT)
           }
         }
       }
-      for (int k0 = fast ? a.ell_w : 0; k0 < a.ell_w; k0 += KU) {
+      for (int k0 = (E16 || fast) ? a.ell_w : 0; k0 < a.ell_w; k0 += KU) {
         uint4 pk4[KU];
         int4 pc4[KU];
         double2 pw0[KU], pw1[KU];
@@ -360,7 +433,12 @@ __global__ void __launch_bounds__(NT)
         if (FUSE >= 2) {
           // Q <- acc - beta * P_old ; P <- x (the staged, normalised vector)
           double pold[kE];
-          load4<VEC>(v_local, vix(r0 + r, col0), ok, pold);
+          if (KEEPP) {
+#pragma unroll
+            for (int e = 0; e < kE; e++) pold[e] = c0 == 0 ? pkeep[0][e] : pkeep[1][e];
+          } else {
+            load4<VEC>(v_local, vix(r0 + r, col0), ok, pold);
+          }
           double* pdst = (a.xout ? a.xout : const_cast<double*>(v_local)) + vix(r0 + r, col0);
 #pragma unroll
           for (int e = 0; e < kE; e++) acc[r][e] -= beta * pold[e];
@@ -404,7 +482,7 @@ int normal_pick_rows_per_block(int64_t dim_up, int64_t dw_count) {
 }
 
 // what: 1 = diagonal + up (overwrite), 5 = the same + CSR Hnd, 4 = CSR Hnd only (accumulate), 101-103 = fused Lanczos
-template <int NT, int TD, bool USE_LDS, bool PACKED, bool VEC, bool HDF>
+template <int NT, int TD, bool USE_LDS, bool PACKED, bool VEC, bool HDF, bool E16>
 static int launch_te(const NormalArgs& a, const double* vl, const double* vf, double* hv,
                      int what, hipStream_t st) {
   const int64_t nblk = (a.dw_count + TD - 1) / TD;
@@ -412,7 +490,7 @@ static int launch_te(const NormalArgs& a, const double* vl, const double* vf, do
   dim3 grid((unsigned)nblk), block(NT);
 #define EDIGPU_LAUNCH_ROWS(LOC, NDF, LDSB, UL, PK, HF)                                           \
   do {                                                                                           \
-    auto kern = normal_rows_kernel<NT, TD, UL, LOC, NDF, PK, VEC, HF, 0>;                            \
+    auto kern = normal_rows_kernel<NT, TD, UL, LOC, NDF, PK, VEC, HF, 0, false, E16 && LOC>;     \
     if (ensure_dynamic_lds((const void*)kern, (LDSB))) return 1; \
     hipLaunchKernelGGL(kern, grid, block, (LDSB), st, a, vl, vf, hv);                            \
   } while (0)
@@ -420,19 +498,27 @@ static int launch_te(const NormalArgs& a, const double* vl, const double* vf, do
     case 1: EDIGPU_LAUNCH_ROWS(true, false, lds, USE_LDS, PACKED, HDF); break;
     case 5: EDIGPU_LAUNCH_ROWS(true, true, lds, USE_LDS, PACKED, HDF); break;
     case 101: {  // fused Lanczos, first step
-      auto kern = normal_rows_kernel<NT, TD, USE_LDS, true, false, PACKED, VEC, HDF, 1>;
+      auto kern = normal_rows_kernel<NT, TD, USE_LDS, true, false, PACKED, VEC, HDF, 1, false, E16>;
       if (ensure_dynamic_lds((const void*)kern, lds)) return 1;
       hipLaunchKernelGGL(kern, grid, block, lds, st, a, vl, vf, hv);
       break;
     }
     case 102: {  // fused Lanczos, rotate + H*v
-      auto kern = normal_rows_kernel<NT, TD, USE_LDS, true, false, PACKED, VEC, HDF, 2>;
+      auto kern = normal_rows_kernel<NT, TD, USE_LDS, true, false, PACKED, VEC, HDF, 2, false, E16>;
       if (ensure_dynamic_lds((const void*)kern, lds)) return 1;
       hipLaunchKernelGGL(kern, grid, block, lds, st, a, vl, vf, hv);
       break;
     }
     case 103: {  // fused Lanczos, pending axpy + rotate + H*v
-      auto kern = normal_rows_kernel<NT, TD, USE_LDS, true, false, PACKED, VEC, HDF, 3>;
+      // one short row per workgroup on the 16-bit image: P stays in registers between staging and epilogue (KP)
+      constexpr bool kp_ok = E16 && TD == 1 && NT == 512 && USE_LDS && PACKED;
+      if (kp_ok && a.dim_up <= 2 * NT * kE) {
+        auto kern = normal_rows_kernel<NT, TD, USE_LDS, true, false, PACKED, VEC, HDF, 3, false, E16, kp_ok>;
+        if (ensure_dynamic_lds((const void*)kern, lds)) return 1;
+        hipLaunchKernelGGL(kern, grid, block, lds, st, a, vl, vf, hv);
+        break;
+      }
+      auto kern = normal_rows_kernel<NT, TD, USE_LDS, true, false, PACKED, VEC, HDF, 3, false, E16>;
       if (ensure_dynamic_lds((const void*)kern, lds)) return 1;
       hipLaunchKernelGGL(kern, grid, block, lds, st, a, vl, vf, hv);
       break;
@@ -452,11 +538,15 @@ static int launch_td(const NormalArgs& a, bool packed, bool hdf, const double* v
   // one workgroup per CU by LDS (a single row > 80 KiB): use all 1024 threads of it
   const bool big = TD == 1 && USE_LDS && (size_t)a.dim_up * sizeof(double) > 80 * 1024;
   constexpr int NTBIG = (TD == 1 && USE_LDS) ? 1024 : 512;  // only TD=1 instantiates the 1024 variant
-#define EDIGPU_TD(PK, VC)                                                                  \
-  (big ? (hdf ? launch_te<NTBIG, TD, USE_LDS, PK, VC, true>(a, vl, vf, hv, what, st)       \
-              : launch_te<NTBIG, TD, USE_LDS, PK, VC, false>(a, vl, vf, hv, what, st))     \
-       : (hdf ? launch_te<512, TD, USE_LDS, PK, VC, true>(a, vl, vf, hv, what, st)         \
-              : launch_te<512, TD, USE_LDS, PK, VC, false>(a, vl, vf, hv, what, st)))
+  // the 16-bit typed image exists (rows of at most 4095 columns, never `big`): the variant that reads it
+  const bool e16 = USE_LDS && packed && a.ell_typed != 0 && a.ell_pk16 != nullptr && !big;
+#define EDIGPU_TD(PK, VC)                                                                             \
+  (big   ? (hdf ? launch_te<NTBIG, TD, USE_LDS, PK, VC, true, false>(a, vl, vf, hv, what, st)         \
+                : launch_te<NTBIG, TD, USE_LDS, PK, VC, false, false>(a, vl, vf, hv, what, st))       \
+   : e16 ? (hdf ? launch_te<512, TD, USE_LDS, PK, VC, true, (PK && USE_LDS)>(a, vl, vf, hv, what, st) \
+                : launch_te<512, TD, USE_LDS, PK, VC, false, (PK && USE_LDS)>(a, vl, vf, hv, what, st)) \
+         : (hdf ? launch_te<512, TD, USE_LDS, PK, VC, true, false>(a, vl, vf, hv, what, st)           \
+                : launch_te<512, TD, USE_LDS, PK, VC, false, false>(a, vl, vf, hv, what, st)))
   if (vec) return packed ? EDIGPU_TD(true, true) : EDIGPU_TD(false, true);
   return packed ? EDIGPU_TD(true, false) : EDIGPU_TD(false, false);
 #undef EDIGPU_TD
@@ -516,6 +606,7 @@ static void fill_args(const edigpu_sector* s, NormalArgs& a) {
   a.ed = s->d_ed;
   a.impd = s->d_impd;
   a.ell_pk = s->up_ell.pk;
+  a.ell_pk16 = s->up_ell.pk16;
   a.ell_coef = s->up_ell.coef;
   a.ell_col = s->up_ell.col;
   a.ell_val = s->up_ell.val;
@@ -601,6 +692,7 @@ int launch_normal_rows_pos(const edigpu_sector* s, const double* P, double* Q, d
   a.split_count = d->plen;
   a.eux = d->pr.eux;
   a.ell_pk = d->pr.ell.pk;
+  a.ell_pk16 = nullptr;  // position order: the 32-bit image
   a.ell_coef = d->pr.ell.coef;
   a.ell_col = d->pr.ell.col;
   a.ell_val = d->pr.ell.val;

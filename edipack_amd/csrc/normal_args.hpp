@@ -17,6 +17,7 @@ struct NormalArgs {
   // Hup as ELL: packed (pk + coef table) or plain (col,val)
   const uint32_t* ell_pk;
   const double* ell_coef;  // 128 entries
+  const uint32_t* ell_pk16;  // 16-bit typed LDS image (DevEll::pk16) or null: the rows kernel then reads ell_pk
   const int32_t* ell_col;
   const double* ell_val;
   int ell_w;
