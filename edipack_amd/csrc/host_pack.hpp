@@ -1,0 +1,83 @@
+// host_pack.hpp -- host-side encoders of the packed tables the generic kernels read: the ELL images of a factor
+// matrix (normal_rows_kernel), the SELL-64 image of a CSR block (sell_rows_kernel) and the per-row lists of the panel
+// sweeps (normal_dw_*_kernel).  Plain C++17: host data and explicit options in, vectors and scalars out.  The switches
+// that choose among the images, and the uploads, belong to the C-ABI source; an empty vector means "not built".
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "host_build.hpp"
+
+namespace edigpu {
+
+struct HostInt4 {  // the device's int4
+  int32_t x, y, z, w;
+};
+
+// ELL (column-major [slot][row]) images of a small square factor matrix: the fields of DevEll
+struct HostEll {
+  int64_t nrow = 0, pitch = 0;
+  int width = 0;
+  int typed = 0;
+  std::vector<uint32_t> pk;
+  std::vector<double> coef;
+  std::vector<uint32_t> pk16;
+  std::vector<int32_t> col;
+  std::vector<double> val;
+};
+// lds: the sector's row kernel stages V rows in LDS; the packed layouts then hold byte offsets into
+// the staged row instead of columns, and dead typed slots name its zero slot (index nrow).
+HostEll encode_ell(const HostCsr& a, bool lds, bool allow_typed, bool allow_16);
+
+// SELL-64 image of a CSR block: the sell_* fields of DevCsr; built == false: keep the CSR kernel
+struct HostSell {
+  bool built = false;
+  int64_t nslice = 0;
+  bool packed = false;
+  std::vector<int32_t> ptr;
+  std::vector<uint32_t> pk;
+  std::vector<double> dict, diag;
+  std::vector<int32_t> col;
+  std::vector<double> val;
+};
+HostSell encode_sell(int64_t nrow, int64_t ncol, const int64_t* rowptr, const int32_t* col, const double* val, int cplx,
+                     bool is_loc, double max_pad, bool allow_packed);
+
+void plan_tile_chunks(const HostCsr& dw, int64_t dw_first, int64_t dw_count, int rmax, std::vector<int32_t>& starts,
+                      int& longest);
+
+// merged per-local-row list for the panel kernel: Hdw entries (tag 0) + applicable Hnd terms
+struct HostMergedList {
+  std::vector<int32_t> rowptr, col;
+  std::vector<double> val;
+};
+HostMergedList merge_dw_lists(const HostCsr& dw, const HostFactored& f, int64_t dw_first, int64_t dw_count, int64_t dim_dw);
+
+// per-row lists of the tiled sweep; f: the factored Hnd terms to append, or null
+struct HostTileLists {
+  std::vector<HostInt4> meta;  // per local row: first entry, entries inside the chunk, outside, Hnd terms
+  std::vector<int32_t> col;
+  std::vector<double> val;
+  std::vector<int32_t> lbeg;   // first entry of every chunk, then the end of the last
+  int list_cap = 4;            // entries of the longest chunk
+  bool has_nd = false;
+};
+HostTileLists build_tile_lists(const HostCsr& dw, int64_t dim_dw, int64_t dw_first, int64_t dw_count,
+                               const std::vector<int32_t>& tile_starts, const HostFactored* f);
+
+// per-row lists of the narrow-panel sweep with their weight table; fits == false: no blocked layout
+struct HostBlockLists {
+  bool fits = false;
+  int rows = 0;                // rows of an LDS block
+  std::vector<HostInt4> meta;
+  std::vector<uint32_t> ent;
+  std::vector<double> wtab;
+  std::vector<int32_t> lend;   // end of every block's entries
+  int list_cap = 4;
+};
+HostBlockLists build_block_lists(const HostCsr& dw, const HostFactored& f, int64_t dim_dw, int shift, int64_t lds_kb);
+
+// max |partner column - column| over the factored Hnd terms
+int factored_col_halo(const HostFactored& f, int64_t dim_up);
+
+}  // namespace edigpu

@@ -1,10 +1,12 @@
 // CPU-side sanitizer harness (ASan + UBSan) for the host builders of libedigpu (csrc/host_build.cpp): every bath type,
-// mode and sector of a few small models, shards included.  Built and run by tests/test_host_sanitizers.py.
+// mode and sector of a few small models, shards included; the image encoders of the generic kernels (csrc/host_pack.cpp)
+// on one sector with Hnd terms.  Built and run by tests/test_host_sanitizers.py.
 #include <cstdio>
 #include <cstring>
 #include <random>
 #include "host_build.hpp"
 #include "host_ib.hpp"
+#include "host_pack.hpp"
 using namespace edigpu;
 static void fill(edigpu_model& m, int mode, int bath, int norb, int nbath) {
   memset(&m, 0, sizeof(m));
@@ -19,8 +21,39 @@ static void fill(edigpu_model& m, int mode, int bath, int norb, int nbath) {
     p[0] = (a==b && is==js) ? e(g) : 0.1; p[1] = 0.0; }
 }
 static bool mode_jz(int bath, int norb, int nbath) { return norb == 3 && (bath >= 2 || nbath == 1) && 2 * (bath == 1 ? nbath + norb : (nbath + 1) * norb) <= 14; }
+// every encoder of host_pack.hpp on the sector (4, 4) of norb = 2, nbath = 3 (Jx = Jp != 0: Hnd terms), whole and as a sub-range
+static int pack_images() {
+  edigpu_model m; fill(m, 0, 0, 2, 3);
+  HostNormal hn; if (!build_normal(m, 4, 4, 0, -1, hn, false).empty() || !hn.fac.valid || hn.fac.nterms == 0) return 1;
+  int nell = 0, nsell = 0, nlist = 0, nblk = 0;
+  for (int lds = 0; lds < 2; lds++) for (int opt = 0; opt < 3; opt++) nell += !encode_ell(hn.up, lds != 0, opt != 1, opt != 2).pk.empty();
+  HostCsr many;  // 130 distinct |values| on 65 rows: the plain ELL image; 260 values: the plain SELL image
+  many.nrow = many.ncol = 65; many.rowptr.push_back(0);
+  for (int i = 0; i < 65; i++) { for (int j = 0; j < 4; j++) { many.col.push_back((i + 7 * j) % 65); many.val.push_back(1.0 + 0.01 * (4 * i + j)); } many.rowptr.push_back((int64_t)many.col.size()); }
+  nell += !encode_ell(many, true, true, true).col.empty();
+  for (int loc = 0; loc < 2; loc++) for (int pk = 0; pk < 2; pk++) {
+    nsell += encode_sell(hn.dw.nrow, hn.dw.ncol, hn.dw.rowptr.data(), hn.dw.col.data(), hn.dw.val.data(), 0, loc != 0, 16.0, pk != 0).built;
+    nsell += encode_sell(many.nrow, many.ncol, many.rowptr.data(), many.col.data(), many.val.data(), 0, loc != 0, 16.0, pk != 0).built;
+  }
+  std::vector<double> zv(many.val.size() * 2, 0.5);  // the same pattern as a complex block
+  nsell += encode_sell(many.nrow, many.ncol, many.rowptr.data(), many.col.data(), zv.data(), 1, true, 16.0, true).built;
+  for (int sub = 0; sub < 2; sub++) for (int rmax : {8, 64}) {
+    const int64_t first = sub ? 5 : 0, count = sub ? 40 : hn.dim_dw;
+    std::vector<int32_t> starts; int longest = 0;
+    plan_tile_chunks(hn.dw, first, count, rmax, starts, longest);
+    nlist += !build_tile_lists(hn.dw, hn.dim_dw, first, count, starts, &hn.fac).col.empty();
+    nlist += !build_tile_lists(hn.dw, hn.dim_dw, first, count, starts, nullptr).col.empty();
+    nlist += !merge_dw_lists(hn.dw, hn.fac, first, count, hn.dim_dw).col.empty();
+  }
+  for (int shift = 4; shift <= 6; shift++) for (int kb : {4, 32}) nblk += build_block_lists(hn.dw, hn.fac, hn.dim_dw, shift, kb).fits;
+  const int halo = factored_col_halo(hn.fac, hn.dim_up);
+  // every image was built
+  if (nell == 7 && nsell == 9 && nlist == 12 && nblk == 6 && halo > 0) return 0;
+  printf("host_pack: %d of 7 ELL, %d of 9 SELL, %d of 12 tile / merged lists, %d of 6 block lists, col_halo %d\n", nell, nsell, nlist, nblk, halo);
+  return 1;
+}
 int main() {
-  int nfail = 0, nib = 0, njz = 0;
+  int nfail = pack_images(), nib = 0, njz = 0;
   for (int bath = 0; bath < 4; bath++) for (int norb = 1; norb <= 3; norb++) for (int nbath = 1; nbath <= 3; nbath++) {
     edigpu_model m; fill(m, 0, bath, norb, nbath);
     int ns = model_ns(m);
