@@ -17,6 +17,7 @@
 #include "host_pack.hpp"
 #include "host_sb.hpp"
 #include "kernels.hpp"
+#include "tile_map.hpp"
 
 namespace edigpu {
 
@@ -681,6 +682,7 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
     if (on && shift == 7 && s->nloc >= min_rows && s->panel_mode == 2 && (f.nterms == 0 || s->tl_has_nd)) {
       // 128-column panels: the tiled sweep and its lists as they are, on line-aligned contiguous panels
       s->blk_shift = 7;
+      s->blk_tail_balance = !(e = getenv("EDIGPU_TILE_BALANCE")) || atoi(e) != 0;
       s->blk_rows = s->tile_rows;
       s->blk_ps = dim_dw << 7;
       s->blk_len = ((dim_up + 127) >> 7) * s->blk_ps;
@@ -3099,6 +3101,49 @@ int edigpu_time_apply(edigpu_handle s, int warmup, int steps, int lanczos, doubl
     return 1;
   }
   *ms_per_step = (double)ms / (double)steps;
+  return 0;
+}
+
+int edigpu_apply_loop_d(edigpu_handle s, int64_t nloc, const double* v_host, double* hv_host) {
+  if (!s || !v_host || !hv_host) {
+    set_error("edigpu_apply_loop_d: NULL argument");
+    return 1;
+  }
+  if (single_shard(s, "edigpu_apply_loop_d")) return 1;
+  if (s->is_complex || s->kind == 4 || nloc != s->nloc) {
+    set_error("edigpu_apply_loop_d: needs a real handle and a vector of its local rows");
+    return 1;
+  }
+  EDIGPU_HIP(hipSetDevice(s->device));
+  if (ensure_workspace(s)) return 1;
+  hipStream_t st = s->stream;
+  if (lanczos_prepare(s, 1, 0.0, st)) return 1;  // chooses the layout
+  if (lanczos_seed(s, v_host, 0, st)) return 1;
+  // (the result goes to d_vout: d_tmp is what lanczos_fetch converts through)
+  if (s->lz_blocked ? launch_normal_blocked(s, s->d_vin, s->d_vout, st) : apply_any(s, s->d_vin, s->d_vin, s->d_vout, 3, st))
+    return 1;
+  if (lanczos_fetch(s, s->d_vout, hv_host, st)) return 1;
+  EDIGPU_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+int edigpu_tile_task_map(int32_t npanels, int32_t blocks_per_panel, int32_t balanced, int32_t* grid, int32_t* np,
+                         int32_t* panel, int32_t* chunk, int32_t* pos) {
+  if (npanels < 1 || blocks_per_panel < 1 || !grid || !np ||
+      ((int64_t)npanels + 7) / 8 * 8 * (int64_t)blocks_per_panel > INT32_MAX) {
+    set_error("edigpu_tile_task_map: bad argument");
+    return 1;
+  }
+  const TileMap m = plan_tile_map(npanels, blocks_per_panel, balanced != 0);
+  *grid = m.grid;
+  *np = m.np;
+  for (int wg = 0; wg < m.grid; wg++) {
+    int pn, ch, ps;
+    if (!tile_task_of(m, npanels, blocks_per_panel, wg, pn, ch, ps)) pn = -1;
+    if (panel) panel[wg] = pn;
+    if (chunk) chunk[wg] = ch;
+    if (pos) pos[wg] = ps;
+  }
   return 0;
 }
 

@@ -205,6 +205,7 @@ struct edigpu_sector {
   // panel-major vector layout of the fused Lanczos loop (NormalArgs::blk_shift): chosen at set-up for large factored
   // whole sectors, 0 = not available; lz_blocked: the current recurrence runs on it
   int blk_shift = 0;
+  int blk_tail_balance = 1;     // EDIGPU_TILE_BALANCE=0 at set-up: the padded grid of the tiled sweep (A/B timing, tests)
   int64_t blk_ps = 0, blk_len = 0;
   int4* d_bl_meta = nullptr;
   int blk_rows = 0;             // rows of an LDS block of the blocked sweep

@@ -638,6 +638,7 @@ static void fill_args(const edigpu_sector* s, NormalArgs& a) {
   a.tl_has_nd = s->tl_has_nd;
   a.blk_shift = 0;  // natural layout unless the caller runs the panel-major Lanczos loop
   a.blk_ps = 0;
+  a.blk_tail_balance = s->blk_tail_balance;
   a.bl_meta = s->d_bl_meta;
   a.blk_rows = s->blk_rows;
   a.blk_list_cap = s->blk_list_cap;

@@ -27,6 +27,7 @@
 
 #include "lz_finalize.hpp"
 #include "normal_args.hpp"
+#include "tile_map.hpp"
 
 namespace edigpu {
 
@@ -38,6 +39,7 @@ struct PanelArgs {
   int halo;
   int tile_rows;  // LDS-tiled form: rows of the largest chunk
   int list_cap;   // LDS-tiled form: list entries of the fullest chunk (multiple of 4)
+  TileMap map;    // LDS-tiled form on the panel-major layout: task of a workgroup, position of its sums
 };
 
 constexpr int kPanelNT = 512;
@@ -416,8 +418,12 @@ __global__ void __launch_bounds__(kPanelNT)
 // (SQ_WAIT_ANY / SQ_WAVE_CYCLES = 0.71) and it moves V + result once (FETCH = 155 MB) but at 3.2 TB/s.  In-kernel
 // time stamps and the ISA explain it:
 //  * the launch is bound by the WAVE LAUNCH RATE: 8192 workgroups x 8 waves at the ~0.5-0.8 waves/ns the dispatcher
-//    sustains for 512-thread groups IS the 86 us the sweep takes (the row kernel: 3432 x 8 waves, 52 us) -- so the
-//    grid here is persistent: one launch of as many workgroups as stay resident, each looping over its tasks;
+//    sustains for 512-thread groups IS the 86 us the sweep takes (the row kernel: 3432 x 8 waves, 52 us) -- so a
+//    workgroup here takes a whole task of up to 64 rows.  The kernel loops over tasks, slot + k * (gridDim.x / 8), and
+//    launch_dw_panels can size the grid to what stays resident (EDIGPU_TILE_PERSIST=1), but that measured 3-5 % slower:
+//    by default the natural layout launches one workgroup per task, padding included, and the loop runs once.  On the
+//    panel-major layout (BLK, launch_dw_blocked_tiles) a workgroup always has exactly one task, the one the launcher's
+//    TileMap gives it (tile_map.hpp), and none is launched without one;
 //  * a row's neighbour list was walked entry by entry -- s_load, wait, gather -- paying a scalar-cache miss (~0.5 us
 //    under load) per dependent step; here the lists of a task are copied to LDS once, coalesced, next to the data;
 //  * the result row (an HBM miss) was waited for together with the first gather (vmcnt retires in order) and two
@@ -452,25 +458,38 @@ __global__ void __launch_bounds__(NT)
   int32_t* lcol = reinterpret_cast<int32_t*>(lval + p.list_cap);
   int4* lmeta = reinterpret_cast<int4*>(lcol + p.list_cap);
   uint32_t* ju2 = reinterpret_cast<uint32_t*>(lmeta + p.tile_rows);
+  const int x = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
+  // BLK: the one task of this workgroup and the position of its three sums (tile_map.hpp); np positions per sum
+  int bpanel = 0, bchunk = 0, ppos = blockIdx.x;
+  const int np = BLK ? p.map.np : (int)gridDim.x;
+  const bool has_task = !BLK || tile_task_of(p.map, p.npanels, p.blocks_per_panel, blockIdx.x, bpanel, bchunk, ppos);
+  if (ALPHA && BLK && (int)blockIdx.x >= p.map.wg_tail && bpanel == p.map.panel_tail && threadIdx.x < 24) {
+    // the finalize adds up all np positions: those of the tasks that the partly filled last group of eight panels
+    // lacks (no workgroup stands for them) are zeroed by the workgroups of the tail's first panel, chunk by chunk
+    const int xx = threadIdx.x & 7;
+    if (p.map.panel_tail + xx >= p.npanels) a.partial[(threadIdx.x >> 3) * np + ppos + xx] = 0.0;
+  }
   if (ALPHA && a.scal[SC_STOP] != 0.0) {
     if (threadIdx.x == 0) {
-      a.partial[blockIdx.x] = 0.0;
-      a.partial[gridDim.x + blockIdx.x] = 0.0;
+      a.partial[ppos] = 0.0;
+      a.partial[np + ppos] = 0.0;
+      a.partial[2 * np + ppos] = 0.0;
     }
     return;
   }
   double asum = 0.0, qsum = 0.0, nsum = 0.0;  // <v|w>, sum (w - sg v)^2, <v|v> (k_finalize_ab)
   const double sg = ALPHA ? a.scal[SC_ALPHA] : 0.0;  // see normal_dw_panel_kernel
-  const int x = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   constexpr int NW = NT / 64;
   const int64_t DimUp = a.dim_up;
   int cur_panel = -1;
-  for (int task = slot;; task += nslots) {
-    const int panel = (task / p.blocks_per_panel) * 8 + x;
+  for (int task = slot, it = 0;; task += nslots, it++) {
+    // BLK: one task per workgroup (no stepping by nslots: a balanced grid need not be a multiple of 8, nslots can be 0)
+    if (BLK && (it > 0 || !has_task)) break;
+    const int panel = BLK ? bpanel : (task / p.blocks_per_panel) * 8 + x;
     if (panel >= p.npanels) break;  // uniform: the whole workgroup leaves together
-    const int chunk = task % p.blocks_per_panel;
+    const int chunk = BLK ? bchunk : task % p.blocks_per_panel;
     const int rb = a.tile_chunks[chunk], nrows = a.tile_chunks[chunk + 1] - rb;
     const int lb = a.tile_lbeg[chunk], ln = a.tile_lbeg[chunk + 1] - lb;
     const int64_t pbase = (int64_t)panel * p.width;
@@ -678,12 +697,13 @@ __global__ void __launch_bounds__(NT)
         n += red[2 * (NT / 64) + i];
       }
       if (!a.lz_counter) {
-        a.partial[blockIdx.x] = t;
-        a.partial[gridDim.x + blockIdx.x] = q;
-        a.partial[2 * gridDim.x + blockIdx.x] = n;
+        a.partial[ppos] = t;
+        a.partial[np + ppos] = q;
+        a.partial[2 * np + ppos] = n;
       }
     }
-    // the staged tile is no longer needed: its LDS serves the in-kernel finalize (the launcher sizes it for that)
+    // the staged tile is no longer needed: its LDS serves the in-kernel finalize (the launcher sizes it for that; it
+    // counts the workgroups of the padded grid, which is what the launcher keeps while lz_counter is set)
     if (a.lz_counter)
       lz_finalize_if_last<NT>(a.lz_counter, a.partial, t, q, n, v_full, hv, a.lz_len, const_cast<double*>(a.scal), a.lz_nlanc,
                               reinterpret_cast<double*>(tile));
@@ -970,12 +990,17 @@ static int launch_dw_blocked_tiles(const NormalArgs& a, bool do_nd, const double
   p.blocks_per_panel = a.tile_nchunks;
   p.list_cap = a.tile_list_cap;
   const int panel_groups = (p.npanels + 7) / 8;
-  const int64_t g = (int64_t)panel_groups * p.blocks_per_panel * 8;
-  if (nblocks) *nblocks = (int)g;
-  if (alpha && 3 * g > a.partial_cap) {
+  const int64_t np = (int64_t)panel_groups * p.blocks_per_panel * 8;  // partial positions: the padded grid's
+  if (np > INT32_MAX || (alpha && 3 * np > a.partial_cap)) {
     set_error("launch_dw_blocked: partial buffer too small for this grid");
     return 1;
   }
+  // the tasks of a partly filled last group of eight panels spread over all XCDs (tile_map.hpp), unless the sector was
+  // set up with EDIGPU_TILE_BALANCE=0 or the sweep finalizes the step itself (opt-in; lz_finalize_if_last counts the
+  // workgroups of the padded grid and places the sums by blockIdx)
+  p.map = plan_tile_map(p.npanels, p.blocks_per_panel, a.blk_tail_balance != 0 && !a.lz_counter);
+  const int g = p.map.grid;
+  if (nblocks) *nblocks = p.map.np;
   size_t lds = (size_t)p.tile_rows * kTileSeg * sizeof(double2) + (size_t)p.list_cap * (sizeof(double) + sizeof(int32_t)) +
                (size_t)p.tile_rows * sizeof(int4) + (do_nd ? (size_t)2 * a.nterms * 64 * sizeof(uint32_t) : 0);
   if (alpha) lds = std::max<size_t>(lds, 3 * 1024 * sizeof(double) + 16);  // the in-kernel finalize reuses the tile's LDS

@@ -67,6 +67,7 @@ struct NormalArgs {
   // (iup >> blk_shift) * blk_ps + (idw << blk_shift) + (iup & (W - 1)), W = 1 << blk_shift columns per panel, blk_ps =
   // DimDw * W; the last panel is padded with zeros.  blk_shift = 0: natural layout (idw * DimUp + iup).
   int blk_shift;
+  int blk_tail_balance;  // 128-column panels: spread the last, partly filled group of eight panels over all XCDs (tile_map.hpp)
   int64_t blk_ps;
   // lists of the blocked sweep (normal_dw_blk_kernel): per row bl_meta = (first entry, hops inside the row's LDS block,
   // hops leaving it -- both padded to x4 --, Hnd terms); entry = row (16 bit: index inside the block / global row) |

@@ -363,6 +363,14 @@ class SectorHamiltonian:
                    "edigpu_apply")
         return hv
 
+    def apply_loop(self, v: np.ndarray) -> np.ndarray:
+        """Test hook: the plain product as the device-resident Lanczos loops compute it (panel-major vectors where they
+        are used), on host arrays in the reference's layout."""
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        hv = np.empty_like(v)
+        capi.check(capi.lib().edigpu_apply_loop_d(self._h, v.shape[0], capi.pd(v), capi.pd(hv)), "edigpu_apply_loop_d")
+        return hv
+
     def apply_dev(self, v_full_ptr: int, hv_ptr: int, stream: int = 0) -> None:
         capi.check(capi.lib().edigpu_apply_dev(self._h, v_full_ptr, hv_ptr, stream if stream else None), "edigpu_apply_dev")
 

@@ -611,6 +611,23 @@ int edigpu_cache_destroy(edigpu_cache c);
 int edigpu_time_apply(edigpu_handle h, int warmup, int steps, int lanczos, double *ms_per_step);
 
 /*
+ * Test hook: one plain product as the device-resident Lanczos loops compute it (edigpu_time_apply, lanczos = 2), on
+ * host vectors of nloc doubles in the reference's layout: v is converted to the layout the loops use for this handle
+ * (panel-major where they use it), multiplied there, and the result converted back.
+ */
+int edigpu_apply_loop_d(edigpu_handle h, int64_t nloc, const double *v_host, double *hv_host);
+
+/*
+ * Test hook (host only, no device needed): the task -> workgroup mapping of the tiled column sweep on 128-column
+ * panels of the panel-major layout (csrc/tile_map.hpp) for npanels panels of blocks_per_panel row chunks; balanced = 0:
+ * the padded grid (EDIGPU_TILE_BALANCE=0).  *grid = workgroups launched, *np = positions per sum in the partial buffer;
+ * panel / chunk / pos (np entries each, the first *grid are written): the task of every workgroup and the position of
+ * its sums, panel = -1 for a workgroup without a task.
+ */
+int edigpu_tile_task_map(int32_t npanels, int32_t blocks_per_panel, int32_t balanced, int32_t *grid, int32_t *np,
+                         int32_t *panel, int32_t *chunk, int32_t *pos);
+
+/*
  * Measurement helper for bench.py: `warmup` + `steps` full Lanczos steps (H*v + the vector
  * recurrence) on a random unit start vector.  *ms_wall_per_step = host wall clock of the timed
  * steps (stream synchronised on both sides) / steps; *ms_hv_per_launch = average duration of the

@@ -15,7 +15,7 @@ for sw in EDIGPU_LANCZOS_UNFUSED EDIGPU_NORMAL_EXPLICIT EDIGPU_FLAT_HOSTBUILD ED
           "EDIGPU_IB=1 EDIGPU_IB_MIN=0 EDIGPU_SB_CW=1" "EDIGPU_IB=1 EDIGPU_IB_MIN=0 EDIGPU_SB_AMODE=1" \
           "EDIGPU_IB=1 EDIGPU_IB_MIN=0 EDIGPU_IB_SPLIT=1 EDIGPU_SB_SPLIT=1" "EDIGPU_IB=1 EDIGPU_IB_MIN=0 EDIGPU_IB_PAIRS=1" \
           "EDIGPU_IB=1 EDIGPU_IB_MIN=0 EDIGPU_POSROWS=1" "EDIGPU_IB=1 EDIGPU_IB_MIN=0 EDIGPU_IB_PSPAD=48" \
-          "EDIGPU_ELL16=0"; do
+          "EDIGPU_ELL16=0" "EDIGPU_BLOCKED=1 EDIGPU_BLOCKED_MIN=0 EDIGPU_PANEL_VEC2_MIN=0 EDIGPU_TILE_BALANCE=0"; do
   N=$((N+1)); [ $N -le $SKIP ] && continue
   [ $N -gt $((SKIP+COUNT)) ] && break
   case $sw in *=*) kv=$sw;; *) kv=$sw=1;; esac
