@@ -160,6 +160,24 @@ struct IbDev {
   double *up_pt = nullptr, *dw_pt = nullptr;
 };
 
+// Occupation tables of a library-built whole sector (host_occ.hpp; kernels_occ.hip), made and uploaded by the first
+// edigpu_apply_occ / edigpu_occ_moments on the handle and kept until edigpu_destroy.  Normal mode: pu[dim_up], the down
+// patterns are edigpu_sector::d_impd where the sector has it (pd stays null), order = the rows sorted by down pattern;
+// superc / nonsu2: pu[electronic rows] = up | down << norb.
+struct OccDev {
+  int norb = 0, flat = 0, nblk = 1, ncu = 0;
+  int64_t dim_up = 0, dim_dw = 1;
+  uint16_t* pu = nullptr;
+  uint8_t* pd = nullptr;
+  int32_t* order = nullptr;
+  int32_t run[33] = {0};
+  double *partial = nullptr, *sums = nullptr;  // edigpu_occ_moments: the waves' partial sums, the vectors' sums
+  int64_t partial_cap = 0, sums_cap = 0;       // in doubles
+};
+void free_occ(edigpu_sector* s);
+// device bytes of the tables above (made lazily, so the sector cache adds them to what it measured at build time)
+int64_t occ_table_bytes(const edigpu_sector* s);
+
 }  // namespace edigpu
 
 struct edigpu_sector {
@@ -254,6 +272,8 @@ struct edigpu_sector {
   uint2* d_dir_tests = nullptr;   // (need_set, need_set | need_clear) per term, padded to a multiple of 4
   double* d_dir_dtab = nullptr;
   double* d_dir_xtab = nullptr;
+  // ---- occupation operators (lazily built) ----
+  edigpu::OccDev* occ = nullptr;
   // ---- Lanczos workspace (lazily allocated) ----
   int64_t partial_cap = 0;      // doubles in d_partial
   double* d_vin = nullptr;

@@ -213,4 +213,32 @@ int launch_build_count(const BuildArgs& a, int32_t* width_loc, int32_t* width_no
 int launch_build_fill(const BuildArgs& a, int which, int maxlen, const int32_t* sptr, uint32_t* pk, double* diag,
                       hipStream_t st);
 
+// ---- occupation operators (kernels_occ.hip; tables: host_occ.hpp) ----
+// what the kernels read of a sector: normal mode the vector is nblk (phonon) blocks of dim_dw rows of dim_up elements,
+// pu[iup] / pd[idw] the patterns; flat (superc / nonsu2): nblk blocks of dim_up rows, pu[row] = up | down << norb
+struct OccTables {
+  int norb = 0, flat = 0, cplx = 0, nblk = 1;
+  int64_t dim_up = 0, dim_dw = 1;
+  const uint16_t* pu = nullptr;
+  const uint8_t* pd = nullptr;
+  const int32_t* order = nullptr;  // normal mode: rows sorted by down pattern (occ_sort_rows)
+};
+struct OccWeights {  // occ_weight_table of w_up, w_dw
+  double wu[32], wd[32];
+};
+struct OccSlots {    // occ_sum_slots
+  uint8_t need_up[64], need_dw[64];
+  int nslots;
+};
+struct OccRuns {     // occ_sort_rows
+  int32_t run[33];
+};
+// v_dst(i) = (wu[up pattern of i] + wd[down pattern of i]) v_src(i); enqueued on st, no synchronisation
+int launch_apply_occ(const OccTables& t, const OccWeights& w, const double* src, double* dst, hipStream_t st);
+// waves (= partial sums per vector) launch_occ_moments wants for this sector on a device of ncu compute units
+int occ_moment_waves(const OccTables& t, int ncu);
+// sums[k][64] (slots of occ_sum_slots) of nvec consecutive vectors; partial: nvec * nwaves * 64 doubles
+int launch_occ_moments(const OccTables& t, const OccSlots& sl, const OccRuns& rn, const double* v, int nvec, int nwaves,
+                       double* partial, double* sums, hipStream_t st);
+
 }  // namespace edigpu

@@ -171,9 +171,10 @@ def _csr_args(rowptr, col, val, cplx=False):
 class SectorHamiltonian:
     """One sector Hamiltonian resident on the GPU (an ``edigpu_handle``)."""
 
-    def __init__(self, handle: C.c_void_p, owned: bool = True):
+    def __init__(self, handle: C.c_void_p, owned: bool = True, norb: int = 0):
         self._h = handle
         self._owned = owned        # False: the handle belongs to a SectorCache
+        self.norb = int(norb)      # of the model the sector was built from (0: hand-over arrays)
         info = (C.c_int64 * 10)()
         capi.check(capi.lib().edigpu_info(self._h, info), "edigpu_info")
         (self.dim, self.nloc, self.row_first, cplx, self.kind, self.dim_up, self.dim_dw,
@@ -189,7 +190,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_normal_build(C.byref(h), C.byref(cm), nup, ndw, dw_first, dw_count),
                    "edigpu_normal_build")
-        return cls(h)
+        return cls(h, norb=model.norb)
 
     @classmethod
     def normal_cmplx_from_model(cls, model: ImpurityModel, nup: int, ndw: int) -> "SectorHamiltonian":
@@ -198,7 +199,7 @@ class SectorHamiltonian:
         h = C.c_void_p()
         cm = model.to_c()
         capi.check(capi.lib().edigpu_normal_build_z(C.byref(h), C.byref(cm), nup, ndw), "edigpu_normal_build_z")
-        return cls(h)
+        return cls(h, norb=model.norb)
 
     @classmethod
     def flat_from_model(cls, model: ImpurityModel, sector: int, row_first: int = 0,
@@ -207,7 +208,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_flat_build(C.byref(h), C.byref(cm), sector, row_first, row_count),
                    "edigpu_flat_build")
-        return cls(h)
+        return cls(h, norb=model.norb)
 
     @classmethod
     def flat_jz_from_model(cls, model: ImpurityModel, ntot: int, twojz: int, row_first: int = 0,
@@ -217,7 +218,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_flat_build_jz(C.byref(h), C.byref(cm), ntot, twojz, row_first, row_count),
                    "edigpu_flat_build_jz")
-        return cls(h)
+        return cls(h, norb=model.norb)
 
     @classmethod
     def direct_jz_from_model(cls, model: ImpurityModel, ntot: int, twojz: int, row_first: int = 0,
@@ -227,7 +228,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_direct_build_jz(C.byref(h), C.byref(cm), ntot, twojz, row_first, row_count),
                    "edigpu_direct_build_jz")
-        return cls(h)
+        return cls(h, norb=model.norb)
 
     @classmethod
     def direct_from_model(cls, model: ImpurityModel, sector: int, row_first: int = 0,
@@ -237,7 +238,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_direct_build(C.byref(h), C.byref(cm), sector, row_first, row_count),
                    "edigpu_direct_build")
-        return cls(h)
+        return cls(h, norb=model.norb)
 
     @classmethod
     def orbs_from_model(cls, model: ImpurityModel, nups, ndws, row_first: int = 0,
@@ -253,7 +254,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_orbs_build_rows(C.byref(h), C.byref(cm), capi.pi32(a), capi.pi32(b), row_first,
                                                      row_count), "edigpu_orbs_build")
-        return cls(h)
+        return cls(h, norb=model.norb)
 
     @classmethod
     def orbs_from_arrays(cls, dims, hd, factors) -> "SectorHamiltonian":
@@ -468,6 +469,45 @@ class SectorHamiltonian:
         capi.check(fn(self._h, dst._h, v_src_ptr, v_dst_ptr, iorb, ispin, int(create),
                       stream if stream else None), "edigpu_apply_op")
 
+    # ---- operators diagonal in the occupation basis (edigpu_apply_occ, edigpu_occ_moments) -----
+    def apply_occ(self, v_src_ptr: int, v_dst_ptr: int, w_up, w_dw, stream: int = 0) -> None:
+        """|dst> = sum_a (w_up[a] n_{a,up} + w_dw[a] n_{a,dw}) |src> on device vectors of this sector (dst may be src);
+        enqueued on `stream`, no synchronisation.  w_up, w_dw: norb weights each."""
+        wu = np.ascontiguousarray(w_up, dtype=np.float64)
+        wd = np.ascontiguousarray(w_dw, dtype=np.float64)
+        if self.norb and (wu.size != self.norb or wd.size != self.norb):
+            raise ValueError("apply_occ: w_up and w_dw need norb entries each")
+        capi.check(capi.lib().edigpu_apply_occ(self._h, v_src_ptr, v_dst_ptr, capi.pd(wu), capi.pd(wd),
+                                               stream if stream else None), "edigpu_apply_occ")
+
+    def apply_n(self, v_src_ptr: int, v_dst_ptr: int, iorb: int, stream: int = 0) -> None:
+        """apply_op_N (ED_SECTOR.f90:1141): |dst> = (n_{iorb,up} + n_{iorb,dw}) |src>."""
+        w = np.zeros(max(self.norb, iorb + 1))
+        w[iorb] = 1.0
+        self.apply_occ(v_src_ptr, v_dst_ptr, w, w, stream)
+
+    def apply_sz(self, v_src_ptr: int, v_dst_ptr: int, iorb: int, stream: int = 0) -> None:
+        """apply_op_Sz (ED_SECTOR.f90:1290): |dst> = (n_{iorb,up} - n_{iorb,dw}) / 2 |src>."""
+        w = np.zeros(max(self.norb, iorb + 1))
+        w[iorb] = 0.5
+        self.apply_occ(v_src_ptr, v_dst_ptr, w, -w, stream)
+
+    def occ_moments(self, v_ptr: int, nvec: int = 1):
+        """(M[nvec, 2 norb, 2 norb], norm2[nvec]) of nvec consecutive device vectors: M[k, x, y] = sum_i |v_k(i)|^2
+        n_x(i) n_y(i), x = a (up) / norb + a (down), not normalised (edipack_amd.observables.from_moments reads it)."""
+        n2 = 2 * (self.norb or capi.MAXORB)   # hand-over handles are refused by the library
+        m = np.zeros((nvec, n2, n2))
+        nrm = np.zeros(nvec)
+        capi.check(capi.lib().edigpu_occ_moments(self._h, v_ptr, nvec, capi.pd(m), capi.pd(nrm)), "edigpu_occ_moments")
+        return m, nrm
+
+    def time_occ(self, v_ptr: int, warmup: int, steps: int):
+        """(ms of the occ_moments kernels, ms of apply_occ in place): medians over `steps` runs, HIP events; the vector
+        is overwritten."""
+        ms = (C.c_double * 2)()
+        capi.check(capi.lib().edigpu_time_occ(self._h, v_ptr, warmup, steps, ms), "edigpu_time_occ")
+        return float(ms[0]), float(ms[1])
+
     def lanczos_eigh(self, nitermax: int = 512, tol: float = 1e-12, check_every: int = 10,
                      v0: np.ndarray | None = None, want_vector: bool = True):
         """sp_lanc_eigh semantics (lowest eigenpair)."""
@@ -613,7 +653,7 @@ class SectorCache:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_cache_get(self._c, C.byref(cm), self.KINDS[kind], q1, q2, C.byref(h)),
                    "edigpu_cache_get")
-        return SectorHamiltonian(h, owned=False)
+        return SectorHamiltonian(h, owned=False, norb=model.norb)
 
     def stats(self) -> dict:
         a = (C.c_int64 * 5)()

@@ -232,6 +232,19 @@ module EDIGPU_SHIM
        integer(c_int), value :: iorb, ispin, create
        integer(c_int) :: ierr
      end function edigpu_apply_op_flat
+     function edigpu_apply_occ(h, v_src_dev, v_dst_dev, w_up, w_dw, stream) bind(C, name="edigpu_apply_occ") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, v_src_dev, v_dst_dev, stream
+       real(c_double), intent(in) :: w_up(*), w_dw(*)
+       integer(c_int) :: ierr
+     end function edigpu_apply_occ
+     function edigpu_occ_moments(h, v_dev, nvec, moments, norm2) bind(C, name="edigpu_occ_moments") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, v_dev
+       integer(c_int), value :: nvec
+       real(c_double), intent(inout) :: moments(*), norm2(*)
+       integer(c_int) :: ierr
+     end function edigpu_occ_moments
      function edigpu_apply_cops_normal(src, dst, v_src_dev, v_dst_dev, nops, coef, create, iorb, ispin, stream) &
           bind(C, name="edigpu_apply_cops_normal") result(ierr)
        import :: c_ptr, c_int, c_int32_t, c_double
@@ -404,6 +417,7 @@ module EDIGPU_SHIM
   public :: gpu_sp_lanc_eigh_d, gpu_sp_lanc_eigh_c, gpu_sp_eigh_d, gpu_sp_eigh_c
   public :: gpu_vec_alloc, gpu_vec_free, gpu_vec_upload_d, gpu_vec_download_d, gpu_vec_upload_c, gpu_vec_download_c
   public :: gpu_sp_lanc_eigh_dev, gpu_apply_op, gpu_apply_cops, gpu_lanc_tridiag_dev
+  public :: gpu_apply_op_N, gpu_apply_op_Sz, gpu_occ_moments
   ! N > 1: communicator + the MPI twins of the product and of the tridiagonalisation
   public :: gpu_comm_unique_id, gpu_comm_create, gpu_comm_create_shm, gpu_comm_destroy, gpu_shard_plan
   public :: spMatVec_mpi_gpu_d, spMatVec_mpi_gpu_c, gpu_lanc_tridiag_mpi_d, gpu_lanc_tridiag_mpi_c
@@ -846,6 +860,40 @@ contains
             cr, c_null_ptr), "gpu_apply_op")
     end if
   end subroutine gpu_apply_op
+
+  !> vvinit = apply_op_N(v_state, iorb, isector) (ED_SECTOR.f90:1141-1285; the seed of ED_CHI_DENS.f90:118): device vector
+  !! -> device vector of the SAME sector h (v_dst_dev may be v_src_dev), (n_up + n_dw) of orbital iorb (1-based).  Any
+  !! whole-sector handle built from a model; enqueued on the default stream, no host synchronisation.
+  subroutine gpu_apply_op_N(h, v_src_dev, v_dst_dev, iorb)
+    type(c_ptr), intent(in) :: h, v_src_dev, v_dst_dev
+    integer, intent(in) :: iorb
+    real(c_double) :: w(EDIGPU_MAXORB)
+    if (iorb < 1 .or. iorb > EDIGPU_MAXORB) stop "gpu_apply_op_N: orbital out of range"
+    w = 0d0; w(iorb) = 1d0
+    call gpu_check(edigpu_apply_occ(h, v_src_dev, v_dst_dev, w, w, c_null_ptr), "gpu_apply_op_N")
+  end subroutine gpu_apply_op_N
+
+  !> vvinit = apply_op_Sz(v_state, iorb, isector) (ED_SECTOR.f90:1290-1430; the seed of ED_CHI_SPIN.f90:121):
+  !! (n_up - n_dw) / 2 of orbital iorb (1-based), as gpu_apply_op_N
+  subroutine gpu_apply_op_Sz(h, v_src_dev, v_dst_dev, iorb)
+    type(c_ptr), intent(in) :: h, v_src_dev, v_dst_dev
+    integer, intent(in) :: iorb
+    real(c_double) :: wu(EDIGPU_MAXORB), wd(EDIGPU_MAXORB)
+    if (iorb < 1 .or. iorb > EDIGPU_MAXORB) stop "gpu_apply_op_Sz: orbital out of range"
+    wu = 0d0; wu(iorb) = 0.5d0
+    wd = -wu
+    call gpu_check(edigpu_apply_occ(h, v_src_dev, v_dst_dev, wu, wd, c_null_ptr), "gpu_apply_op_Sz")
+  end subroutine gpu_apply_op_Sz
+
+  !> moments(x, y, k) = sum_i |v_k(i)|^2 n_x(i) n_y(i), norm2(k) = <v_k|v_k> of size(norm2) consecutive device vectors of
+  !! sector h; x, y = 1 .. 2 Norb, orbital a up = a, down = Norb + a (symmetric, so the C row-major order is this one).
+  !! What the loop of ED_OBSERVABLES_NORMAL.f90:120-185 accumulates, without the vector on the host.
+  subroutine gpu_occ_moments(h, v_dev, moments, norm2)
+    type(c_ptr), intent(in) :: h, v_dev
+    real(8), intent(inout) :: moments(:, :, :), norm2(:)
+    if (size(moments, 3) /= size(norm2) .or. size(moments, 1) /= size(moments, 2)) stop "gpu_occ_moments: shapes"
+    call gpu_check(edigpu_occ_moments(h, v_dev, int(size(norm2), c_int), moments, norm2), "gpu_occ_moments")
+  end subroutine gpu_occ_moments
 
   !> vvinit = apply_Cops(v_state, coefs, Os, orbs, spins, isector, jsector) (ED_SECTOR.f90:839-960; the mixed seeds
   !! of the off-diagonal Green's functions, ED_NORMAL/ED_GF_NORMAL.f90:216-261): Os(i) = +1 for c^+, -1 for c

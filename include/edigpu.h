@@ -427,6 +427,41 @@ int edigpu_lanczos_tridiag_dev(edigpu_handle h, const double *vin_dev, int nlanc
                                double threshold, int *niter_done, double *norm2);
 
 /*
+ * Operators diagonal in the occupation basis, on device vectors of ONE sector (source = destination sector).
+ *
+ * edigpu_apply_occ: v_dst(i) = ( sum_a w_up[a] n_{a,up}(i) + w_dw[a] n_{a,dw}(i) ) * v_src(i) -- apply_op_N
+ * (w_up[a] = w_dw[a] = 1) and apply_op_Sz (w_up[a] = +0.5, w_dw[a] = -0.5) of ED_SECTOR.f90:1141-1430, the seeds of
+ * ED_CHI_DENS.f90:118,158-166 and ED_CHI_SPIN.f90:121,162-170; the mixed seeds vI + vJ of those files are one call with
+ * two orbitals weighted.  w_up, w_dw: host arrays of norb doubles, read before the call returns.  v_dst_dev == v_src_dev
+ * is allowed.  The call is enqueued on `stream` and does not synchronise; only the first occupation call on a handle
+ * builds and uploads the handle's occupation tables (synchronously).
+ *
+ * edigpu_occ_moments: for nvec consecutive device vectors of the sector's length (as edigpu_lanczos_eigh_multi writes
+ * evecs; they must be complete when the call is made)
+ *   moments[k][x][y] = sum_i |v_k(i)|^2 n_x(i) n_y(i),   norm2[k] = <v_k|v_k>   (norm2_host may be NULL)
+ * with x, y = 0 .. 2 norb - 1, x = a for (a, up) and norb + a for (a, down), row-major, both triangles filled, NOT divided
+ * by norm2.  Everything the loop of ED_OBSERVABLES_NORMAL.f90:120-185 (and its superc / nonsu2 sisters) sums over the
+ * occupations -- dens, docc, magz, sz2, n2, s2tot -- is a combination of these numbers (edipack_amd/observables.py).  Runs on the
+ * handle's private stream and returns after synchronising.  The sums are made in a fixed order: two calls on the same
+ * input return the same bits.
+ *
+ * Handles: whole sectors built from a model -- edigpu_normal_build (phonon sectors included: the occupation depends on
+ * i mod dim_el only; real vectors), edigpu_normal_build_z, edigpu_flat_build[_jz], edigpu_direct_build[_jz] (interleaved
+ * complex vectors).  The occupation of orbital a is bit a of the up / down map word (normal mode), bit a / bit a + Ns of
+ * the 2 Ns-bit state (superc, nonsu2).  Refused, with these messages: ed_total_ud=F handles ("ed_total_ud=F sectors are
+ * not supported"), hand-over handles -- edigpu_normal_create, edigpu_csr_create_*, edigpu_orbs_create -- ("the handle must
+ * be built from a model ..."), shards ("the handle must hold the whole sector ...").
+ */
+int edigpu_apply_occ(edigpu_handle h, const double *v_src_dev, double *v_dst_dev, const double *w_up, const double *w_dw,
+                     void *stream);
+int edigpu_occ_moments(edigpu_handle h, const double *v_dev, int nvec, double *moments_host, double *norm2_host);
+/* Measurement helper for scripts/time_occupations.py: `warmup` untimed and `steps` timed runs of the device work of
+ * edigpu_occ_moments (one vector: both kernels, without the copy of the result) and of edigpu_apply_occ in place (N of
+ * all orbitals: weights 0, 1, 2, v_dev is overwritten) on the handle's stream, each run between two HIP events;
+ * ms2[0], ms2[1] = the medians in milliseconds. */
+int edigpu_time_occ(edigpu_handle h, double *v_dev, int warmup, int steps, double *ms2);
+
+/*
  * Lowest eigenpair by plain Lanczos (lanc_method="lanczos": sp_lanc_eigh call
  * sites ED_NORMAL/ED_DIAG_NORMAL.f90:206-214): iterate until the lowest Ritz value
  * moves by less than tol (checked every `check_every` steps) or nitermax, then
