@@ -177,6 +177,15 @@ struct OccDev {
 void free_occ(edigpu_sector* s);
 // device bytes of the tables above (made lazily, so the sector cache adds them to what it measured at build time)
 int64_t occ_table_bytes(const edigpu_sector* s);
+// the three refusals the occupation entry points share (ed_total_ud=F, hand-over handle, shard): 1 with the message set
+int occ_refuse(const edigpu_sector* s, const std::string& who);
+
+// Tables and workspace of edigpu_imp_rdm on a library-built whole normal-mode sector (host_rdm.hpp; kernels_rdm.hip),
+// made and uploaded by the first call on the handle and kept until edigpu_destroy.
+struct RdmDev;
+void free_rdm(edigpu_sector* s);
+// device bytes of those tables (made lazily: the sector cache adds them like occ_table_bytes)
+int64_t rdm_table_bytes(const edigpu_sector* s);
 
 }  // namespace edigpu
 
@@ -274,6 +283,8 @@ struct edigpu_sector {
   double* d_dir_xtab = nullptr;
   // ---- occupation operators (lazily built) ----
   edigpu::OccDev* occ = nullptr;
+  // ---- impurity reduced density matrix (lazily built) ----
+  edigpu::RdmDev* rdm = nullptr;
   // ---- Lanczos workspace (lazily allocated) ----
   int64_t partial_cap = 0;      // doubles in d_partial
   double* d_vin = nullptr;

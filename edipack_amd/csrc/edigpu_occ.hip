@@ -30,7 +30,7 @@ int64_t occ_table_bytes(const edigpu_sector* s) {
   return 2 * s->dim_up + ((base && base->d_impd) ? 0 : s->dim_dw) + 4 * s->dim_dw * (s->nph + 1) + workspace;
 }
 
-static int occ_refuse(const edigpu_sector* s, const std::string& who) {
+int occ_refuse(const edigpu_sector* s, const std::string& who) {
   if (s->kind == 3) {
     set_error(who + ": ed_total_ud=F sectors are not supported");
     return 1;

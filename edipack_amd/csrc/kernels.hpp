@@ -3,6 +3,7 @@
 #include <functional>
 
 #include "edigpu_internal.hpp"
+#include "host_rdm.hpp"
 
 namespace edigpu {
 
@@ -240,5 +241,21 @@ int occ_moment_waves(const OccTables& t, int ncu);
 // sums[k][64] (slots of occ_sum_slots) of nvec consecutive vectors; partial: nvec * nwaves * 64 doubles
 int launch_occ_moments(const OccTables& t, const OccSlots& sl, const OccRuns& rn, const double* v, int nvec, int nwaves,
                        double* partial, double* sums, hipStream_t st);
+
+// ---- impurity reduced density matrix (kernels_rdm.hip; tables and work list: host_rdm.hpp) ----
+struct RdmArgs {  // the device copies of an RdmPlan
+  int cw = 1, stride = 0, ld_max = 0, ept_max = 0, rel_max = 0;
+  int64_t dim_up = 0, dim_dw = 0;
+  const int32_t* rows = nullptr;
+  const uint16_t* rel = nullptr;
+  const uint32_t* ent = nullptr;
+  const RdmWork* work = nullptr;
+};
+// dynamic LDS of the tiles kernel: staged slab, accumulators, the chunk's run starts
+size_t rdm_lds_bytes(const RdmArgs& a);
+// out[k][ntri cw] (ostride doubles apart) = the packed triangles of nvec vectors vstride doubles apart; partial: nvec
+// blocks of pstride doubles; groups: host array.  Enqueued on st, no synchronisation.
+int launch_imp_rdm(const RdmArgs& a, int nwork, const RdmGroup* groups, int ngroups, const double* v, int64_t vstride,
+                   int nvec, double* partial, int64_t pstride, double* out, int64_t ostride, hipStream_t st);
 
 }  // namespace edigpu

@@ -508,6 +508,24 @@ class SectorHamiltonian:
         capi.check(capi.lib().edigpu_time_occ(self._h, v_ptr, warmup, steps, ms), "edigpu_time_occ")
         return float(ms[0]), float(ms[1])
 
+    # ---- impurity reduced density matrix (edigpu_imp_rdm) --------------------------------------
+    def imp_rdm(self, v_ptr: int, nvec: int = 1):
+        """(rho[nvec, D, D], norm2[nvec]) of nvec consecutive device vectors of a normal-mode sector, D = 4^norb:
+        rho = Tr_bath |v><v| in the ordering io = Iup + 2^norb Idw, not normalised (norm2 = its trace); float64, or
+        complex128 on a complex handle (edipack_amd.observables.rdm_average reads it)."""
+        d = 4 ** (self.norb or capi.MAXORB)   # hand-over handles are refused by the library
+        rho = np.zeros((nvec, d, d), dtype=np.complex128 if self.is_complex else np.float64)
+        nrm = np.zeros(nvec)
+        capi.check(capi.lib().edigpu_imp_rdm(self._h, v_ptr, nvec, rho.ctypes.data_as(C.POINTER(C.c_double)), capi.pd(nrm)),
+                   "edigpu_imp_rdm")
+        return rho, nrm
+
+    def time_rdm(self, v_ptr: int, warmup: int, steps: int) -> float:
+        """ms of the imp_rdm kernels on one vector: the median over `steps` runs, HIP events; the vector is unchanged."""
+        ms = C.c_double(0.0)
+        capi.check(capi.lib().edigpu_time_rdm(self._h, v_ptr, warmup, steps, C.byref(ms)), "edigpu_time_rdm")
+        return float(ms.value)
+
     def lanczos_eigh(self, nitermax: int = 512, tol: float = 1e-12, check_every: int = 10,
                      v0: np.ndarray | None = None, want_vector: bool = True):
         """sp_lanc_eigh semantics (lowest eigenpair)."""

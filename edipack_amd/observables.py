@@ -14,7 +14,12 @@ U = M[:n, :n] (up-up), D = M[n:, n:] (down-down), X = M[:n, n:] (up-down)
     s2tot   = sum sz2                    (imp.check[0])
     dust    = sum_{a<b} X_ab + X_ba      dund    = sum_{a<b} U_ab + D_ab      (doubles.check[0:2])
 
-Pure numpy: O(norb^2) numbers per vector reach the host."""
+``SectorHamiltonian.imp_rdm`` (edigpu_imp_rdm) gives the other family, the impurity reduced density matrix
+rho = Tr_bath |v><v| in the ordering io = Iup + 2^norb Idw (imp_rdm_normal, ED_NORMAL/ED_RDM_NORMAL.f90): rdm_average
+normalises and averages it as that routine's loop over the states does, rdm_occupations reads its diagonal,
+entanglement_entropy its spectrum.
+
+Pure numpy: O(norb^2) numbers per vector (16^norb for the density matrix) reach the host."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -55,3 +60,39 @@ def from_moments(M, norb: int, norm2=None) -> OccObservables:
     off = np.triu(np.ones((n, n), dtype=bool), 1)
     return OccObservables(dens=up + dw, dens_up=up, dens_dw=dw, docc=np.diag(X).copy(), magz=up - dw, sz2=sz2, n2=n2,
                           s2tot=float(sz2.sum()), dust=float((X + X.T)[off].sum()), dund=float((U + D)[off].sum()))
+
+
+def rdm_average(rhos, norm2, weights=None) -> np.ndarray:
+    """rho of a manifold: rhos[k, D, D] as imp_rdm returns them, each divided by norm2[k], then averaged -- equal weights
+    (the degenerate ground states of imp_rdm_normal at zero temperature) or `weights` (Boltzmann weights; they are
+    normalised to sum 1)."""
+    rhos = np.asarray(rhos)
+    if rhos.ndim == 2:
+        rhos = rhos[None]
+    n2 = np.atleast_1d(np.asarray(norm2, dtype=np.float64))
+    if rhos.ndim != 3 or rhos.shape[1] != rhos.shape[2] or n2.shape != (rhos.shape[0],):
+        raise ValueError(f"rdm_average: expected rhos[k, D, D] and k norms, got {rhos.shape} and {n2.shape}")
+    w = np.full(n2.size, 1.0 / n2.size) if weights is None else np.asarray(weights, dtype=np.float64) / np.sum(weights)
+    if w.shape != n2.shape:
+        raise ValueError("rdm_average: one weight per state")
+    return np.tensordot(w / n2, rhos, axes=(0, 0))
+
+
+def rdm_occupations(rho, norb: int):
+    """(dens_up, dens_dw, docc) per orbital from the diagonal of rho[D, D], D = 4^norb, io = Iup + 2^norb Idw."""
+    n = int(norb)
+    rho = np.asarray(rho)
+    if rho.shape != (4 ** n, 4 ** n):
+        raise ValueError(f"rdm_occupations: expected [{4 ** n}, {4 ** n}], got {rho.shape}")
+    p = np.real(np.diag(rho))
+    io = np.arange(4 ** n)
+    up = np.array([(io >> a) & 1 for a in range(n)], dtype=np.float64)
+    dw = np.array([(io >> (n + a)) & 1 for a in range(n)], dtype=np.float64)
+    return up @ p, dw @ p, (up * dw) @ p
+
+
+def entanglement_entropy(rho) -> float:
+    """-sum p ln p over the eigenvalues p > 1e-300 of the (normalised, Hermitian) rho."""
+    p = np.linalg.eigvalsh(np.asarray(rho))
+    p = p[p > 1e-300]
+    return float(-np.sum(p * np.log(p)))

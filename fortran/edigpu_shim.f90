@@ -245,6 +245,13 @@ module EDIGPU_SHIM
        real(c_double), intent(inout) :: moments(*), norm2(*)
        integer(c_int) :: ierr
      end function edigpu_occ_moments
+     function edigpu_imp_rdm(h, v_dev, nvec, rdm, norm2) bind(C, name="edigpu_imp_rdm") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, v_dev
+       integer(c_int), value :: nvec
+       real(c_double), intent(inout) :: rdm(*), norm2(*)
+       integer(c_int) :: ierr
+     end function edigpu_imp_rdm
      function edigpu_apply_cops_normal(src, dst, v_src_dev, v_dst_dev, nops, coef, create, iorb, ispin, stream) &
           bind(C, name="edigpu_apply_cops_normal") result(ierr)
        import :: c_ptr, c_int, c_int32_t, c_double
@@ -417,7 +424,7 @@ module EDIGPU_SHIM
   public :: gpu_sp_lanc_eigh_d, gpu_sp_lanc_eigh_c, gpu_sp_eigh_d, gpu_sp_eigh_c
   public :: gpu_vec_alloc, gpu_vec_free, gpu_vec_upload_d, gpu_vec_download_d, gpu_vec_upload_c, gpu_vec_download_c
   public :: gpu_sp_lanc_eigh_dev, gpu_apply_op, gpu_apply_cops, gpu_lanc_tridiag_dev
-  public :: gpu_apply_op_N, gpu_apply_op_Sz, gpu_occ_moments
+  public :: gpu_apply_op_N, gpu_apply_op_Sz, gpu_occ_moments, gpu_imp_rdm
   ! N > 1: communicator + the MPI twins of the product and of the tridiagonalisation
   public :: gpu_comm_unique_id, gpu_comm_create, gpu_comm_create_shm, gpu_comm_destroy, gpu_shard_plan
   public :: spMatVec_mpi_gpu_d, spMatVec_mpi_gpu_c, gpu_lanc_tridiag_mpi_d, gpu_lanc_tridiag_mpi_c
@@ -894,6 +901,17 @@ contains
     if (size(moments, 3) /= size(norm2) .or. size(moments, 1) /= size(moments, 2)) stop "gpu_occ_moments: shapes"
     call gpu_check(edigpu_occ_moments(h, v_dev, int(size(norm2), c_int), moments, norm2), "gpu_occ_moments")
   end subroutine gpu_occ_moments
+
+  !> rdm(io, jo, k) = sum over the bath (and phonon) indices of v_k(io-part, bath) conj v_k(jo-part, bath), norm2(k) =
+  !! <v_k|v_k>, of size(norm2) consecutive REAL device vectors of the normal-mode sector h; io, jo = 1 .. 4**Norb,
+  !! io - 1 = Iup + 2**Norb * Idw as in imp_rdm_normal (ED_RDM_NORMAL.f90:146-209).  Not divided by norm2.  The matrix is
+  !! symmetric, so the C row-major order is this one.  Complex handles return interleaved (re, im): call edigpu_imp_rdm.
+  subroutine gpu_imp_rdm(h, v_dev, rdm, norm2)
+    type(c_ptr), intent(in) :: h, v_dev
+    real(8), intent(inout) :: rdm(:, :, :), norm2(:)
+    if (size(rdm, 3) /= size(norm2) .or. size(rdm, 1) /= size(rdm, 2)) stop "gpu_imp_rdm: shapes"
+    call gpu_check(edigpu_imp_rdm(h, v_dev, int(size(norm2), c_int), rdm, norm2), "gpu_imp_rdm")
+  end subroutine gpu_imp_rdm
 
   !> vvinit = apply_Cops(v_state, coefs, Os, orbs, spins, isector, jsector) (ED_SECTOR.f90:839-960; the mixed seeds
   !! of the off-diagonal Green's functions, ED_NORMAL/ED_GF_NORMAL.f90:216-261): Os(i) = +1 for c^+, -1 for c

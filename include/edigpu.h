@@ -462,6 +462,35 @@ int edigpu_occ_moments(edigpu_handle h, const double *v_dev, int nvec, double *m
 int edigpu_time_occ(edigpu_handle h, double *v_dev, int warmup, int steps, double *ms2);
 
 /*
+ * Impurity reduced density matrix rho_imp = Tr_bath |v><v| of device vectors of a normal-mode sector (imp_rdm_normal,
+ * ED_NORMAL/ED_RDM_NORMAL.f90:146-209, rdm_flag=T): the source of entanglement entropies, local state probabilities and
+ * the impurity correlators that are not diagonal in the occupations.
+ *
+ * A spin word of the sector (Nup, Ndw) is I + 2^norb B, I the impurity pattern (low norb bits), B the bath pattern; the
+ * vector index is i = iup + idw DimUp (+ iph DimUp DimDw).  For nvec consecutive device vectors (they must be complete
+ * when the call is made)
+ *   rdm[k][io][jo] = sum_{Bup, Bdw (, iph)} v_k(Iup Bup, Idw Bdw) conj v_k(Jup Bup, Jdw Bdw),   norm2[k] = <v_k|v_k>
+ *   io = Iup + 2^norb Idw,  jo = Jup + 2^norb Jdw,  D = 4^norb
+ * NOT divided by norm2 and without a fermionic sign (none appears in normal mode).  On phonon sectors the phonon index
+ * is traced as well (the sum runs over the nph + 1 blocks); the reference's routine ignores phonons.
+ * rdm_host: [nvec][D][D] row-major, dense, both triangles filled; doubles for real handles, interleaved (re, im) for
+ * complex handles (edigpu_normal_build_z).  norm2_host (nvec doubles) may be NULL; it is the trace of the result.
+ * The result is exactly Hermitian (one triangle is computed and mirrored).  The sums are made in a fixed order: two
+ * calls on the same input return the same bits.  Runs on the handle's private stream and returns after synchronising;
+ * the first call on a handle builds and uploads the handle's tables, later calls upload nothing.
+ *
+ * Handles: whole sectors from edigpu_normal_build (phonon sectors included) and edigpu_normal_build_z, norb = 1 ..
+ * EDIGPU_MAXORB.  Refused: superc / nonsu2 handles, stored or on the fly ("only ed_mode=normal sectors are supported":
+ * those modes carry fermionic signs in the reference), and, with the messages of edigpu_occ_moments, ed_total_ud=F
+ * handles, hand-over handles and shards.
+ */
+int edigpu_imp_rdm(edigpu_handle h, const double *v_dev, int nvec, double *rdm_host, double *norm2_host);
+/* Measurement helper for scripts/time_rdm.py: `warmup` untimed and `steps` timed runs of the device work of
+ * edigpu_imp_rdm on one vector (all kernels, without the copy of the result) on the handle's stream, each run between
+ * two HIP events; *ms = the median in milliseconds.  v_dev is left unchanged. */
+int edigpu_time_rdm(edigpu_handle h, const double *v_dev, int warmup, int steps, double *ms);
+
+/*
  * Lowest eigenpair by plain Lanczos (lanc_method="lanczos": sp_lanc_eigh call
  * sites ED_NORMAL/ED_DIAG_NORMAL.f90:206-214): iterate until the lowest Ritz value
  * moves by less than tol (checked every `check_every` steps) or nitermax, then

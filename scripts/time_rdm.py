@@ -1,0 +1,88 @@
+#!/usr/bin/env python
+"""Times edigpu_imp_rdm on two normal-mode sectors and prints ONE JSON line (profiles/rdm.json):
+
+  cfg2        Ns=14 (7,7), two orbitals, 94 MB per vector (inside the 256 MiB Infinity Cache)
+  cfg3_ns16   Ns=16 (8,8), three orbitals, 1.33 GB per vector: the HBM-resident sector of bench.py
+
+Per sector, in this one process: the median of the imp_rdm kernels over >= 20 runs between HIP events after a warm-up
+(edigpu_time_rdm), the occ_moments median on the same vector (edigpu_time_occ: the same single pass over v), the read
+ceiling of edigpu_membw on a buffer of the vector's size, and what a host has to do without this entry point:
+edigpu_dev_download of the vector plus the numpy restatement of imp_rdm_normal (tests/test_rdm_host.py::numpy_rdm) on
+it (wall clock, once).
+
+    python scripts/time_rdm.py [--workloads cfg2,cfg3_ns16] [--steps 21]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def host_baseline(h, model, sector, v_ptr):
+    """seconds of (download, numpy rho) for the vector at v_ptr, and rho"""
+    from edipack_amd import capi
+    from edipack_amd.hamiltonian import sector_map
+    from tests.test_rdm_host import numpy_rdm
+    v = np.empty(h.dim, dtype=h.dtype)
+    t0 = time.perf_counter()
+    capi.check(capi.lib().edigpu_dev_download(v.ctypes.data_as(C.c_void_p), C.c_void_p(v_ptr), v.nbytes), "edigpu_dev_download")
+    t1 = time.perf_counter()
+    mu, md = sector_map(model, sector[0], sector[1], 0), sector_map(model, sector[0], sector[1], 1)
+    t2 = time.perf_counter()
+    rho = numpy_rdm(mu, md, model.norb, v)
+    t3 = time.perf_counter()
+    return t1 - t0, t3 - t2, rho
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="cfg2,cfg3_ns16")
+    ap.add_argument("--steps", type=int, default=21)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+    import torch
+    from edipack_amd import capi
+    from edipack_amd.synthetic import WORKLOADS, build_workload, synthetic_model
+    if capi.device_count() < 1:
+        raise SystemExit("time_rdm.py: no HIP device (there is nothing to time on a CPU)")
+    capi.init(0)
+    out = {"script": "scripts/time_rdm.py", "kernel_source_hash": capi.kernel_source_hash(),
+           "steps": args.steps, "warmup": args.warmup, "sectors": []}
+    for name in args.workloads.split(","):
+        w = WORKLOADS[name]
+        model = synthetic_model(w)
+        h = build_workload(w)
+        gen = torch.Generator(device="cuda").manual_seed(1234)
+        v = torch.randn(h.dim, dtype=torch.float64, device="cuda", generator=gen)
+        torch.cuda.synchronize()
+        nbytes = h.dim * 8
+        rho, n2 = h.imp_rdm(v.data_ptr())             # first call: builds the tables; the result checks the baseline
+        t_down, t_numpy, rho_host = host_baseline(h, model, w.sector, v.data_ptr())
+        agree = float(np.max(np.abs(rho[0] - rho_host)) / n2[0])
+        ms_rdm = h.time_rdm(v.data_ptr(), args.warmup, args.steps)
+        ms_mom, _ = h.time_occ(v.data_ptr(), args.warmup, args.steps)   # overwrites v
+        del v
+        torch.cuda.empty_cache()
+        read, _, _ = capi.membw(max(nbytes, 1 << 20))
+        gbs_rdm, gbs_mom = nbytes / (ms_rdm * 1e-3) / 1e9, nbytes / (ms_mom * 1e-3) / 1e9
+        out["sectors"].append({
+            "workload": name, "note": w.note, "dim": h.dim, "norb": model.norb, "vector_bytes": nbytes,
+            "imp_rdm": {"ms": ms_rdm, "GBs": gbs_rdm, "ceiling_read_GBs": read, "frac_of_ceiling": gbs_rdm / read,
+                        "rate_over_occ_moments": ms_mom / ms_rdm},
+            "occ_moments": {"ms": ms_mom, "GBs": gbs_mom, "frac_of_ceiling": gbs_mom / read},
+            "host_baseline": {"download_ms": t_down * 1e3, "numpy_rdm_ms": t_numpy * 1e3,
+                              "total_over_imp_rdm": (t_down + t_numpy) * 1e3 / ms_rdm,
+                              "max_abs_diff_rho_over_norm2": agree}})
+        h.destroy()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
