@@ -610,7 +610,8 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
     const bool with_nd = f && f->nterms > 0 && s->d_mx_rowptr != nullptr;
     const HostTileLists l = build_tile_lists(dw, dim_dw, dw_first, dw_count, tile_starts, with_nd ? f : nullptr);
     s->tile_list_cap = l.list_cap;
-    if (dev_upload(&s->d_tile_lbeg, l.lbeg.data(), l.lbeg.size()) || dev_upload(&s->d_tl_meta, as_int4(l.meta), l.meta.size()) ||
+    const std::vector<HostInt4> meta = tile_meta_live(l, dw_first);  // the kernel gathers the live outside entries only
+    if (dev_upload(&s->d_tile_lbeg, l.lbeg.data(), l.lbeg.size()) || dev_upload(&s->d_tl_meta, as_int4(meta), meta.size()) ||
         dev_upload(&s->d_tl_col, l.col.data(), l.col.size()) || dev_upload(&s->d_tl_val, l.val.data(), l.val.size()))
       return 1;
     s->tl_has_nd = l.has_nd ? 1 : 0;

@@ -352,6 +352,18 @@ HostTileLists build_tile_lists(const HostCsr& dw, int64_t dim_dw, int64_t dw_fir
   return l;
 }
 
+std::vector<HostInt4> tile_meta_live(const HostTileLists& l, int64_t dw_first) {
+  std::vector<HostInt4> meta = l.meta;
+  for (size_t r = 0; r < meta.size(); r++) {
+    HostInt4& m = meta[r];
+    const int ob = m.x + m.y;
+    while (m.z % 4 != 1 && m.z > 0 && l.val[(size_t)(ob + m.z - 1)] == 0.0 &&
+           l.col[(size_t)(ob + m.z - 1)] == (int32_t)(dw_first + (int64_t)r))
+      m.z--;
+  }
+  return meta;
+}
+
 HostBlockLists build_block_lists(const HostCsr& dw, const HostFactored& f, int64_t dim_dw, int shift, int64_t lds_kb) {
   HostBlockLists b;
   // weight table: +/- every hop amplitude and Hnd coefficient, 0.0 at index 0 (padding entries)

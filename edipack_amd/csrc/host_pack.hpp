@@ -64,6 +64,9 @@ struct HostTileLists {
 };
 HostTileLists build_tile_lists(const HostCsr& dw, int64_t dim_dw, int64_t dw_first, int64_t dw_count,
                                const std::vector<int32_t>& tile_starts, const HostFactored* f);
+// the row meta as the kernel reads it: the count of hops leaving the chunk WITHOUT the padding of its last batch (the
+// trailing entries that name the row itself, which no live outside entry can: a row lies inside its own chunk)
+std::vector<HostInt4> tile_meta_live(const HostTileLists& l, int64_t dw_first);
 
 // per-row lists of the narrow-panel sweep with their weight table; fits == false: no blocked layout
 struct HostBlockLists {

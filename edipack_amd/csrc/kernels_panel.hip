@@ -436,8 +436,14 @@ __global__ void __launch_bounds__(kPanelNT)
 // global row), NormalArgs::tl_*; both lists are padded to whole batches of four with (own row, weight 0) entries, so a
 // batch is four accesses issued back to back behind one wait, never branched over entry by entry (hipcc guards every
 // load behind a branch with a full vmcnt(0)): from LDS a contiguous 1 KiB ds_read_b128 sweep without bank
-// conflicts, from L2 a 1 KiB segment.  Workgroups with equal blockIdx % 8 (one XCD under the observed round-robin
-// placement; speed only) walk the tasks of the same panel together.
+// conflicts, from L2 a 1 KiB segment.  The L2 is asked for nothing the result does not need: the padding of the
+// outside list is never gathered -- the row meta carries the count of LIVE outside entries (tile_meta_live), the full
+// batches run as said and the last, partly filled batch takes one of three straight-line paths (1, 2 or 3 gathers
+// back to back behind one wait) chosen by a scalar branch; and an Hnd partner row that lies inside the chunk (the
+// adjacent row in the sorted basis: all but the pairs a chunk cut separates) is read from the staged tile, every lane
+// its partner column's component directly, instead of a global segment load and four 64-bit shuffles.  Workgroups
+// with equal blockIdx % 8 (one XCD under the observed round-robin placement; speed only) walk the tasks of the same
+// panel together.
 constexpr int kTileSeg = 64;       // double2 per staged row segment (128 columns)
 constexpr int kTileRowsPerWave = 4;
 constexpr int kTileMaxRows = kTileRowsPerWave * 16;  // 1024-thread workgroups; 512-thread ones take half as many
@@ -589,12 +595,13 @@ __global__ void __launch_bounds__(NT)
     }
     __syncthreads();
     auto row_sum = [&](int r, double2 s) -> double2 {
-      const int4 m = lmeta[r];  // first entry, hops inside the chunk, hops leaving it, Hnd terms (LDS broadcast)
+      const int4 m = lmeta[r];  // first entry, hops inside the chunk, live hops leaving it, Hnd terms (LDS broadcast)
       const int mb = __builtin_amdgcn_readfirstlane(m.x), ni = __builtin_amdgcn_readfirstlane(m.y),
                 no = __builtin_amdgcn_readfirstlane(m.z), nn = __builtin_amdgcn_readfirstlane(m.w);
-      // hops that leave the chunk first (L2 latency), then the staged ones
-      const int ob = mb + ni, oe = ob + no;
-      for (int jb = ob; jb < oe; jb += kTileBatch) {
+      // hops that leave the chunk first (L2 latency), then the staged ones.  no counts the LIVE entries: the padding
+      // of the last batch is never gathered
+      const int ob = mb + ni, of = ob + (no & ~(kTileBatch - 1)), oe = ob + ((no + kTileBatch - 1) & ~(kTileBatch - 1));
+      for (int jb = ob; jb < of; jb += kTileBatch) {
         const int4 cw = *reinterpret_cast<const int4*>(lcol + jb);
         const double2 wa = *reinterpret_cast<const double2*>(lval + jb);
         const double2 wb = *reinterpret_cast<const double2*>(lval + jb + 2);
@@ -610,6 +617,36 @@ __global__ void __launch_bounds__(NT)
         s.y += wb.x * y2.y;
         s.x += wb.y * y3.x;
         s.y += wb.y * y3.y;
+      }
+      if (const int rem = no & (kTileBatch - 1)) {  // the last batch: one straight-line path per live count
+        const int4 cw = *reinterpret_cast<const int4*>(lcol + of);
+        const double2 wa = *reinterpret_cast<const double2*>(lval + of);
+        const double wb = lval[of + 2];
+        const double* q0 = &vb[(int64_t)__builtin_amdgcn_readfirstlane(cw.x) * RS + cc];
+        const double* q1 = &vb[(int64_t)__builtin_amdgcn_readfirstlane(cw.y) * RS + cc];
+        const double* q2 = &vb[(int64_t)__builtin_amdgcn_readfirstlane(cw.z) * RS + cc];
+        if (rem == 1) {
+          const double2 y0 = ld2(q0);
+          s.x += wa.x * y0.x;
+          s.y += wa.x * y0.y;
+        } else if (rem == 2) {
+          const double2 y0 = ld2(q0);
+          const double2 y1 = ld2(q1);
+          s.x += wa.x * y0.x;
+          s.y += wa.x * y0.y;
+          s.x += wa.y * y1.x;
+          s.y += wa.y * y1.y;
+        } else {
+          const double2 y0 = ld2(q0);
+          const double2 y1 = ld2(q1);
+          const double2 y2 = ld2(q2);
+          s.x += wa.x * y0.x;
+          s.y += wa.x * y0.y;
+          s.x += wa.y * y1.x;
+          s.y += wa.y * y1.y;
+          s.x += wb * y2.x;
+          s.y += wb * y2.y;
+        }
       }
       for (int jb = mb; jb < ob; jb += kTileBatch) {
         const int4 cw = *reinterpret_cast<const int4*>(lcol + jb);
@@ -638,12 +675,23 @@ __global__ void __launch_bounds__(NT)
           const uint32_t j1 = ju2[(2 * (tag - 1) + 1) * 64 + lane];
           const bool v0 = j0 != 0xFFFFFFFFu, v1 = j1 != 0xFFFFFFFFu;
           const double w0 = v0 ? ((j0 >> 31) ? -w : w) : 0.0, w1 = v1 ? ((j1 >> 31) ? -w : w) : 0.0;
-          // the partner row's segment, coalesced like a down hop; the partner columns sit a few lanes away
-          const double2 y = ld2(&vb[prow * RS + cc]);
-          const int l0 = (int)((j0 >> 1) & 63u), l1 = (int)((j1 >> 1) & 63u);
-          const double s0x = __shfl(y.x, l0, 64), s0y = __shfl(y.y, l0, 64);
-          const double s1x = __shfl(y.x, l1, 64), s1y = __shfl(y.y, l1, 64);
-          double p0 = (j0 & 1u) ? s0y : s0x, p1 = (j1 & 1u) ? s1y : s1x;
+          double p0, p1;
+          if (prow >= g0 && prow < g0 + nrows) {  // wave-uniform
+            // the partner row is staged (the adjacent row, nearly always): each lane reads its partner column's
+            // component from the tile, 128 doubles per row in column order
+            const double* trow = reinterpret_cast<const double*>(tile + (int)(prow - g0) * kTileSeg);
+            p0 = trow[j0 & 127u];
+            p1 = trow[j1 & 127u];
+          } else {
+            // the chunk cut separates the pair: the partner row's segment, coalesced like a down hop; the partner
+            // columns sit a few lanes away
+            const double2 y = ld2(&vb[prow * RS + cc]);
+            const int l0 = (int)((j0 >> 1) & 63u), l1 = (int)((j1 >> 1) & 63u);
+            const double s0x = __shfl(y.x, l0, 64), s0y = __shfl(y.y, l0, 64);
+            const double s1x = __shfl(y.x, l1, 64), s1y = __shfl(y.y, l1, 64);
+            p0 = (j0 & 1u) ? s0y : s0x;
+            p1 = (j1 & 1u) ? s1y : s1x;
+          }
           auto edge = [&](uint32_t jw) -> double {  // a partner column in a neighbouring panel
             const int64_t jc = (int64_t)(jw & 0x3FFFFFFFu);
             return BLK ? v_full[(jc >> 7) * a.blk_ps + prow * 128 + (jc & 127)] : v_full[prow * DimUp + jc];

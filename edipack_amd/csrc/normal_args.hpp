@@ -57,7 +57,8 @@ struct NormalArgs {
   const int32_t* tile_chunks;
   const int32_t* tile_lbeg;  // nchunks + 1: first list entry of a chunk's rows (tl_col / tl_val)
   int tile_list_cap;         // list entries of the fullest chunk
-  // per local row (tile form): tl_meta = (first entry, hops inside the row's chunk, hops leaving it, Hnd terms);
+  // per local row (tile form): tl_meta = (first entry, hops inside the row's chunk, padded to whole batches of four;
+  // LIVE hops leaving it -- their list is padded too, host_pack.hpp: tile_meta_live; Hnd terms);
   // tl_col: staged row index / global row / (partner row | tag << 24); tl_val: weights; both padded by 8 entries
   const int4* tl_meta;
   const int32_t* tl_col;
