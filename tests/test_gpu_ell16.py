@@ -36,14 +36,15 @@ def _layout_env(monkeypatch, layout):
         monkeypatch.setenv("EDIGPU_BLOCKED", "0")
 
 
-def _build(monkeypatch, ho, pm, sec, image, ell16):
+def _build(monkeypatch, ho, pm, sec, image, ell16, **shard):
+    """shard: dw_first / dw_count of a library-built handle that owns a slice of the down rows"""
     from edipack_amd.hamiltonian import SectorHamiltonian
     if ell16:
         monkeypatch.delenv("EDIGPU_ELL16", raising=False)
     else:
         monkeypatch.setenv("EDIGPU_ELL16", "0")
     if image == "library":
-        return SectorHamiltonian.normal_from_model(pm, *sec)
+        return SectorHamiltonian.normal_from_model(pm, *sec, **shard)
     return SectorHamiltonian.normal_from_arrays(ho.dimup, ho.dimdw, ho.hd, ho.up, ho.dw, ho.nd if ho.has_nd else None)
 
 

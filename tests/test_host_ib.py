@@ -128,3 +128,18 @@ def test_refusals(shim):
     _, pm = make_models("normal", "normal", 4, 1, seed=3)
     rc, _, _, msg = _check(shim, pm, 4, 4, 480)
     assert rc == 1 and "1..3" in msg
+
+
+def test_chunk_rows_of_the_long_row_cases(shim):
+    """tests/test_gpu_rows_long.py runs the position-order pairing on these (sector, chunk rows) pairs: each has an image.
+    3432 x 91 at 24 rows per chunk has none (runs of 21 down rows: 7 bath levels outside a chunk), which is why the
+    24-row case is on 3432 x 14."""
+    from tests.rows_long_cases import MODEL_SEED, POS_CASES
+    for (bath, norb, nbath, sec), rows in POS_CASES:
+        _, pm = make_models("normal", bath, norb, nbath, seed=MODEL_SEED)
+        rc, info, diff, msg = _check(shim, pm, *sec, rows)
+        assert rc == 0 and info[0] == 1 and diff < 1e-13, msg
+    (bath, norb, nbath, sec), _ = POS_CASES[0]
+    _, pm = make_models("normal", bath, norb, nbath, seed=MODEL_SEED)
+    rc, _, _, msg = _check(shim, pm, *sec, 24)
+    assert rc == 1 and "more than 6 bath levels outside a chunk" in msg

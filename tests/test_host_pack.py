@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests.common import make_models
+from tests.rows_long_cases import MODEL_SEED, SECTORS, SYNTH_DIMUP, ring_hup
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = 0xFFFFFFFF
@@ -203,8 +204,8 @@ def test_ell16_pads_an_odd_width_with_a_dead_half_word(shim):
     assert np.array_equal(decode_ell(img, True), csr_triples(a))
 
 
-def model_sector(lib, norb, nbath, nup, ndw):
-    _, pm = make_models("normal", "normal", norb, nbath, seed=11)
+def model_sector(lib, norb, nbath, nup, ndw, bath="normal", seed=11):
+    _, pm = make_models("normal", bath, norb, nbath, seed=seed)
     m = pm.to_c()
     dims = np.zeros(5, I64)
     assert lib.hp_build_normal(C.addressof(m), nup, ndw, ptr(dims)) == 0, lib.hp_error().decode()
@@ -243,6 +244,52 @@ def test_ell_images_of_a_real_hup(shim, norb, nbath, nup):
     assert img["typed"] == 1 and not img["pk16"].size
     img = encode_ell(shim, up, True, allow_typed=False)
     assert img["typed"] == 0 and img["pk"].size and np.array_equal(decode_ell(img, True), want)
+
+
+def check_long_row_image(lib, up):
+    """The image the rows kernel gets for `up`, as tests/test_gpu_rows_long.py assumes it: typed; with a 16-bit form
+    whose live half-words use bit 14 of the byte offset and the sign bit beside it for rows of 2049 to 4095 columns;
+    without one from 4096 columns on."""
+    img = encode_ell(lib, up, True)
+    assert img["typed"] == 1 and img["pk"].size
+    assert np.array_equal(decode_ell(img, True), csr_triples(up))
+    if up.nrow >= 4096:
+        assert not img["pk16"].size
+        return img
+    assert img["pk16"].size
+    check_ell16(img)
+    if up.nrow > 2048:
+        half = np.concatenate([img["pk16"] & 0xFFFF, img["pk16"] >> 16])
+        live = (half & 0x7FFF) != up.nrow * 8
+        assert (half[live] & 0x4000).any() and (half[live] & 0x8000).any()
+    return img
+
+
+@pytest.mark.parametrize("bath,norb,nbath,sec", SECTORS)
+def test_long_row_sectors_have_a_16bit_image(shim, bath, norb, nbath, sec):
+    """the Hup of the sectors of test_gpu_rows_long.py, as the library builds it and as the oracle hands it over"""
+    from oracle import oracle as O
+    up = model_sector(shim, norb, nbath, *sec, bath=bath, seed=MODEL_SEED)[0]
+    om, _ = make_models("normal", bath, norb, nbath, seed=MODEL_SEED)
+    ho = O.HNormal(om, *sec)
+    assert 2048 < up.nrow == ho.dimup <= 4095
+    check_long_row_image(shim, up)
+    check_long_row_image(shim, Csr.from_arrays(*ho.up))
+
+
+@pytest.mark.parametrize("n", SYNTH_DIMUP)
+def test_synthetic_long_rows_16bit_image_ends_at_4095(shim, n):
+    """the ring stencils of test_gpu_rows_long.py: six slots, 16-bit image up to 4095 columns and none beyond"""
+    up = Csr.from_arrays(*ring_hup(n))
+    dense = {(i, j): v for i in range(n) for j, v in up.rows[i]}
+    assert all(dense[(j, i)] == v for (i, j), v in dense.items())                # symmetric
+    # the first and last rows reach the last and first columns (three wrapped hops each), with both signs between them
+    wrapped = [v for j, v in up.rows[0] if j in (n - 1, n - 7, n - 1031)] + [v for j, v in up.rows[n - 1] if j in (0, 6, 1030)]
+    assert len(wrapped) == 6 and {np.sign(v) for v in wrapped} == {-1.0, 1.0}
+    img = check_long_row_image(shim, up)
+    assert img["width"] == 6 and bool(img["pk16"].size) == (n <= 4095)
+    if n == 4095:
+        assert n * 8 == 32760 and ((img["pk16"] & 0x7FFF) == 32760).any()        # the largest offset the format holds
 
 
 # ---------------------------------------------------------------- SELL ---------------------------------------------------------------
