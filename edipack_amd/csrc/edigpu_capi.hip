@@ -110,11 +110,10 @@ static void free_csr(DevCsr& d) {
   dev_free(d.val);
 }
 
-// device copies of the images of host_pack.hpp; the switches that choose among them are read here, at every call
-static int upload_ell(DevEll& e, const HostCsr& a, bool lds) {
+// device copies of the images of host_pack.hpp
+static int upload_ell(DevEll& e, const HostCsr& a, bool lds, const Switches& sw) {
   e = DevEll();
-  const char* e16 = getenv("EDIGPU_ELL16");
-  const HostEll h = encode_ell(a, lds, !getenv("EDIGPU_ELL_UNTYPED"), !(e16 && atoi(e16) == 0));
+  const HostEll h = encode_ell(a, lds, !sw.ell_untyped, sw.ell16);
   e.nrow = h.nrow;
   e.pitch = h.pitch;
   e.width = h.width;
@@ -125,9 +124,9 @@ static int upload_ell(DevEll& e, const HostCsr& a, bool lds) {
 }
 
 static int upload_sell(DevCsr& d, int64_t nrow, int64_t ncol, const int64_t* rowptr, const int32_t* col,
-                       const double* val, int cplx, bool is_loc, double max_pad = 1.6) {
-  if (getenv("EDIGPU_CSR_NOSELL")) return 0;
-  const HostSell h = encode_sell(nrow, ncol, rowptr, col, val, cplx, is_loc, max_pad, !getenv("EDIGPU_CSR_UNPACKED"));
+                       const double* val, int cplx, bool is_loc, const Switches& sw, double max_pad = 1.6) {
+  if (sw.csr_nosell) return 0;
+  const HostSell h = encode_sell(nrow, ncol, rowptr, col, val, cplx, is_loc, max_pad, !sw.csr_unpacked);
   if (!h.built) return 0;
   d.sell = 1;
   d.nslice = h.nslice;
@@ -202,11 +201,6 @@ static int finish_handle(edigpu_sector* s) {
   return 0;
 }
 
-static bool env_flag(const char* name) {
-  const char* e = getenv(name);
-  return e && e[0] == '1';
-}
-
 static void free_sb(DevSb* q) {
   if (!q) return;
   dev_free(q->urank); dev_free(q->ublist); dev_free(q->uslot); dev_free(q->rmap2); dev_free(q->up_vtab); dev_free(q->up_tloc);
@@ -237,22 +231,21 @@ static void free_ib(IbDev* p) {
 
 // Local-block tables (host_sb.hpp, kernels_sb.hip) on the layout of the impurity-block image d: when the sector is of that
 // form and a geometry of the kernels fits, the product and the fused step of the device-resident loops run on them
-// (EDIGPU_SB=0: keep the round-3 impurity-block kernels; EDIGPU_SB_VERBOSE=1 says why a sector gets none).
-static int setup_sb(IbDev* d, const HostNormal& hn, const HostIb& h, int chunk_rows) {
-  if (const char* e = getenv("EDIGPU_SB"))
-    if (atoi(e) == 0) return 0;
-  const bool verbose = getenv("EDIGPU_SB_VERBOSE") != nullptr;
+// (Switches::sb off: keep the round-3 impurity-block kernels).
+static int setup_sb(IbDev* d, const HostNormal& hn, const HostIb& h, const Switches& sw) {
+  if (!sw.sb) return 0;
+  const bool verbose = sw.sb_verbose;
+  const int chunk_rows = sw.ib_rows;
   auto skip = [&](const std::string& why) {
     if (verbose) fprintf(stderr, "edigpu: no local-block tables: %s\n", why.c_str());
     return 0;
   };
   const bool split = h.nhalf == 2;  // rows staged in halves: the local-block ROWS kernel per half, the impurity-block columns kernel
   if (split) {
-    // Opt-in (EDIGPU_SB_SPLIT=1): measured at Ns = 17 the local-block rows kernel on half rows takes 3.30 + 3.15 ms against
+    // Opt-in (Switches::sb_split): measured at Ns = 17 the local-block rows kernel on half rows takes 3.30 + 3.15 ms against
     // 2.77 + 2.58 ms for the round-3 kernel (kernels_sb_impl.hpp, TOP) -- the gathers of the hop over the top level cost it
     // more than the cheaper walk gains.  Kept, tested (CPU shim and GPU), off.
-    const char* e = getenv("EDIGPU_SB_SPLIT");
-    if (!e || atoi(e) == 0) return skip("rows staged in halves (EDIGPU_SB_SPLIT=1 takes the local-block rows kernel)");
+    if (!sw.sb_split) return skip("rows staged in halves (EDIGPU_SB_SPLIT=1 takes the local-block rows kernel)");
   }
   const int nb0 = sb_nb0(h.norb);
   if (nb0 < 1 || hn.ns - h.norb - nb0 < 2) return skip("too few bath levels");
@@ -260,12 +253,13 @@ static int setup_sb(IbDev* d, const HostNormal& hn, const HostIb& h, int chunk_r
   if (slots < 1) return skip("not of the local-block form");
   const int plen_rows = split ? std::max(h.half[0].npanels, h.half[1].npanels) * kIbPanel : h.npanels * kIbPanel;
   HostSb t;
-  build_sb(hn, h, nb0, chunk_rows, 64 * slots, 1, sb_cols_waves(), t, sb_cols_gs());  // (the class stride of the row image: needed to choose the geometry)
+  const int gs = sb_cols_gs(sw.sb_cw), waves = sb_cols_waves(sw.sb_cw);
+  build_sb(hn, h, nb0, chunk_rows, 64 * slots, 1, waves, t, gs, sw.sb_amode);  // (the class stride of the row image: needed to choose the geometry)
   if (!t.valid) return skip(t.why);
   int nt = 0, nbt = 0;
-  if (!sb_rows_config(h.norb, slots, plen_rows, t.rcs, &nt, &nbt)) return skip("no geometry of the rows kernel fits");
+  if (!sb_rows_config(h.norb, slots, plen_rows, t.rcs, sw.sb_nt, sw.sb_nbt, &nt, &nbt)) return skip("no geometry of the rows kernel fits");
   if (split && nbt > 4) return skip("rows staged in halves: more than 4 blocks per thread");
-  build_sb(hn, h, nb0, chunk_rows, nt, nbt, sb_cols_waves(), t, sb_cols_gs());
+  build_sb(hn, h, nb0, chunk_rows, nt, nbt, waves, t, gs, sw.sb_amode);
   if (!t.valid) return skip(t.why);
   if (split && t.amode != 0) return skip("rows staged in halves: all-orbital walk only");
   std::unique_ptr<DevSb, void (*)(DevSb*)> q(new DevSb(), free_sb);
@@ -323,20 +317,18 @@ static int setup_sb(IbDev* d, const HostNormal& hn, const HostIb& h, int chunk_r
 }
 
 // Short rows (IbDev::PosRows): Hup and the diagonal table in POSITION order for the generic LDS row kernel, which then
-// works on the padded panel layout beside the local-block columns kernel.  Built on request (EDIGPU_POSROWS=1) when the
-// sector has local-block tables with whole rows; for rows shorter than EDIGPU_IB_MINROW the block image is then built for it.
+// works on the padded panel layout beside the local-block columns kernel.  Built on request (Switches::posrows) when the
+// sector has local-block tables with whole rows; for rows shorter than Switches::ib_min_row_bytes() the block image is then built for it.
 static int setup_pos_rows(edigpu_sector* s, const HostNormal& hn, const HostIb& h) {
   IbDev* d = s->ib;
   if (!d || !d->sb || d->sb->nhalf != 1 || !s->factored || !hn.fac.valid) return 0;
-  const char* e = getenv("EDIGPU_POSROWS");
-  // Opt-in (EDIGPU_POSROWS=1).  Measured on config 2: the plain product gains (0.110 against 0.119 ms: 0.43 against 0.40
+  // Opt-in.  Measured on config 2: the plain product gains (0.110 against 0.119 ms: 0.43 against 0.40
   // of the peak) but the fused Lanczos step loses (0.166 against 0.158 ms per step, 6020 against 6350 it/s): on 16-column
   // panels a row is 215 pieces 439 KB apart, and the fused row kernel's five streams of them take 100-120 us where the
   // 128-column panels of the default loop (27 pieces per row) take 81.
-  const bool on = e && atoi(e) != 0;
-  if (!on) return 0;
+  if (!s->sw.posrows) return 0;
   const int plen = d->plen;
-  const int td = normal_pick_rows_per_block(plen, hn.dim_dw);
+  const int td = normal_pick_rows_per_block(plen, hn.dim_dw, s->sw.rows_td);
   if (td < 1) return 0;
   const HostCsr& up = s->h_up;
   HostCsr pu;
@@ -359,7 +351,7 @@ static int setup_pos_rows(edigpu_sector* s, const HostNormal& hn, const HostIb& 
       pu.val[(size_t)at] = up.val[(size_t)q];
     }
   }
-  if (upload_ell(d->pr.ell, pu, true)) return 1;
+  if (upload_ell(d->pr.ell, pu, true, s->sw)) return 1;
   if (!d->pr.ell.pk || !d->pr.ell.typed) {  // the fast path of the row kernel only
     free_ell(d->pr.ell);
     d->pr.ell = DevEll();
@@ -372,20 +364,20 @@ static int setup_pos_rows(edigpu_sector* s, const HostNormal& hn, const HostIb& 
   if (dev_upload(&d->pr.eux, ex.data(), ex.size())) return 1;
   d->pr.td = td;
   d->pr.on = true;
-  if (getenv("EDIGPU_SB_VERBOSE")) fprintf(stderr, "edigpu: rows half on the generic row kernel in position order (plen %d, %d rows per workgroup, ELL width %d)\n", plen, td, d->pr.ell.width);
+  if (s->sw.sb_verbose) fprintf(stderr, "edigpu: rows half on the generic row kernel in position order (plen %d, %d rows per workgroup, ELL width %d)\n", plen, td, d->pr.ell.width);
   return 0;
 }
 
 // device copy of the impurity-block image; leaves s->ib null (and returns 0) when the sector is not of that form
-static int setup_ib(edigpu_sector* s, const HostNormal& hn, int chunk_rows) {
+static int setup_ib(edigpu_sector* s, const HostNormal& hn) {
+  const Switches& sw = s->sw;
   HostIb h;
   // Rows whose image does not fit the LDS beside the tables are staged one half at a time (host_ib.hpp IbUpHalf);
-  // EDIGPU_IB_SPLIT=1 forces that form on any sector (tests), =0 leaves such sectors to the generic kernels.
-  int lds_budget = 156 * 1024;
-  if (const char* e = getenv("EDIGPU_IB_SPLIT")) lds_budget = atoi(e) != 0 ? -1 : 0;
-  build_ib(hn, chunk_rows, h, lds_budget);
+  // Switches::ib_split forces that form on any sector (tests) or leaves such sectors to the generic kernels.
+  const int lds_budget = !sw.ib_split ? 156 * 1024 : *sw.ib_split != 0 ? -1 : 0;
+  build_ib(hn, sw.ib_rows, h, lds_budget);
   if (!h.valid) {
-    if (getenv("EDIGPU_IB_VERBOSE")) fprintf(stderr, "edigpu: no impurity-block image: %s\n", h.why.c_str());
+    if (sw.ib_verbose) fprintf(stderr, "edigpu: no impurity-block image: %s\n", h.why.c_str());
     return 0;
   }
   int nt = 0, nbt = 0;
@@ -395,11 +387,11 @@ static int setup_ib(edigpu_sector* s, const HostNormal& hn, int chunk_rows) {
     const IbUpHalf &a = h.half[0], &b = h.half[1];
     const int rimg = std::max(a.rimg_len, b.rimg_len);
     if (!ib_rows_config(h.norb, h.up.nb - 1, (int)std::max(a.ublist.size(), b.ublist.size()),
-                        std::max(a.npanels, b.npanels) * kIbPanel, rimg, &nt, &nbt, true))
+                        std::max(a.npanels, b.npanels) * kIbPanel, rimg, sw.ib_nt, &nt, &nbt, true))
       return 0;
     rows_lds = ib_rows_lds_bytes(h.up.nb - 1, rimg);
   } else {
-    if (!ib_rows_config(h.norb, h.up.nb, (int)h.ublist.size(), plen, h.rimg_len, &nt, &nbt)) return 0;
+    if (!ib_rows_config(h.norb, h.up.nb, (int)h.ublist.size(), plen, h.rimg_len, sw.ib_nt, &nt, &nbt)) return 0;
     rows_lds = ib_rows_lds_bytes(h.up.nb, h.rimg_len);
   }
   int mcb = 8;
@@ -416,19 +408,16 @@ static int setup_ib(edigpu_sector* s, const HostNormal& hn, int chunk_rows) {
   d->nchunks = (int)h.chunk_row.size() - 1;
   d->max_chunk_rows = h.max_chunk_rows;
   d->max_chunk_blocks = mcb;
-  {
-    // workgroups per chunk of the columns kernel (EDIGPU_IB_NSUB, default 1).  Two per chunk make one panel's tasks cover
-    // the 64 workgroup slots of an XCD, so that a single panel is in flight per L2 -- measured SLOWER (Ns = 16: 2.79
-    // against 2.42 ms per product, Ns = 15: 0.69 against 0.64): staging the chunk twice costs more than the gathers that
-    // then hit the L2 save.
-    const char* e = getenv("EDIGPU_IB_NSUB");
-    d->nsub = e ? std::max(1, std::min(8, atoi(e))) : 1;
-  }
+  // workgroups per chunk of the columns kernel.  Two per chunk make one panel's tasks cover the 64 workgroup slots of an
+  // XCD, so that a single panel is in flight per L2 -- measured SLOWER (Ns = 16: 2.79 against 2.42 ms per product,
+  // Ns = 15: 0.69 against 0.64): staging the chunk twice costs more than the gathers that then hit the L2 save.
+  d->nsub = sw.ib_nsub;
+  d->cols2 = sw.ib_cols2;
   d->nterms = h.nterms;
   d->dim_up = hn.dim_up;
   d->dim_dw = hn.dim_dw;
   d->ps = hn.dim_dw * kIbPanel;
-  if (const char* e = getenv("EDIGPU_IB_PSPAD")) d->ps += (int64_t)std::max(0, atoi(e)) / 2 * 2;  // doubles between two panels (tuning)
+  d->ps += (int64_t)sw.ib_pspad / 2 * 2;  // doubles between two panels (tuning)
   d->len = (int64_t)h.npanels * d->ps;
   d->rows_nt = nt;
   d->rows_nbt = nbt;
@@ -497,7 +486,7 @@ static int setup_ib(edigpu_sector* s, const HostNormal& hn, int chunk_rows) {
     }
   }
   s->ib = d.release();
-  if (setup_sb(s->ib, hn, h, chunk_rows)) return 1;
+  if (setup_sb(s->ib, hn, h, sw)) return 1;
   return setup_pos_rows(s, hn, h);
 }
 
@@ -518,20 +507,20 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
   s->h_up = up;
   s->h_dw = dw;
   std::vector<int32_t> tile_starts;  // row chunks of the LDS-tiled panel sweep (empty: not planned)
-  s->rows_per_block = normal_pick_rows_per_block(dim_up, dw_count);
+  const Switches& sw = s->sw;
+  s->rows_per_block = normal_pick_rows_per_block(dim_up, dw_count, sw.rows_td);
   // Rows longer than the LDS (rows_per_block == 0): staged in column parts when the typed LDS image exists
-  // (normal_rows_kernel SPLIT); EDIGPU_ROW_SPLIT=<parts> forces it on any sector (tests), =0 switches it off.
+  // (normal_rows_kernel SPLIT); Switches::row_split forces it on any sector (tests) or switches it off.
   {
-    const char* e = getenv("EDIGPU_ROW_SPLIT");
     int parts = 0;
-    if (e) {
-      parts = atoi(e);
+    if (sw.row_split) {
+      parts = *sw.row_split;
       if (parts > 1) s->rows_per_block = 0;
     } else if (s->rows_per_block == 0) {
       parts = (int)(((dim_up + 2) * 8 + 140 * 1024 - 1) / (140 * 1024));
     }
     if (s->rows_per_block == 0 && parts > 1 && dim_up >= 4 * parts) {
-      if (upload_ell(s->up_ell, up, true)) return 1;
+      if (upload_ell(s->up_ell, up, true, sw)) return 1;
       if (s->up_ell.typed && s->up_ell.pk) {
         s->row_split = parts;
       } else {
@@ -540,25 +529,18 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
       }
     }
   }
-  if (s->row_split == 1 && upload_ell(s->up_ell, up, s->rows_per_block != 0)) return 1;
+  if (s->row_split == 1 && upload_ell(s->up_ell, up, s->rows_per_block != 0, sw)) return 1;
   if (upload_csr(s->dw, dim_dw, dw.rowptr.data(), dw.col.data(), dw.val.data(), 0)) return 1;
   for (int64_t i = 0; i < dim_dw; i++)
     s->dw_maxrow = std::max<int>(s->dw_maxrow, (int)(dw.rowptr[i + 1] - dw.rowptr[i]));
   {
     // panel sweep variant (kernels_panel.hip).  Measured: cache-resident sectors are 13 % SLOWER with the two-column
-    // panels (fewer, fatter waves), hence the size gate; EDIGPU_PANEL_VEC2_MIN (rows) moves it (tests force the
-    // large-sector kernels on small sectors), EDIGPU_PANEL_VEC2=0 / EDIGPU_PANEL_TILE=0 switch the variants off,
-    // EDIGPU_TILE_ROWS sets the chunk length (KiB of LDS per workgroup).
-    const char* e;
-    const bool vec2_env = !(e = getenv("EDIGPU_PANEL_VEC2")) || atoi(e) != 0;
-    const int64_t vec2_min = (e = getenv("EDIGPU_PANEL_VEC2_MIN")) ? atoll(e) : ((int64_t)1 << 21);
-    const bool tile_env = !(e = getenv("EDIGPU_PANEL_TILE")) || atoi(e) != 0;
-    int rmax = (e = getenv("EDIGPU_TILE_ROWS")) ? atoi(e) : 32;
-    if (rmax < 8) rmax = 8;
-    if (rmax > 64) rmax = 64;   // kTileMaxRows of kernels_panel.hip: 4 rows per wave (their results live in registers), 16 waves
-    if (vec2_env && dim_up >= 2 && dim_up * dw_count >= vec2_min) s->panel_mode = 1;
-    if (s->panel_mode == 1 && tile_env && dw_count > 0 && dim_dw < ((int64_t)1 << 24)) {
-      plan_tile_chunks(dw, dw_first, dw_count, rmax, tile_starts, s->tile_rows);
+    // panels (fewer, fatter waves), hence the size gate Switches::panel_vec2_min (tests force the large-sector kernels on
+    // small sectors).  Switches::tile_rows sets the chunk length (KiB of LDS per workgroup), at most kTileMaxRows of
+    // kernels_panel.hip: 4 rows per wave (their results live in registers), 16 waves.
+    if (sw.panel_vec2 && dim_up >= 2 && dim_up * dw_count >= sw.panel_vec2_min) s->panel_mode = 1;
+    if (s->panel_mode == 1 && sw.panel_tile && dw_count > 0 && dim_dw < ((int64_t)1 << 24)) {
+      plan_tile_chunks(dw, dw_first, dw_count, sw.tile_rows, tile_starts, s->tile_rows);
       s->tile_nchunks = (int)tile_starts.size() - 1;
       if (dev_upload(&s->d_tile_chunks, tile_starts.data(), tile_starts.size())) return 1;
       s->panel_mode = 2;
@@ -571,8 +553,8 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
     s->nd_nnz = s->has_nd ? built->nd_nnz : 0;
   }
   // library-built sectors keep the diagonal and Hnd in factored form on the device (the explicit
-  // arrays stay on the host for export); EDIGPU_NORMAL_EXPLICIT=1 forces the explicit image.
-  if (built && built->fac.valid && built->fac.nterms <= 16 && !env_flag("EDIGPU_NORMAL_EXPLICIT")) {
+  // arrays stay on the host for export); Switches::normal_explicit forces the explicit image.
+  if (built && built->fac.valid && built->fac.nterms <= 16 && !sw.normal_explicit) {
     const HostFactored& f = built->fac;
     s->factored = 1;
     s->fac_nimp = f.nimp;
@@ -600,8 +582,8 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
     if (s->has_nd && upload_csr(s->nd, s->nloc, nd_rowptr, nd_col, nd_val, 0)) return 1;
     // Hnd as its own SELL pass after the panel sweep (global columns): keeps the row kernel free of the CSR
     // row pointers and lets the Lanczos step stay fused (the dot partials move to this last pass)
-    if (s->has_nd && !env_flag("EDIGPU_ND_IN_ROWS") &&
-        upload_sell(s->nd, s->nloc, dim_up * dim_dw, nd_rowptr, nd_col, nd_val, 0, false, 16.0))
+    if (s->has_nd && !sw.nd_in_rows &&
+        upload_sell(s->nd, s->nloc, dim_up * dim_dw, nd_rowptr, nd_col, nd_val, 0, false, sw, 16.0))
       return 1;
   }
   if (s->panel_mode == 2) {
@@ -620,21 +602,16 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
   // levels with single bath levels (normal / hybrid baths), <= 3 orbitals.  The device-resident Lanczos loops then run
   // on its padded 16-column panel layout and its two kernels.  Measured (r3): 0.61 against 0.85 ms per product at
   // Ns = 15, 2.4 against 3.3 ms at Ns = 16, but 0.18 against 0.13 ms on config 2, whose 27 KB rows leave the generic
-  // row kernel four workgroups per CU -- so the default takes it for rows of more than EDIGPU_IB_MINROW bytes (40 KB).
-  // EDIGPU_IB=0 switches it off, EDIGPU_IB_MIN sets the smallest sector (elements; tests force it on small ones with
-  // EDIGPU_IB_MIN=0, which also lifts the row gate), EDIGPU_IB_ROWS the rows of a staged chunk (<= 480).
+  // row kernel four workgroups per CU -- so the default takes it for rows of more than Switches::ib_min_row_bytes()
+  // (40 KB) in sectors of at least Switches::ib_min elements (tests force it on small ones with 0, which also lifts the
+  // row gate).
   if (s->factored && built && built->norb > 0 && dw_first == 0 && dw_count == dim_dw) {
-    const char* e;
-    const bool on = !(e = getenv("EDIGPU_IB")) || atoi(e) != 0;
-    const int64_t min_rows = (e = getenv("EDIGPU_IB_MIN")) ? atoll(e) : ((int64_t)1 << 21);
-    int chunk_rows = (e = getenv("EDIGPU_IB_ROWS")) ? atoi(e) : 480;
-    chunk_rows = std::max(4, std::min(chunk_rows, 480));
-    const int64_t min_row_bytes = (e = getenv("EDIGPU_IB_MINROW")) ? atoll(e) : (min_rows == 0 ? 0 : 40 * 1024);
+    const int64_t min_rows = sw.ib_min;
     // Replica / general baths (hops between the bath levels of a replica, host_ib.hpp IbSide::pmask): the image and its
     // kernels hold them as pair hops of whole blocks -- tested, golden-pinned -- but every lane runs through every pair
     // (half of them idle), which costs as much as the walk over the levels: measured on the 3-orbital x 4-replica sector
     // of Ns = 15 the product takes 1.16 ms on the blocks against 0.81 ms on the generic kernels.  So the default keeps
-    // such sectors on the generic kernels; EDIGPU_IB_PAIRS=1 (or EDIGPU_IB_MIN=0, the tests) takes the image.
+    // such sectors on the generic kernels; Switches::ib_pairs (or ib_min == 0, the tests) takes the image.
     bool pairs = false;
     for (int sp = 0; sp < 2 && !pairs; sp++) {
       const std::vector<double>& a = built->ob_a[sp];
@@ -647,13 +624,11 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
               break;
             }
     }
-    const bool pairs_ok = !pairs || min_rows == 0 || env_flag("EDIGPU_IB_PAIRS");
-    // Rows below EDIGPU_IB_MINROW: the block ROWS kernels lose to the generic LDS row kernel there; the image is still built
+    const bool pairs_ok = !pairs || min_rows == 0 || sw.ib_pairs;
+    // Rows below ib_min_row_bytes(): the block ROWS kernels lose to the generic LDS row kernel there; the image is still built
     // when that kernel can take the rows half on the image's layout (setup_pos_rows), and dropped again when it cannot.
-    const bool short_rows = dim_up * 8 < min_row_bytes;
-    const bool posrows_ok = (e = getenv("EDIGPU_POSROWS")) && atoi(e) != 0;
-    if (on && pairs_ok && s->nloc >= min_rows && (!short_rows || posrows_ok) && !env_flag("EDIGPU_LANCZOS_UNFUSED") &&
-        setup_ib(s, *built, chunk_rows))
+    const bool short_rows = dim_up * 8 < sw.ib_min_row_bytes();
+    if (sw.ib && pairs_ok && s->nloc >= min_rows && (!short_rows || sw.posrows) && !sw.lanczos_unfused && setup_ib(s, *built))
       return 1;
     if (s->ib && short_rows && !s->ib->pr.on) {
       free_ib(s->ib);
@@ -664,33 +639,26 @@ static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_
   // Panel-major vector layout for the device-resident Lanczos loop (normal_args.hpp): large
   // factored whole sectors whose rows fit the LDS row kernel.  Default: 128-column panels (1 KiB line-aligned segments)
   // swept by the LDS-tiled kernel -- measured 6 % (config 2), 14 % (Ns = 15) and 8 % (Ns = 16) faster per product than
-  // the same kernel on the natural layout, whose segments start at arbitrary 8-byte offsets.  EDIGPU_BLOCKED=0 keeps the
-  // natural layout; EDIGPU_BLOCKED_W=16 / 32 / 64 selects the narrow-panel sweep (normal_dw_blk_kernel: panels that
-  // stay in one L2, fetch traffic 1.1-1.9x of V + result instead of 1.8-5x, but bound by the L2's gather throughput and
-  // 10-60 % slower: an experiment that is kept, tested, off); EDIGPU_BLOCKED_MIN the smallest sector (rows),
-  // EDIGPU_BLOCKED_LDS_KB the staged block of the narrow sweep.
+  // the same kernel on the natural layout, whose segments start at arbitrary 8-byte offsets.  Panels of 16 / 32 / 64
+  // columns (Switches::blocked_w) take the narrow-panel sweep (normal_dw_blk_kernel: panels that stay in one L2, fetch
+  // traffic 1.1-1.9x of V + result instead of 1.8-5x, but bound by the L2's gather throughput and 10-60 % slower: an
+  // experiment that is kept, tested, off).
   if (!s->ib && s->factored && built && dw_first == 0 && dw_count == dim_dw && s->rows_per_block >= 1 && s->row_split == 1 &&
       dim_dw <= 65535 && dim_up >= 64) {
-    const char* e;
-    const bool on = !(e = getenv("EDIGPU_BLOCKED")) || atoi(e) != 0;
-    const int64_t min_rows = (e = getenv("EDIGPU_BLOCKED_MIN")) ? atoll(e) : ((int64_t)1 << 21);
-    int shift = 7;
-    if ((e = getenv("EDIGPU_BLOCKED_W"))) {
-      const int w = atoi(e);
-      shift = w == 128 ? 7 : w == 64 ? 6 : w == 32 ? 5 : w == 16 ? 4 : 0;
-    }
+    const bool on = sw.blocked;
+    const int64_t min_rows = sw.blocked_min;
+    const int shift = sw.blocked_shift();
     const HostFactored& f = built->fac;
     if (on && shift == 7 && s->nloc >= min_rows && s->panel_mode == 2 && (f.nterms == 0 || s->tl_has_nd)) {
       // 128-column panels: the tiled sweep and its lists as they are, on line-aligned contiguous panels
       s->blk_shift = 7;
-      s->blk_tail_balance = !(e = getenv("EDIGPU_TILE_BALANCE")) || atoi(e) != 0;
+      s->blk_tail_balance = sw.tile_balance;
       s->blk_rows = s->tile_rows;
       s->blk_ps = dim_dw << 7;
       s->blk_len = ((dim_up + 127) >> 7) * s->blk_ps;
     } else if (on && shift && shift < 7 && s->nloc >= min_rows && f.nterms <= 16) {
-      // narrow panels: lists over LDS blocks of EDIGPU_BLOCKED_LDS_KB (default 32) of staged segments
-      const int64_t lds_kb = (e = getenv("EDIGPU_BLOCKED_LDS_KB")) ? atoll(e) : 32;
-      const HostBlockLists b = build_block_lists(dw, f, dim_dw, shift, lds_kb);
+      // narrow panels: lists over LDS blocks of Switches::blocked_lds_kb KiB of staged segments
+      const HostBlockLists b = build_block_lists(dw, f, dim_dw, shift, sw.blocked_lds_kb);
       if (b.fits) {
         s->blk_list_cap = b.list_cap;
         if (dev_upload(&s->d_bl_lend, b.lend.data(), b.lend.size()) || dev_upload(&s->d_bl_meta, as_int4(b.meta), b.meta.size()) ||
@@ -743,8 +711,8 @@ static int setup_flat(edigpu_sector* s, int64_t nrow_local, int64_t ncol_global,
   }
   if (upload_csr(s->loc, nrow_local, rpl.data(), cl.data(), vl.data(), cplx)) return 1;
   if (upload_csr(s->nonloc, nrow_local, rpn.data(), cn.data(), vn.data(), cplx)) return 1;
-  if (upload_sell(s->loc, nrow_local, nrow_local, rpl.data(), cl.data(), vl.data(), cplx, true)) return 1;
-  if (upload_sell(s->nonloc, nrow_local, ncol_global, rpn.data(), cn.data(), vn.data(), cplx, false)) return 1;
+  if (upload_sell(s->loc, nrow_local, nrow_local, rpl.data(), cl.data(), vl.data(), cplx, true, s->sw)) return 1;
+  if (upload_sell(s->nonloc, nrow_local, ncol_global, rpn.data(), cn.data(), vn.data(), cplx, false, s->sw)) return 1;
   return finish_handle(s);
 }
 
@@ -1115,8 +1083,7 @@ static int tql2(int n, std::vector<double>& d, std::vector<double>& e, std::vect
 
 // enqueue one Lanczos step (iter is 0-based); vin/vout/tmp live in the workspace
 static bool flat_lanczos_fusable(const edigpu_sector* s) {
-  static const bool off = getenv("EDIGPU_LANCZOS_UNFUSED") != nullptr;
-  if (off || s->nloc != s->dim || s->nloc == 0 || s->nph > 0) return false;
+  if (s->sw.lanczos_unfused || s->nloc != s->dim || s->nloc == 0 || s->nph > 0) return false;
   if (s->kind == 2) return true;
   return s->kind == 1 && csr_lanczos_fusable(s->loc) && s->nonloc.nnz == 0;
 }
@@ -1130,8 +1097,8 @@ static int lanczos_step(edigpu_sector* s, int iter, int nlanc, hipStream_t st) {
   const bool ib_split = s->kind == 0 && s->ib && s->ib->nhalf == 2 && s->lz_blocked;
   if (normal_lanczos_fusable(s) || ib_split) {
     // rotate (and the pending axpy) fused into the row kernel, alpha and <Q|Q> into the panel sweep
-    // (kernels_normal.hip); EDIGPU_LANCZOS_EXACTBETA=1 keeps the separate axpy+norm kernel
-    const bool exactbeta = s->lz_exactbeta;  // read once per run in lanczos_prepare
+    // (kernels_normal.hip); LoopSwitches::lanczos_exactbeta keeps the separate axpy+norm kernel
+    const bool exactbeta = s->lz.lanczos_exactbeta;
     int np = 0;
     bool finalized = false;
     bool in_x = false;
@@ -1162,12 +1129,11 @@ static int lanczos_step(edigpu_sector* s, int iter, int nlanc, hipStream_t st) {
   // product goes to its own buffer; the one-reduction recurrence around it -- lazy rotate with the pending axpy, Q += H P
   // with the three sums, one finalize -- moves 8 vector passes per step where the literal form moves 11.  The three-sum
   // beta (k_finalize_ab) is what makes this safe: with beta^2 = <w|w> - alpha^2 the same loop made the lowest Ritz value
-  // jitter at 6e-14 |H| (round 1, removed then).  EDIGPU_LANCZOS_EXACTBETA=1 / EDIGPU_LANCZOS_UNFUSED=1: the literal form.
-  static const bool literal = getenv("EDIGPU_LANCZOS_UNFUSED") != nullptr;
+  // jitter at 6e-14 |H| (round 1, removed then).  LoopSwitches::lanczos_exactbeta / Switches::lanczos_unfused: the literal form.
   auto product = [&]() -> int {  // tmp <- H vin, in the layout lanczos_prepare chose
     return s->lz_blocked ? launch_normal_blocked(s, s->d_vin, s->d_tmp, st) : apply_any(s, s->d_vin, s->d_vin, s->d_tmp, 3, st);
   };
-  if (literal || s->lz_exactbeta) {
+  if (s->sw.lanczos_unfused || s->lz.lanczos_exactbeta) {
     if (iter > 0 && lz_rotate(s->d_vin, s->d_vout, len, s->d_scal, st)) return 1;
     if (product()) return 1;
     if (lz_alpha(s->d_vin, s->d_vout, s->d_tmp, len, s->d_partial, s->d_scal, iter, nlanc, st)) return 1;
@@ -1181,10 +1147,10 @@ static int lanczos_step(edigpu_sector* s, int iter, int nlanc, hipStream_t st) {
 }
 
 static int lanczos_prepare(edigpu_sector* s, int nlanc, double threshold, hipStream_t st) {
-  s->lz_exactbeta = getenv("EDIGPU_LANCZOS_EXACTBETA") != nullptr;
+  s->lz = LoopSwitches::sample();
   // the recurrence of a large factored normal-mode sector runs on panel-major vectors (set-up decides, blk_shift)
   // (the impurity-block image with rows staged in halves: rows_per_block == 0 there, its step is in launch_ib_lanczos)
-  const bool ib_whole = s->kind == 0 && s->ib && s->nph == 0 && s->nloc == s->dim && !getenv("EDIGPU_LANCZOS_UNFUSED");
+  const bool ib_whole = s->kind == 0 && s->ib && s->nph == 0 && s->nloc == s->dim && !s->sw.lanczos_unfused;
   s->lz_blocked = s->kind == 0 && (s->blk_shift > 0 || s->ib) && s->nph == 0 &&
                   (normal_lanczos_fusable(s) || (ib_whole && s->ib->nhalf == 2));
   s->lz_len = s->lz_blocked ? (s->ib ? s->ib->len : s->blk_len) : s->ws_len;
@@ -1215,7 +1181,7 @@ static int lanczos_seed(edigpu_sector* s, const double* src, uint64_t seed, hipS
   if (s->lz_blocked && s->ib) {
     if (vec_to_ib(s->ib, s->d_tmp, s->d_vin, st)) return 1;
     if (s->ib->ps != s->ib->dim_dw * kIbPanel) {
-      // padded panel stride (EDIGPU_IB_PSPAD): the doubles between two panels are written by no kernel and enter the vector
+      // padded panel stride (Switches::ib_pspad): the doubles between two panels are written by no kernel and enter the vector
       // sums; the two other buffers may hold anything there (d_tmp just held the vector in the reference's layout)
       EDIGPU_HIP(hipMemsetAsync(s->d_tmp, 0, (size_t)s->ib->len * sizeof(double), st));
       EDIGPU_HIP(hipMemsetAsync(s->d_vout, 0, (size_t)s->ib->len * sizeof(double), st));
@@ -1226,24 +1192,22 @@ static int lanczos_seed(edigpu_sector* s, const double* src, uint64_t seed, hipS
   return 0;
 }
 
-// Steps [from, to) of the current recurrence.  EDIGPU_LANCZOS_GRAPH=1: the later steps of a small sector -- identical
+// Steps [from, to) of the current recurrence.  Switches::lanczos_graph: the later steps of a small sector -- identical
 // launches once the step index lives on the device (k_finalize_ab, iter < 0) -- are captured once as a hipGraph of
 // kGraphSteps steps and replayed; the executable stays with the handle for the next run of the same length.
 // OPT-IN because it buys nothing here: measured on configs 1 / 3 / 4 (10.9 / 20.3 / 23.8 us per step with the graph,
 // 11.4 / 20.4 / 23.1 without), i.e. the three dependent kernels of a step are bound by their own dispatch-to-completion
 // latency on the device, not by host-side launch cost; fusing the finalize into the sweep's last workgroup is what would
-// shorten a small sector's step.  EDIGPU_LANCZOS_GRAPH_MAX sets the largest sector (rows) that uses the graph.
+// shorten a small sector's step.
 static int lanczos_run(edigpu_sector* s, int from, int to, int nlanc, hipStream_t st) {
   constexpr int kGraphSteps = 8;
-  static const bool graph_on = getenv("EDIGPU_LANCZOS_GRAPH") && atoi(getenv("EDIGPU_LANCZOS_GRAPH")) != 0;
-  static const int64_t graph_max = getenv("EDIGPU_LANCZOS_GRAPH_MAX") ? atoll(getenv("EDIGPU_LANCZOS_GRAPH_MAX")) : ((int64_t)1 << 21);
-  static const bool literal = getenv("EDIGPU_LANCZOS_UNFUSED") != nullptr;
   int it = from;
   if (it == 0 && it < to) {
     if (lanczos_step(s, 0, nlanc, st)) return 1;
     it = 1;
   }
-  const bool eligible = graph_on && !literal && !s->lz_exactbeta && !s->lz_graph_failed && s->nloc <= graph_max &&
+  const bool eligible = s->sw.lanczos_graph && !s->sw.lanczos_unfused && !s->lz.lanczos_exactbeta && !s->lz_graph_failed &&
+                        s->nloc <= s->sw.lanczos_graph_max &&
                         s->nph == 0 && s->kind != 4 && to - it >= kGraphSteps + (s->lz_graph ? 0 : 1);
   if (eligible) {
     if (s->lz_graph && (s->lz_graph_nlanc != nlanc || s->lz_graph_scal != s->d_scal || s->lz_graph_blocked != s->lz_blocked)) {
@@ -1336,6 +1300,7 @@ int edigpu_normal_create(edigpu_handle* h, int64_t dim_up, int64_t dim_dw, int64
   }
   *h = nullptr;
   if (ensure_device()) return 1;
+  const Switches sw = Switches::sample();
   if (dim_up <= 0 || dim_dw <= 0 || dw_first < 0 || dw_count < 0 || dw_first + dw_count > dim_dw) {
     set_error("edigpu_normal_create: inconsistent dimensions");
     return 1;
@@ -1367,12 +1332,11 @@ int edigpu_normal_create(edigpu_handle* h, int64_t dim_up, int64_t dim_dw, int64
   dw.val.assign(dw_val, dw_val + dw_rowptr[dim_dw]);
   // The arrays of an impurity model have the structure the library's own builder emits (separable diagonal, Hnd a short
   // sum of signed partial permutations): recover it and run the factored kernels; anything else keeps the explicit
-  // image.  EDIGPU_HANDOVER_FACTOR=0 (or EDIGPU_NORMAL_EXPLICIT=1) switches the attempt off.
+  // image.
   HostNormal hn;
   bool fact = false;
   {
-    const char* e = getenv("EDIGPU_HANDOVER_FACTOR");
-    if (!(e && atoi(e) == 0) && !env_flag("EDIGPU_NORMAL_EXPLICIT"))
+    if (sw.handover_factor && !sw.normal_explicit)
       fact = factor_handover(dim_up, dim_dw, dw_first, dw_count, hd, nd_rowptr, nd_col, nd_val, 16, hn.fac);
     if (fact) {  // the arrays as given stay on the host for edigpu_normal_export
       const int64_t nloc = dim_up * dw_count;
@@ -1386,7 +1350,7 @@ int edigpu_normal_create(edigpu_handle* h, int64_t dim_up, int64_t dim_dw, int64
       }
     }
   }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector());
+  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
   if (setup_normal(s.get(), dim_up, dim_dw, dw_first, dw_count, hd, up, dw, nd_rowptr, nd_col, nd_val,
                    fact ? &hn : nullptr)) {
     edigpu_destroy(s.release());
@@ -1405,6 +1369,7 @@ static int csr_create_any(edigpu_handle* h, int64_t nrow_local, int64_t ncol_glo
   }
   *h = nullptr;
   if (ensure_device()) return 1;
+  const Switches sw = Switches::sample();
   if (nrow_local < 0 || ncol_global <= 0 || row_first < 0 || row_first + nrow_local > ncol_global) {
     set_error("edigpu_csr_create: inconsistent dimensions");
     return 1;
@@ -1418,7 +1383,7 @@ static int csr_create_any(edigpu_handle* h, int64_t nrow_local, int64_t ncol_glo
     set_error(e);
     return 1;
   }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector());
+  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
   if (setup_flat(s.get(), nrow_local, ncol_global, row_first, rowptr, col, val, cplx)) {
     edigpu_destroy(s.release());
     return 1;
@@ -1447,19 +1412,20 @@ int edigpu_normal_build(edigpu_handle* h, const edigpu_model* model, int nup, in
   }
   *h = nullptr;
   if (ensure_device()) return 1;
+  const Switches sw = Switches::sample();
   HostNormal hn;
   // the O(Dim) explicit images (hd, Hnd CSR) are skipped when the kernels run on the factored tables
-  bool lazy = !env_flag("EDIGPU_NORMAL_EXPLICIT");
-  std::string e = build_normal(*model, nup, ndw, dw_first, dw_count, hn, !lazy);
+  bool lazy = !sw.normal_explicit;
+  std::string e = build_normal(*model, nup, ndw, dw_first, dw_count, hn, !lazy, !sw.nd_no_merge);
   if (e.empty() && lazy && hn.fac.nterms > 16) {
     lazy = false;
-    e = build_normal(*model, nup, ndw, dw_first, dw_count, hn, true);
+    e = build_normal(*model, nup, ndw, dw_first, dw_count, hn, true, !sw.nd_no_merge);
   }
   if (!e.empty()) {
     set_error(e);
     return 1;
   }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector());
+  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
   s->model = *model;
   s->sec_a = nup;
   s->sec_b = ndw;
@@ -1523,6 +1489,7 @@ int edigpu_normal_build_z(edigpu_handle* h, const edigpu_model* model, int nup, 
     return 1;
   }
   *h = nullptr;
+  const Switches sw = Switches::sample();
   if (model->ed_mode != 0) {
     set_error("edigpu_normal_build_z: ed_mode must be normal");
     return 1;
@@ -1539,7 +1506,7 @@ int edigpu_normal_build_z(edigpu_handle* h, const edigpu_model* model, int nup, 
     edigpu_destroy(hs);
     return 1;
   }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector());
+  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
   s->kind = 4;
   s->is_complex = 1;
   s->device = g_device;
@@ -1553,13 +1520,13 @@ int edigpu_normal_build_z(edigpu_handle* h, const edigpu_model* model, int nup, 
   s->sub_s = hs;
   s->sub_a = ha;
   // The complex operator as one real sector on the doubled up index: one pass over 2 Dim elements instead of four
-  // real products and two layout passes.  EDIGPU_CMPLX_FOURPRODUCTS=1, or more than 16 factored terms (complex replica
+  // real products and two layout passes.  Switches::cmplx_fourproducts, or more than 16 factored terms (complex replica
   // matrices with many imaginary inter-orbital hops), keep the composite above.
-  if (!env_flag("EDIGPU_CMPLX_FOURPRODUCTS") && !env_flag("EDIGPU_NORMAL_EXPLICIT")) {
+  if (!sw.cmplx_fourproducts && !sw.normal_explicit) {
     HostNormal hd2;
-    const std::string e2 = build_normal_doubled(*model, nup, ndw, hd2, 16);
+    const std::string e2 = build_normal_doubled(*model, nup, ndw, hd2, 16, !sw.nd_no_merge);
     if (e2.empty()) {
-      std::unique_ptr<edigpu_sector> sd(new edigpu_sector());
+      std::unique_ptr<edigpu_sector> sd(new edigpu_sector(sw));
       if (setup_normal(sd.get(), hd2.dim_up, hd2.dim_dw, 0, hd2.dim_dw, nullptr, hd2.up, hd2.dw, nullptr, nullptr, nullptr,
                        &hd2)) {
         edigpu_destroy(sd.release());
@@ -1624,7 +1591,7 @@ static int attach_phonons_flat(edigpu_sector* s, const edigpu_model& m, const st
 
 }  // extern "C"
 namespace edigpu {
-// edigpu_flat_build / edigpu_flat_build_jz: the stored image, generated on the device unless EDIGPU_FLAT_HOSTBUILD=1
+// edigpu_flat_build / edigpu_flat_build_jz: the stored image, generated on the device unless Switches::flat_hostbuild
 static int flat_build_common(edigpu_handle* h, const edigpu_model* model, int sector, int64_t row_first, int64_t row_count,
                              bool jz, int twojz) {
   if (!h || !model) {
@@ -1633,15 +1600,16 @@ static int flat_build_common(edigpu_handle* h, const edigpu_model* model, int se
   }
   *h = nullptr;
   if (ensure_device()) return 1;
+  const Switches sw = Switches::sample();
   if (jz && model->nph > 0) {
     set_error("edigpu_flat_build_jz: phonon sectors are not built in the Jz basis");
     return 1;
   }
-  if (!env_flag("EDIGPU_FLAT_HOSTBUILD")) {
+  if (!sw.flat_hostbuild) {
     // generate the stored image on the device from the on-the-fly description (kernels_build.hip);
     // the host CSR builder below is the fallback and what edigpu_csr_export materialises
     HostDirect hd;
-    std::string e = build_direct(*model, sector, row_first, row_count, hd, jz, twojz);
+    std::string e = build_direct(*model, sector, row_first, row_count, hd, jz, twojz, !sw.direct_nosort);
     if (!e.empty()) {
       set_error(e);
       return 1;
@@ -1650,7 +1618,7 @@ static int flat_build_common(edigpu_handle* h, const edigpu_model* model, int se
       set_error("edigpu_flat_build: empty sector");
       return 1;
     }
-    std::unique_ptr<edigpu_sector> s(new edigpu_sector());
+    std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
     s->kind = 1;
     s->is_complex = 1;
     s->device = g_device;
@@ -1689,7 +1657,7 @@ static int flat_build_common(edigpu_handle* h, const edigpu_model* model, int se
     set_error("edigpu_flat_build: empty sector");
     return 1;
   }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector());
+  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
   s->model = *model;
   s->sec_a = sector;
   s->sec_b = jz ? twojz : 0;
@@ -1702,7 +1670,7 @@ static int flat_build_common(edigpu_handle* h, const edigpu_model* model, int se
   }
   if (model->nph > 0) {
     HostDirect hd;  // for the sector map
-    e = build_direct(*model, sector, row_first, row_count, hd, jz, twojz);
+    e = build_direct(*model, sector, row_first, row_count, hd, jz, twojz, !sw.direct_nosort);
     if (!e.empty()) set_error(e);
     if (!e.empty() || attach_phonons_flat(s.get(), *model, hd.states, hd.ns)) {
       edigpu_destroy(s.release());
@@ -1752,13 +1720,14 @@ static int direct_build_common(edigpu_handle* h, const edigpu_model* model, int 
   }
   *h = nullptr;
   if (ensure_device()) return 1;
+  const Switches sw = Switches::sample();
   HostDirect hd;
-  std::string e = build_direct(*model, sector, row_first, row_count, hd, jz, twojz);
+  std::string e = build_direct(*model, sector, row_first, row_count, hd, jz, twojz, !sw.direct_nosort);
   if (!e.empty()) {
     set_error(e);
     return 1;
   }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector());
+  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
   s->kind = 2;
   s->model = *model;
   s->sec_a = sector;
@@ -1808,6 +1777,7 @@ int edigpu_orbs_build_rows(edigpu_handle* h, const edigpu_model* model, const in
   }
   *h = nullptr;
   if (ensure_device()) return 1;
+  const Switches sw = Switches::sample();
   HostOrbs ho;
   std::string e = build_orbs(*model, nups, ndws, ho);
   if (!e.empty()) {
@@ -1823,7 +1793,7 @@ int edigpu_orbs_build_rows(edigpu_handle* h, const edigpu_model* model, const in
     set_error("edigpu_orbs_build_rows: row range outside the sector");
     return 1;
   }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector());
+  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
   s->model = *model;
   if (setup_orbs(s.get(), ho, nullptr)) {
     edigpu_destroy(s.release());
@@ -1843,6 +1813,7 @@ int edigpu_orbs_create(edigpu_handle* h, int naxes, const int64_t* dims, const d
   }
   *h = nullptr;
   if (ensure_device()) return 1;
+  const Switches sw = Switches::sample();
   if (naxes < 2 || naxes > kOrbsMaxAxes || (naxes & 1)) {
     set_error("edigpu_orbs_create: naxes must be 2*Norb <= 2*EDIGPU_MAXORB");
     return 1;
@@ -1885,7 +1856,7 @@ int edigpu_orbs_create(edigpu_handle* h, int naxes, const int64_t* dims, const d
       }
     row0 += d;
   }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector());
+  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
   if (setup_orbs(s.get(), ho, hd)) {
     edigpu_destroy(s.release());
     return 1;
@@ -2062,7 +2033,7 @@ int edigpu_normal_export(edigpu_handle s, double* hd, int64_t* up_rowptr, int32_
   if (s->lazy_export && s->factored) {
     // first export of a factored sector: materialise the explicit images from the stored model
     HostNormal hn;
-    std::string e = build_normal(s->model, s->sec_a, s->sec_b, s->dw_first, s->dw_count, hn, true);
+    std::string e = build_normal(s->model, s->sec_a, s->sec_b, s->dw_first, s->dw_count, hn, true, !s->sw.nd_no_merge);
     if (!e.empty()) {
       set_error(e);
       return 1;
@@ -2458,8 +2429,8 @@ static int apply_op_flat_term(edigpu_handle src, edigpu_handle dst, const double
   }
   EDIGPU_HIP(hipSetDevice(src->device));
   HostDirect hs, hd;
-  std::string e = build_direct(src->model, src->sec_a, 0, -1, hs, src->jz, src->sec_b);
-  if (e.empty()) e = build_direct(dst->model, dst->sec_a, 0, -1, hd, dst->jz, dst->sec_b);
+  std::string e = build_direct(src->model, src->sec_a, 0, -1, hs, src->jz, src->sec_b, !src->sw.direct_nosort);
+  if (e.empty()) e = build_direct(dst->model, dst->sec_a, 0, -1, hd, dst->jz, dst->sec_b, !dst->sw.direct_nosort);
   if (!e.empty()) {
     set_error(e);
     return 1;
@@ -2601,10 +2572,10 @@ int edigpu_lanczos_eigh(edigpu_handle s, int nitermax, double tol, int check_eve
   // With a vector asked for, the Lanczos vectors are kept as they are produced (blocks of kKeep vectors, allocated
   // while the device has room: 288 GB hold thousands of config-2 vectors) and the Ritz vector is assembled from them --
   // one extra copy per step instead of a second pass that regenerates every v_k with as many products again.
-  // EDIGPU_EIGH_TWOPASS=1, or an allocation that fails, falls back to the second pass.
+  // LoopSwitches::eigh_twopass, or an allocation that fails, falls back to the second pass.
   constexpr int kKeep = 16;
   std::vector<double*> kept;  // block b holds v_(b kKeep) .. v_(b kKeep + kKeep - 1)
-  bool keep = evec_host != nullptr && !getenv("EDIGPU_EIGH_TWOPASS");
+  bool keep = evec_host != nullptr && !s->lz.eigh_twopass;  // (sampled by lanczos_prepare above)
   auto drop_kept = [&]() {
     for (double* b : kept) (void)hipFree(b);
     kept.clear();
@@ -2768,6 +2739,7 @@ int trl_solve(int device, hipStream_t st, int cplx, int64_t n, int64_t len, int6
               double tol, int maxrestart, const double* v0, uint64_t seed_offset, double* evals, double* evecs,
               int* nconv_out, int* nmatvec_out) {
   EDIGPU_HIP(hipSetDevice(device));
+  const LoopSwitches lz = LoopSwitches::sample();
   const bool multi = (bool)ops.allreduce;
   auto reduce = [&](double* dev, size_t cnt) -> int { return multi ? ops.allreduce(dev, cnt, st) : 0; };
   if ((int64_t)neigen > nglobal) neigen = (int)nglobal;
@@ -2825,16 +2797,16 @@ int trl_solve(int device, hipStream_t st, int cplx, int64_t n, int64_t len, int6
   } free2{d_coef, d_nrm};
   std::vector<double> hcoef(2 * hstride * (size_t)m), hnrm(2 * (size_t)m + 80);
   // Classical Gram-Schmidt twice on every step (CGS2).  The variant that skips the second pass when the first one
-  // removed little (EDIGPU_TRL_ONEPASS=1, criterion |w_new|^2 >= 0.5 |w_old|^2) saves up to half the basis traffic
+  // removed little (LoopSwitches::trl_onepass, criterion |w_new|^2 >= 0.5 |w_old|^2) saves up to half the basis traffic
   // but was found to let the restart vector drift out of orthogonality (2e-13 after the first cycle with the
   // earlier 1 % criterion, x1000 per restart: Ritz values below the spectrum after five restarts on a 36-dimensional
   // sector), so it is not the default.
-  static const bool twopass = getenv("EDIGPU_TRL_ONEPASS") == nullptr;
-  // EDIGPU_TRL_FULL=1: full CGS2 on every step (the round-2 solver)
-  static const bool selective = getenv("EDIGPU_TRL_FULL") == nullptr && getenv("EDIGPU_TRL_ONEPASS") == nullptr;
+  const bool twopass = !lz.trl_onepass;
+  // LoopSwitches::trl_full: full CGS2 on every step (the round-2 solver)
+  const bool selective = !lz.trl_full && !lz.trl_onepass;
   constexpr double kSelThr = 1e-14;
   // coefficients below thr_skip * |w_new| are left in w: three orders below the requested residual
-  const double thr_skip = getenv("EDIGPU_TRL_THR") ? atof(getenv("EDIGPU_TRL_THR")) : 1e-3 * tol;
+  const double thr_skip = lz.trl_thr.value_or(1e-3 * tol);
   int* d_skip = nullptr;
   EDIGPU_HIP(hipMalloc((void**)&d_skip, sizeof(int)));
   struct Free1 {
@@ -2914,7 +2886,7 @@ int trl_solve(int device, hipStream_t st, int cplx, int64_t n, int64_t len, int6
       for (int j = 0; j < meff; j++) Tw[(size_t)i * meff + j] = T[(size_t)i * m + j];
     jacobi_eigh(meff, Tw, theta, Y);
     const int want = std::min(neigen, meff);
-    if (getenv("EDIGPU_TRL_DEBUG")) {
+    if (lz.trl_debug) {
       fprintf(stderr, "trl: restart %d k %d meff %d invariant %d beta_last %.3e theta0 %.6e\n  beta:", restart, k, meff,
               (int)invariant, beta_last, theta.empty() ? 0.0 : theta[0]);
       for (int j = k; j < meff; j++) fprintf(stderr, " %.2e", sqrt(std::max(hnrm[2 * j], 0.0)));

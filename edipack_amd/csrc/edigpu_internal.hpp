@@ -9,6 +9,7 @@
 
 #include "../../include/edigpu.h"
 #include "host_build.hpp"
+#include "switches.hpp"
 
 namespace edigpu {
 
@@ -127,6 +128,7 @@ struct DevSb {
 struct IbDev {
   DevSb* sb = nullptr;
   int nhalf = 1;                 // 2: rows longer than the LDS, staged one half (value of the top bath bit) at a time
+  OptInt cols2;                  // Switches::ib_cols2 at set-up: the form of the columns kernel, when set (kernels_ib.hip use_cols2)
   IbDevHalf half[2];
   uint16_t* urank_low = nullptr; // [2^(nb_up - 1)]
   double top_eps = 0.0;          // energy of the top bath level of the up species
@@ -190,6 +192,8 @@ int64_t rdm_table_bytes(const edigpu_sector* s);
 }  // namespace edigpu
 
 struct edigpu_sector {
+  explicit edigpu_sector(const edigpu::Switches& at_creation) : sw(at_creation) {}
+  const edigpu::Switches sw;  // the environment the creating C-ABI call saw (switches.hpp): every set-up and launch choice reads it
   int kind = 0;        // 0 normal (Kronecker), 1 flat CSR, 2 direct (on-the-fly superc/nonsu2), 3 orbs (ed_total_ud=F)
   int is_complex = 0;
   int device = 0;
@@ -232,7 +236,7 @@ struct edigpu_sector {
   // panel-major vector layout of the fused Lanczos loop (NormalArgs::blk_shift): chosen at set-up for large factored
   // whole sectors, 0 = not available; lz_blocked: the current recurrence runs on it
   int blk_shift = 0;
-  int blk_tail_balance = 1;     // EDIGPU_TILE_BALANCE=0 at set-up: the padded grid of the tiled sweep (A/B timing, tests)
+  int blk_tail_balance = 1;     // 0 (Switches::tile_balance off): the padded grid of the tiled sweep (A/B timing, tests)
   int64_t blk_ps = 0, blk_len = 0;
   int4* d_bl_meta = nullptr;
   int blk_rows = 0;             // rows of an LDS block of the blocked sweep
@@ -292,7 +296,7 @@ struct edigpu_sector {
   double* d_tmp = nullptr;
   double* d_partial = nullptr;  // reduction partials
   double* d_scal = nullptr;     // alpha/beta/flags on device
-  bool lz_exactbeta = false;    // EDIGPU_LANCZOS_EXACTBETA at the start of the current recurrence
+  edigpu::LoopSwitches lz = {};  // the environment at the start of the current recurrence (lanczos_prepare)
   // launch-bound sectors replay the steps of a recurrence from a captured hipGraph (lanczos_run): the executable and
   // what it was captured for
   hipGraphExec_t lz_graph = nullptr;

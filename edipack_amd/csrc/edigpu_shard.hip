@@ -121,6 +121,7 @@ struct ShmHeader {
 };
 
 struct edigpu_comm_s {
+  const edigpu::CommSwitches sw = edigpu::CommSwitches::sample();  // the environment edigpu_comm_create* saw (switches.hpp)
   int rank = 0, world = 1;
   int kind = 0;  // 0 RCCL, 1 host-staged through shared memory
   int device = 0;
@@ -149,11 +150,8 @@ struct edigpu_comm_s {
 
 namespace edigpu {
 
-// EDIGPU_FORCE_COLLECTIVES=1: a world of one still issues its collectives through RCCL (one-GPU rehearsal of the calls)
-static bool force_collectives(const edigpu_comm_s* c) {
-  static const bool f = getenv("EDIGPU_FORCE_COLLECTIVES") != nullptr;
-  return f && c->kind == 0 && c->nccl != nullptr;
-}
+// a world of one still issues its collectives through RCCL (one-GPU rehearsal of the calls)
+static bool force_collectives(const edigpu_comm_s* c) { return c->sw.force_collectives && c->kind == 0 && c->nccl != nullptr; }
 
 static int shm_barrier(edigpu_comm_s* c) {
   ShmHeader* h = c->hdr;
@@ -189,11 +187,7 @@ static int shm_fits(edigpu_comm_s* c, size_t bytes) {
 // that is exactly what a single in-order stream guarantees (the first multi-GPU run should not be the one to find out).
 // side_begin: the collective waits for what `st` has enqueued so far; side_end: `st` waits for the collective.  A caller
 // that overlaps the exchange with its own kernels passes c->side itself and places the two events where it needs them.
-// EDIGPU_COMM_TWO_STREAMS=1 (measurement only): collectives on the caller's stream, as before round 3
-static bool comm_two_streams() {
-  static const bool f = getenv("EDIGPU_COMM_TWO_STREAMS") != nullptr;
-  return f;
-}
+// CommSwitches::comm_two_streams (measurement only): collectives on the caller's stream, as before round 3
 static int side_begin(edigpu_comm_s* c, hipStream_t st) {
   if (st == c->side) return 0;
   EDIGPU_HIP(hipEventRecord(c->ev_in, st));
@@ -214,7 +208,7 @@ static int comm_all_to_all(edigpu_comm_s* c, const double* send, double* recv, s
     EDIGPU_HIP(hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, caller));
     return 0;
   }
-  hipStream_t st = comm_two_streams() ? caller : c->side;
+  hipStream_t st = c->sw.comm_two_streams ? caller : c->side;
   if (side_begin(c, st == c->side ? caller : st)) return 1;
   struct End {
     edigpu_comm_s* c;
@@ -250,7 +244,7 @@ static int comm_all_gather(edigpu_comm_s* c, const double* send, double* recv, s
     EDIGPU_HIP(hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, caller));
     return 0;
   }
-  hipStream_t st = comm_two_streams() ? caller : c->side;
+  hipStream_t st = c->sw.comm_two_streams ? caller : c->side;
   if (side_begin(c, st == c->side ? caller : st)) return 1;
   struct End {
     edigpu_comm_s* c;
@@ -276,7 +270,7 @@ static int comm_all_gather(edigpu_comm_s* c, const double* send, double* recv, s
 // buf[0..n) <- sum over the ranks (the same order on every rank: bit-identical results everywhere)
 static int comm_all_reduce(edigpu_comm_s* c, double* buf, size_t n, hipStream_t caller) {
   if (c->world == 1 && !force_collectives(c)) return 0;
-  hipStream_t st = comm_two_streams() ? caller : c->side;
+  hipStream_t st = c->sw.comm_two_streams ? caller : c->side;
   if (side_begin(c, st == c->side ? caller : st)) return 1;
   struct End {
     edigpu_comm_s* c;
@@ -481,9 +475,11 @@ struct ShardGeom {
   bool block = false;
   int npmax = 0;      // panels per rank
   int64_t bplen = 0;  // doubles of a vector in the shard form: world * npmax * q * 16
+  LoopSwitches loop = {};  // the environment shard_geometry saw: held for the product, recurrence or solve that g serves
 };
 
 static int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g) {
+  g.loop = LoopSwitches::sample();
   g.w = s->is_complex ? 2 : 1;
   g.transposed = s->kind == 0 && s->nloc == s->dim && normal_transposable_el(s);
   g.nblk = s->nph > 0 ? s->nph + 1 : 1;
@@ -510,7 +506,7 @@ static int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardG
     if (g.pcol < 1 || g.halo > g.pcol) g.transposed = false;  // blocks narrower than the halo: all-gather form
   }
   // (rows per rank for which the columns kernel's owner rank g / q is not exact: the column-block exchange)
-  if (g.transposed && g.nblk == 1 && sb_shardable(s) && sb::shard_exact(c->world, g.q) && !getenv("EDIGPU_SHARD_GENERIC")) {
+  if (g.transposed && g.nblk == 1 && sb_shardable(s) && sb::shard_exact(c->world, g.q) && !g.loop.shard_generic) {
     g.block = true;
     g.npmax = sb_shard_panels(s, c->world);
     g.bplen = sb::shard_slot(c->world, g.npmax, g.q);
@@ -703,15 +699,12 @@ static int sharded_step(edigpu_sector* s, edigpu_comm_s* c, const ShardGeom& g, 
   return comm_all_reduce(c, t, 3, st);
 }
 
-// The recurrence with its two vectors KEPT in the padded panel layout (ShardGeom::block; EDIGPU_SHARD_PANEL_LOOP=0 falls back
+// The recurrence with its two vectors KEPT in the padded panel layout (ShardGeom::block; LoopSwitches::shard_panel_loop off falls back
 // to the rows of the reference's layout with a conversion on either side of every product): the Lanczos vector is what the
 // first all-to-all sends as it is; it and the work vector live in bp[0] and bp[4] and swap roles every step
 // (sharded_step_panels); the padding of the layout holds zeros in every buffer and stays zero under the element-wise
 // updates, so the three sums are those of the shard.
-static bool panel_loop(const ShardGeom& g) {
-  const char* e = getenv("EDIGPU_SHARD_PANEL_LOOP");
-  return g.block && !(e && atoi(e) == 0);
-}
+static bool panel_loop(const ShardGeom& g) { return g.block && g.loop.shard_panel_loop; }
 
 // after load_seed: the normalised seed goes into the panel layout, every other buffer of the loop starts from zeros
 // (the buffers serve sectors of different geometry in turn: what one leaves behind is not zero in another's padding)
@@ -781,7 +774,7 @@ static int sharded_tridiag(edigpu_sector* s, edigpu_comm_s* c, const double* vin
   std::fill(alanc, alanc + nlanc, 0.0);
   std::fill(blanc, blanc + nlanc, 0.0);
   if (niter_done) *niter_done = 0;
-  const bool force_exact = getenv("EDIGPU_LANCZOS_EXACTBETA") != nullptr;
+  const bool force_exact = g.loop.lanczos_exactbeta;
   std::vector<double> h(3 * (size_t)nlanc + 8);
   for (int pass = force_exact ? 1 : 0; pass < 2; pass++) {
     EDIGPU_HIP(hipMemsetAsync(c->hist, 0, (size_t)c->hist_cap * sizeof(double), st));
@@ -1127,9 +1120,9 @@ int edigpu_lanczos_tridiag_sharded(edigpu_handle h, edigpu_comm c, const double*
     return 1;
   }
   // a world of one rank holding the whole sector: the fused single-GPU recurrence (half the vector traffic of the
-  // exchange form: no send / receive buffers); EDIGPU_FORCE_COLLECTIVES=1 keeps the N > 1 code path (tests)
+  // exchange form: no send / receive buffers); CommSwitches::force_collectives keeps the N > 1 code path (tests)
   if (h->kind == 4 && h->sub_d) h = h->sub_d;  // complex normal sector = its doubled real sector (see apply_sharded)
-  if (c->world == 1 && h->nloc == h->dim && !getenv("EDIGPU_FORCE_COLLECTIVES") && vin_shard)
+  if (c->world == 1 && h->nloc == h->dim && !c->sw.force_collectives && vin_shard)
     return edigpu_lanczos_tridiag_dev(h, vin_shard, nlanc, alanc, blanc, threshold, niter_done, norm2);
   return sharded_tridiag(h, c, vin_shard, nlanc, alanc, blanc, threshold, niter_done, norm2);
 }
@@ -1150,7 +1143,7 @@ int edigpu_lanczos_eigh_multi_sharded(edigpu_handle h, edigpu_comm c, int neigen
     realified = true;
   }
   // a world of one rank holding the whole sector: the single-GPU solver (no exchange buffers)
-  if (c->world == 1 && h->nloc == h->dim && !getenv("EDIGPU_FORCE_COLLECTIVES") && !realified)
+  if (c->world == 1 && h->nloc == h->dim && !c->sw.force_collectives && !realified)
     return edigpu_lanczos_eigh_multi(h, neigen, ncv, tol, maxrestart, v0_shard, evals, evecs_shard, nconv, nmatvec);
   ShardGeom g;
   if (shard_geometry(h, c, g)) return 1;

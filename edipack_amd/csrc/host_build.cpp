@@ -364,7 +364,7 @@ static void merge_factored_terms(HostFactored& fac, int64_t du, int64_t dd) {
 }
 
 std::string build_normal(const edigpu_model& m, int nup, int ndw, int64_t dw_first,
-                         int64_t dw_count, HostNormal& out, bool explicit_arrays) {
+                         int64_t dw_count, HostNormal& out, bool explicit_arrays, bool merge_terms) {
   std::string e = check_model(m);
   if (!e.empty()) return e;
   if (m.ed_mode != 0) return "edigpu_normal_build: model.ed_mode is not normal";
@@ -560,7 +560,7 @@ std::string build_normal(const edigpu_model& m, int nup, int ndw, int64_t dw_fir
       partner_ops(out.bdw, sl.dw, fac.jdw);
       fac.nterms++;
     }
-    if (!getenv("EDIGPU_ND_NO_MERGE")) merge_factored_terms(fac, DimUp, out.dim_dw);
+    if (merge_terms) merge_factored_terms(fac, DimUp, out.dim_dw);
     struct Term { uint32_t xu, xd; double val; };
     std::vector<std::vector<Term>> terms((size_t)1 << (2 * norb));
     for (uint32_t iu = 0; iu <= impmask; iu++)
@@ -1173,7 +1173,7 @@ int twojz_of_level(int p, int ns, int norb) {
 }
 
 std::string build_direct(const edigpu_model& m, int sector, int64_t row_first, int64_t row_count,
-                         HostDirect& out, bool jz_basis, int twojz) {
+                         HostDirect& out, bool jz_basis, int twojz, bool sort_terms) {
   std::string e = check_model(m);
   if (!e.empty()) return e;
   if (m.ed_mode != 1 && m.ed_mode != 2) return "edigpu_direct_build: model.ed_mode must be superc or nonsu2";
@@ -1259,8 +1259,7 @@ std::string build_direct(const edigpu_model& m, int sector, int64_t row_first, i
   // fills) - sum(2^b over the levels it empties), and ranks grow with the state.  A lane pops its applicable terms in
   // list order, so with ascending delta the lanes of a wave (consecutive rows) walk their partners in ascending
   // column order together -- what the column-sorted rows of the stored SELL image give that kernel.
-  // EDIGPU_DIRECT_NOSORT=1 keeps the order of the operator list.
-  if (!getenv("EDIGPU_DIRECT_NOSORT")) {
+  if (sort_terms) {
     auto delta = [](const DirectTerm& t) {
       int64_t d = 0;
       for (int b = 0; b < 32; b++) {
@@ -1523,14 +1522,14 @@ namespace edigpu {
 // factored terms (a partial map of the down index per magnitude and hop (x) the signed swap of the two components).  The
 // kernels of the real sector then compute the complex product in one pass over 2 Dim elements -- about twice a real
 // product instead of four real products and two layout passes.
-std::string build_normal_doubled(const edigpu_model& m, int nup, int ndw, HostNormal& out, int max_terms) {
+std::string build_normal_doubled(const edigpu_model& m, int nup, int ndw, HostNormal& out, int max_terms, bool merge_terms) {
   HostNormal hs, ha;
-  std::string e = build_normal(m, nup, ndw, 0, -1, hs, false);
+  std::string e = build_normal(m, nup, ndw, 0, -1, hs, false, merge_terms);
   if (!e.empty()) return e;
   bool any = false;
   const edigpu_model mi = imag_part_model(m, any);
   if (any) {
-    e = build_normal(mi, nup, ndw, 0, -1, ha, false);
+    e = build_normal(mi, nup, ndw, 0, -1, ha, false, merge_terms);
     if (!e.empty()) return e;
   }
   const int64_t du = hs.dim_up, dd = hs.dim_dw, du2 = 2 * du;

@@ -128,16 +128,18 @@ struct HostOrbs {
 std::string build_orbs(const edigpu_model& m, const int* nups, const int* ndws, HostOrbs& out,
                        bool explicit_diag = false);
 // explicit_arrays = false skips the O(Dim) images (hd, the Hnd CSR): the factored tables are all the
-// kernels need; the arrays are only materialised for export (edigpu_normal_export).
+// kernels need; the arrays are only materialised for export (edigpu_normal_export).  merge_terms = false keeps one
+// factored Hnd term per operator of the model (Switches::nd_no_merge).
 std::string build_normal(const edigpu_model& m, int nup, int ndw, int64_t dw_first,
-                         int64_t dw_count, HostNormal& out, bool explicit_arrays = true);
+                         int64_t dw_count, HostNormal& out, bool explicit_arrays = true, bool merge_terms = true);
 // jz_basis: the nonsu2 sector (Ntot = sector, twoJz) of Jz_basis=T (ED_SECTOR.f90:289-350)
 std::string build_flat(const edigpu_model& m, int sector, int64_t row_first, int64_t row_count,
                        HostFlat& out, bool jz_basis = false, int twojz = 0);
 std::string sector_map_jz(const edigpu_model& m, int ntot, int twojz, std::vector<int32_t>& out);
-// jz_basis: the nonsu2 sector (Ntot = sector, twoJz) of Jz_basis=T; refuses models whose terms change twoJz
+// jz_basis: the nonsu2 sector (Ntot = sector, twoJz) of Jz_basis=T; refuses models whose terms change twoJz;
+// sort_terms = false keeps the order of the operator list (Switches::direct_nosort)
 std::string build_direct(const edigpu_model& m, int sector, int64_t row_first, int64_t row_count,
-                         HostDirect& out, bool jz_basis = false, int twojz = 0);
+                         HostDirect& out, bool jz_basis = false, int twojz = 0, bool sort_terms = true);
 // change of twoJz when level p (0 .. 2 Ns - 1, up levels first) is filled: +-1 from the spin, 2 Lzdiag(iorb) from the
 // orbital (levels labelled iorb + Norb * ibath; Lzdiag = [-1, +1, 0], ED_VARS_GLOBAL.f90:283)
 int twojz_of_level(int p, int ns, int norb);
@@ -149,7 +151,8 @@ bool factor_handover(int64_t dim_up, int64_t dim_dw, int64_t dw_first, int64_t d
                      HostFactored& fac);
 edigpu_model imag_part_model(const edigpu_model& m, bool& any);
 // the complex (_CMPLX_NORMAL) sector as one real sector on the doubled up index 2 iup + (re | im); "" on success
-std::string build_normal_doubled(const edigpu_model& m, int nup, int ndw, HostNormal& out, int max_terms);
+std::string build_normal_doubled(const edigpu_model& m, int nup, int ndw, HostNormal& out, int max_terms,
+                                 bool merge_terms = true);
 bool eph_offdiagonal(const edigpu_model& m);
 edigpu_model eph_operator_model(const edigpu_model& m);
 std::string sector_dim(const edigpu_model& m, int q1, int q2, int64_t& dim);

@@ -119,7 +119,7 @@ int sb_rows_slots(const HostNormal& hn, int nb0, bool split) {
 }
 
 void build_sb(const HostNormal& hn, const HostIb& ib, int nb0, int max_chunk_rows, int rows_nt, int rows_nbt, int cols_nw,
-              HostSb& out, int cols_gs) {
+              HostSb& out, int cols_gs, bool per_orbital_walk) {
   out = HostSb();
   const int gs = cols_gs;
   auto fail = [&](const std::string& w) {
@@ -142,9 +142,8 @@ void build_sb(const HostNormal& hn, const HostIb& ib, int nb0, int max_chunk_row
   // The per-orbital walk (AMODE 1) issues only the multiply-adds of the orbital a level belongs to, but the lanes of a wave
   // then walk unequal numbers of levels per orbital and wait for the longest: measured on config 2 (two orbitals, six levels
   // each) 138 us per product against 126 with the all-orbital walk, whose extra multiply-adds (by amplitudes that are zero)
-  // are cheaper than the extra LDS round trips.  On request only: EDIGPU_SB_AMODE=1.
-  out.amode = 0;
-  if (const char* e = getenv("EDIGPU_SB_AMODE")) out.amode = (atoi(e) != 0 && norb > 1 && out.up.single && out.dw.single) ? 1 : 0;
+  // are cheaper than the extra LDS round trips.  On request only.
+  out.amode = (per_orbital_walk && norb > 1 && out.up.single && out.dw.single) ? 1 : 0;
   const int64_t du = hn.dim_up, dd = hn.dim_dw;
   const uint32_t lmask = (1u << nloc) - 1u, impmask = (1u << norb) - 1u;
   const size_t nw = (size_t)1 << nbw;

@@ -94,10 +94,14 @@ struct HostSb {
 };
 
 // nb0: low bath levels folded into the blocks; rows_nt / rows_nbt: threads per workgroup and blocks per thread of the
-// rows kernel; cols_nw: waves per workgroup of the columns kernel.  out.valid = false with out.why set when the sector
-// is not of this form (the caller keeps the impurity-block kernels).
+// rows kernel; cols_nw: waves per workgroup of the columns kernel; per_orbital_walk: AMODE 1 where the bath allows it
+// (Switches::sb_amode).  out.valid = false with out.why set when the sector is not of this form (the caller keeps the
+// impurity-block kernels).
 void build_sb(const HostNormal& hn, const HostIb& ib, int nb0, int max_chunk_rows, int rows_nt, int rows_nbt, int cols_nw,
-              HostSb& out, int cols_gs = 8);
+              HostSb& out, int cols_gs = 8, bool per_orbital_walk = false);
+// blocks per wave-slot of the columns kernel (build_sb's cols_gs): 8 = two columns per lane, 256 threads; 4 = one column per
+// lane, 512 threads.  cw (Switches::sb_cw) = 1 / 2 chooses (tuning)
+inline int sb_cols_gs(int cw) { return cw == 1 ? 4 : 8; }
 // bytes of a chunk's packed descriptors for nsl wave-slots of gs blocks
 inline uint32_t sb_desc_bytes(int nsl, int gs) {
   return (uint32_t)nsl * gs * 32 + (((uint32_t)nsl * gs * 2 + 15) & ~15u) + (((uint32_t)nsl * 4 + 15) & ~15u);

@@ -23,7 +23,8 @@ int device_cu_count();
 // v_local : first element of the shard's own rows, v_full : element 0 of the whole vector.
 int launch_normal(const edigpu_sector* s, const double* v_local, const double* v_full, double* hv,
                   int phase, hipStream_t st);
-int normal_pick_rows_per_block(int64_t dim_up, int64_t dw_count);
+// rows_td: Switches::rows_td
+int normal_pick_rows_per_block(int64_t dim_up, int64_t dw_count, OptInt rows_td);
 // transposed exchange: the row half and the column half of the product on a whole-sector handle
 bool normal_transposable(const edigpu_sector* s);
 bool normal_transposable_el(const edigpu_sector* s);  // ignoring the phonon blocks
@@ -112,17 +113,16 @@ int launch_sb_rows_shard(const edigpu_sector* s, int64_t row0, int64_t count, in
 int launch_sb_cols_shard(const edigpu_sector* s, int p0, int np, int64_t q, int npmax, int world, const double* v, double* out,
                          hipStream_t st);
 int sb_nb0(int norb);
-int sb_cols_waves();
-int sb_cols_gs();
+int sb_cols_waves(int cw);  // cw: Switches::sb_cw, as for sb_cols_gs (host_sb.hpp)
 size_t sb_rows_lds(int nbw, int rimg_len, bool top = false);
 // one half of the rows kernel's product on a sector whose rows are staged in halves (h = 0 / 1: top walked level empty /
 // occupied); scal: the recurrence's scalars (stop flag) or null
 int launch_sb_rows_half(const edigpu_sector* s, int h, const double* v, double* hv, const double* scal, hipStream_t st);
 size_t sb_cols_lds(int nbw, int nloc, int max_chunk_rows, int max_chunk_slots, int gs);
-bool sb_rows_config(int norb, int slots, int plen, int cs, int* nt_out, int* nbt_out);
+bool sb_rows_config(int norb, int slots, int plen, int cs, int force_nt, int force_nbt, int* nt_out, int* nbt_out);
 size_t ib_rows_lds_bytes(int nb, int rimg_len);
 size_t ib_cols_lds_bytes(int nb, int max_chunk_rows, int max_chunk_blocks);
-bool ib_rows_config(int norb, int nb, int nlist, int plen, int rimg_len, int* nt_out, int* nbt_out, bool split = false);
+bool ib_rows_config(int norb, int nb, int nlist, int plen, int rimg_len, int force_nt, int* nt_out, int* nbt_out, bool split = false);
 int measure_membw(int64_t bytes, double out[3]);
 // stand-alone vector kernels with explicit device scalars (sharded loop)
 int vec_rotate(int64_t n, double* vin, double* vout, const double* beta2, hipStream_t st);

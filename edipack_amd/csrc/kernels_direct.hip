@@ -187,7 +187,7 @@ static int launch_direct_t(const edigpu_sector* s, const double* v_full, double*
                            int* np, const double* sig, hipStream_t st) {
   const int64_t nrow = s->nph > 0 ? s->dim_el : s->nloc;  // phonon sectors: one electronic block per launch
   int64_t nb = (nrow + kDirNT - 1) / kDirNT;
-  static const int wgs_per_cu = getenv("EDIGPU_DIRECT_WGS") ? atoi(getenv("EDIGPU_DIRECT_WGS")) : 2;
+  const int wgs_per_cu = s->sw.direct_wgs;
   if (nb > 256 * wgs_per_cu) nb = 256 * wgs_per_cu;  // persistent workgroups sweep the rows
   if (LZ && 3 * nb > cap) {
     set_error("launch_direct_lanczos: partial buffer too small");
@@ -196,8 +196,7 @@ static int launch_direct_t(const edigpu_sector* s, const double* v_full, double*
   if (np) *np = (int)nb;
   const size_t tab_bytes = (size_t)2 * sizeof(int32_t) << s->dir_ns;
   const size_t term_bytes = (size_t)kDirMaxTerms * (3 * sizeof(uint32_t) + sizeof(double2));
-  static const bool no_compact = getenv("EDIGPU_DIRECT_TERMORDER") != nullptr;
-  const bool compact = !no_compact && s->dir_nterms <= kDirMaxTerms;
+  const bool compact = !s->sw.direct_termorder && s->dir_nterms <= kDirMaxTerms;
   const double2* v2 = reinterpret_cast<const double2*>(v_full);
   double2* h2 = reinterpret_cast<double2*>(hv);
 #define EDIGPU_LAUNCH_DIRECT(LT, CP, LDSB)                                                                       \

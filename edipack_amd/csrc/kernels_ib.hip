@@ -812,7 +812,7 @@ size_t ib_cols_lds_bytes(int nb, int max_chunk_rows, int max_chunk_blocks) {
 
 // threads per workgroup / blocks per thread of the rows kernel for a list of nlist blocks and rows of plen columns;
 // false: no instantiation fits (the caller keeps the generic kernels)
-bool ib_rows_config(int norb, int nb, int nlist, int plen, int rimg_len, int* nt_out, int* nbt_out, bool split) {
+bool ib_rows_config(int norb, int nb, int nlist, int plen, int rimg_len, int force_nt, int* nt_out, int* nbt_out, bool split) {
   const size_t lds = ib_rows_lds_bytes(nb, rimg_len);
   if (lds > 158 * 1024) return false;
   // Candidates: threads per workgroup x blocks per thread the kernels are built for.  A lane has 128 registers when
@@ -820,8 +820,7 @@ bool ib_rows_config(int norb, int nb, int nlist, int plen, int rimg_len, int* nt
   // do.  Rank: threads resident per CU, then no more than 6 blocks per thread, then workgroups per CU (one workgroup
   // alone has nothing to overlap its barriers and row moves with), then fewer blocks per thread.
   static const int opts[3][4] = {{8, 14, 0, 0}, {4, 6, 8, 0}, {4, 6, 8, 12}};
-  int forced = 0;
-  if (const char* e = getenv("EDIGPU_IB_NT")) forced = atoi(e);  // tuning
+  const int forced = force_nt;  // tuning
   long best = -1;
   for (int nt : {256, 512, 768, 1024}) {
     if (split ? nt != 1024 : (forced && nt != forced)) continue;  // (split rows: built for 1024 threads only)
@@ -954,11 +953,10 @@ static int launch_cols2_t(const IbDev* d, const IbArgs& a, const double* v, doub
 // (with every per-element global access compiled out, -DIB_ABL=7, it still takes 0.94 ms).  At Ns = 17 a panel is 3.1 MB
 // and the two panels per XCD that the plain form keeps in flight no longer fit its 4 MB L2 (23.8 GB fetched per product
 // for 9.4 GB of V + result read-in): there the pipelined form, with one panel per XCD, measures 9.6 against 10.1 ms.
-// Default: panels above 2 MiB.  EDIGPU_IB_COLS2=0 / 1 overrides.
+// Default: panels above 2 MiB.  Switches::ib_cols2 overrides.
 static bool use_cols2(const IbDev* d) {
-  static const char* e = getenv("EDIGPU_IB_COLS2");
   if (ib_cols2_lds_bytes(d->nb_dw, d->max_chunk_rows, d->max_chunk_blocks) > 156 * 1024) return false;
-  if (e) return atoi(e) != 0;
+  if (d->cols2) return *d->cols2 != 0;
   return d->dim_dw * (int64_t)(kIbPanel * sizeof(double)) > ((int64_t)2 << 20);
 }
 
@@ -1034,10 +1032,9 @@ int launch_ib(const edigpu_sector* s, const double* v, double* hv, hipStream_t s
 int launch_ib_lanczos(const edigpu_sector* s, const double* P, double* Q, double* X, const double* scal, double* partial,
                       int64_t partial_cap, bool first, bool lazy_axpy, hipStream_t st, int* npartial) {
   // The Lanczos step of the local-block kernels (launch_sb_lanczos chooses between its fused and its semi-fused form);
-  // EDIGPU_SB_STEP=0 keeps the step on the kernels below while the plain product runs on the local blocks.
+  // LoopSwitches::sb_step == 0 keeps the step on the kernels below while the plain product runs on the local blocks.
   if (s->ib->sb && s->ib->sb->nhalf == 1) {
-    const char* es = getenv("EDIGPU_SB_STEP");
-    const bool sb_step = (es ? atoi(es) != 0 : true) || s->ib->pr.on;  // (short rows: the two-buffer step of launch_sb_lanczos only)
+    const bool sb_step = s->lz.sb_step != 0 || s->ib->pr.on;  // (short rows: the two-buffer step of launch_sb_lanczos only)
     if (sb_step) return launch_sb_lanczos(s, P, Q, X, scal, partial, partial_cap, first, lazy_axpy, st, npartial);
   }
   IbArgs a;

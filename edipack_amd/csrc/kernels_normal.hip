@@ -465,10 +465,10 @@ __global__ void __launch_bounds__(NT)
 
 // TD rows of V (8 B/elem) must fit the LDS budget of one workgroup.  Keep two
 // workgroups per CU when possible (<= 64 KiB each of the 160 KiB LDS).
-int normal_pick_rows_per_block(int64_t dim_up, int64_t dw_count) {
+int normal_pick_rows_per_block(int64_t dim_up, int64_t dw_count, OptInt rows_td) {
   const int64_t row_bytes = ((dim_up + 2) & ~(int64_t)1) * 8;  // staged row: columns + zero slot
-  if (const char* e = getenv("EDIGPU_ROWS_TD")) {  // tuning override
-    const int td = atoi(e);
+  if (rows_td) {  // tuning override
+    const int td = *rows_td;
     if ((td == 1 || td == 2 || td == 4 || td == 8) && td * row_bytes <= 150 * 1024) return td;
   }
   if (row_bytes > 150 * 1024) return 0;  // generic (no LDS) kernel
@@ -671,12 +671,12 @@ int launch_normal(const edigpu_sector* s, const double* v_local, const double* v
   if (phase == 1) return launch_rows(s, a, v_local, v_full, hv, 1, st);
   if (phase == 3) {
     if (launch_rows(s, a, v_local, v_full, hv, csr_nd ? 5 : 1, st)) return 1;
-    if (launch_dw_panels(a, true, fac_nd, v_full, hv, st)) return 1;
+    if (launch_dw_panels(a, s->sw, true, fac_nd, v_full, hv, st)) return 1;
     return sell_nd ? launch_csr(s->nd, 0, v_full, hv, 1, st) : 0;
   }
   // phase 2: the terms that need the gathered vector, accumulated into hv
   if (csr_nd && launch_rows(s, a, v_local, v_full, hv, 4, st)) return 1;
-  if (launch_dw_panels(a, true, fac_nd, v_full, hv, st)) return 1;
+  if (launch_dw_panels(a, s->sw, true, fac_nd, v_full, hv, st)) return 1;
   return sell_nd ? launch_csr(s->nd, 0, v_full, hv, 1, st) : 0;
 }
 
@@ -746,7 +746,7 @@ int launch_normal_cols(const edigpu_sector* s, int64_t col_first, int64_t ncol, 
   NormalArgs a;
   fill_args(s, a);
   const bool fac_nd = s->factored && a.nterms > 0;
-  return launch_dw_panel_cols(a, fac_nd, col_first, ncol, stride, halo, w, hv, st);
+  return launch_dw_panel_cols(a, s->sw, fac_nd, col_first, ncol, stride, halo, w, hv, st);
 }
 
 // One fused Lanczos step on a single-shard normal handle (see normal_rows_kernel FUSE):
@@ -757,7 +757,7 @@ bool normal_lanczos_fusable(const edigpu_sector* s) {
   if (s->kind != 0 || s->nloc != s->dim || s->dw_count == 0 || s->nph > 0) return false;
   if (s->rows_per_block == 0) return false;               // needs the LDS row kernel
   if (!s->factored && s->has_nd && !s->nd.sell) return false;  // CSR Hnd inside the row kernel needs the complete new vector
-  if (getenv("EDIGPU_LANCZOS_UNFUSED")) return false;
+  if (s->sw.lanczos_unfused) return false;
   return true;
 }
 
@@ -769,16 +769,15 @@ int launch_normal_lanczos(const edigpu_sector* s, double* P, double* Q, const do
   a.scal = scal;
   a.partial = partial;
   a.partial_cap = partial_cap;
-  // EDIGPU_LANCZOS_INKERNEL_FINALIZE=1: the sweep's last workgroup finalizes the step itself (lz_finalize.hpp) instead of
+  // Switches::lanczos_inkernel_finalize: the sweep's last workgroup finalizes the step itself (lz_finalize.hpp) instead of
   // a separate 5 us kernel.  OPT-IN: it buys nothing.  With a release fence per workgroup (which writes back the XCD's
   // whole L2 on this part) it measured 306 against 162 us per step on config 2; in the fence-free form (device-scope
   // stores / loads for the partials) 167.8 against 162.3 (config 2), 20.9 against 20.1 (config 3), 10.8 against 11.4
   // (config 1): the reduction of a few thousand partials by one workgroup takes as long at the tail of the sweep as it
   // does in its own kernel.
-  static const bool inkernel = getenv("EDIGPU_LANCZOS_INKERNEL_FINALIZE") && atoi(getenv("EDIGPU_LANCZOS_INKERNEL_FINALIZE")) != 0;
   const bool explicit_nd = !s->factored && s->has_nd && s->nd.sell;
   if (finalized) *finalized = false;
-  if (inkernel && lazy_axpy && !explicit_nd && s->d_lzcnt && finalized) {
+  if (s->sw.lanczos_inkernel_finalize && lazy_axpy && !explicit_nd && s->d_lzcnt && finalized) {
     a.lz_counter = s->d_lzcnt;
     a.lz_nlanc = nlanc;
     a.lz_len = s->lz_len;
@@ -799,15 +798,15 @@ int launch_normal_lanczos(const edigpu_sector* s, double* P, double* Q, const do
     a.blk_ps = s->blk_ps;
   }
   if (launch_rows(s, a, P, P, Q, first ? 101 : (lazy_axpy ? 103 : 102), st)) return 1;
-  if (s->lz_blocked) return launch_dw_blocked(a, a.nterms > 0, P, Q, st, true, npartial);
+  if (s->lz_blocked) return launch_dw_blocked(a, s->sw, a.nterms > 0, P, Q, st, true, npartial);
   const bool fac_nd = s->factored && a.nterms > 0 && s->d_mx_rowptr != nullptr;
   if (!s->factored && s->has_nd && s->nd.sell) {
     // explicit image (hand-over arrays): panels without the dot, then Q += Hnd v as a SELL pass whose
     // epilogue carries the <v|Q>, <Q|Q> partials
-    if (launch_dw_panels(a, true, false, P, Q, st)) return 1;
+    if (launch_dw_panels(a, s->sw, true, false, P, Q, st)) return 1;
     return launch_csr_lanczos(s->nd, 0, P, Q, partial, partial_cap, npartial, scal + SC_ALPHA, st);
   }
-  return launch_dw_panels(a, true, fac_nd, P, Q, st, true, npartial);
+  return launch_dw_panels(a, s->sw, true, fac_nd, P, Q, st, true, npartial);
 }
 
 // plain H*v on panel-major vectors (the product of the blocked Lanczos loop without the fused recurrence)
@@ -822,7 +821,7 @@ int launch_normal_blocked(const edigpu_sector* s, const double* v, double* hv, h
   a.blk_shift = s->blk_shift;
   a.blk_ps = s->blk_ps;
   if (launch_rows(s, a, v, v, hv, 1, st)) return 1;
-  return launch_dw_blocked(a, a.nterms > 0, v, hv, st, false, nullptr);
+  return launch_dw_blocked(a, s->sw, a.nterms > 0, v, hv, st, false, nullptr);
 }
 
 }  // namespace edigpu

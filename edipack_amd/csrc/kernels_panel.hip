@@ -1080,7 +1080,7 @@ static int launch_dw_blocked_tiles(const NormalArgs& a, bool do_nd, const double
   return 0;
 }
 
-int launch_dw_blocked(const NormalArgs& a, bool do_nd, const double* v, double* hv, hipStream_t st, bool alpha,
+int launch_dw_blocked(const NormalArgs& a, const Switches& sw, bool do_nd, const double* v, double* hv, hipStream_t st, bool alpha,
                       int* nblocks) {
   if (a.blk_shift == 7) return launch_dw_blocked_tiles(a, do_nd, v, hv, st, alpha, nblocks);
   if (a.blk_shift < 4 || a.blk_shift > 6 || a.blk_rows < 32 || !a.bl_meta || !a.bl_ent || !a.bl_wtab || !a.bl_lend || a.blk_list_cap < 4 || a.dw_first != 0 ||
@@ -1101,13 +1101,9 @@ int launch_dw_blocked(const NormalArgs& a, bool do_nd, const double* v, double* 
   p.list_cap = a.blk_list_cap;
   const size_t lds = (size_t)p.rows_per_task * (W / 2) * sizeof(double2) + (size_t)p.list_cap * sizeof(uint32_t) +
                      (size_t)p.rows_per_task * sizeof(int4);
-  // a persistent grid: as many workgroups as stay resident (EDIGPU_BLOCKED_WGS caps them per CU), each walking its
+  // a persistent grid: as many workgroups as stay resident (Switches::blocked_wgs caps them per CU), each walking its
   // XCD's tasks in order, so that an XCD works on one panel (at a boundary: two) at a time
-  static const int cap_per_cu = [] {
-    const char* e = getenv("EDIGPU_BLOCKED_WGS");
-    const int n = e ? atoi(e) : 8;
-    return n >= 1 && n <= 8 ? n : 8;
-  }();
+  const int cap_per_cu = sw.blocked_wgs >= 1 && sw.blocked_wgs <= 8 ? sw.blocked_wgs : 8;
   const int64_t most = (int64_t)p.panels_per_xcd * p.nchunks * 8;
 #define EDIGPU_LAUNCH_BLK2(SH, ND, AL)                                                                  \
   do {                                                                                                  \
@@ -1150,24 +1146,16 @@ int launch_dw_blocked(const NormalArgs& a, bool do_nd, const double* v, double* 
   return 0;
 }
 
-static int panel_resident_blocks() {
-  // EDIGPU_PANEL_BPP: workgroups per panel (tuning knob); default = what one XCD keeps resident
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("EDIGPU_PANEL_BPP");
-    v = e ? atoi(e) : 128;
-    if (v < 1) v = 128;
-  }
-  return v;
+// workgroups per panel (Switches::panel_bpp, tuning knob); default = what one XCD keeps resident
+static int panel_resident_blocks(const Switches& sw) {
+  const int v = sw.panel_bpp.value_or(128);
+  return v < 1 ? 128 : v;
 }
 
 // panels over ncol columns: a multiple of 8 (one stream of panels per XCD), at most 64 columns wide
-static void plan_panels(PanelArgs& p, int64_t ncol) {
-  int wmax = 64;
-  if (const char* e = getenv("EDIGPU_PANEL_W")) {
-    wmax = atoi(e);
-    if (wmax < 1 || wmax > 64) wmax = 64;
-  }
+static void plan_panels(PanelArgs& p, int64_t ncol, const Switches& sw) {
+  int wmax = sw.panel_w.value_or(64);
+  if (wmax < 1 || wmax > 64) wmax = 64;
   int np = (int)((ncol + 8 * wmax - 1) / (8 * wmax)) * 8;
   if (np < 8) np = 8;
   p.width = (int)((ncol + np - 1) / np);
@@ -1179,7 +1167,7 @@ static void plan_panels(PanelArgs& p, int64_t ncol) {
 // vector_transpose_MPI): w holds the columns [col_first - halo, col_first + ncol + halo) of ALL DimDw rows
 // (row stride `stride`: the full column block of the exchange, which the last rank only partly owns); hv (same layout) receives (Hdw (x) 1 + Hnd) v for the ncol owned columns.
 // a must describe the whole sector (dw_first = 0, dw_count = DimDw).
-int launch_dw_panel_cols(const NormalArgs& a, bool do_nd, int64_t col_first, int64_t ncol, int64_t stride, int halo,
+int launch_dw_panel_cols(const NormalArgs& a, const Switches& sw, bool do_nd, int64_t col_first, int64_t ncol, int64_t stride, int halo,
                          const double* w, double* hv, hipStream_t st) {
   if (ncol <= 0) return 0;
   if (do_nd && a.nterms > kMaxNdTerms) {
@@ -1187,12 +1175,12 @@ int launch_dw_panel_cols(const NormalArgs& a, bool do_nd, int64_t col_first, int
     return 1;
   }
   PanelArgs p;
-  plan_panels(p, ncol);
+  plan_panels(p, ncol, sw);
   p.col_first = col_first;
   p.ncol = ncol;
   p.stride = stride;
   p.halo = halo;
-  int bpp = panel_resident_blocks();
+  int bpp = panel_resident_blocks(sw);
   p.rows_per_block = (int)((a.dw_count + bpp - 1) / bpp);
   if (p.rows_per_block < 16) p.rows_per_block = 16;
   bpp = (int)((a.dw_count + p.rows_per_block - 1) / p.rows_per_block);
@@ -1207,7 +1195,7 @@ int launch_dw_panel_cols(const NormalArgs& a, bool do_nd, int64_t col_first, int
   return 0;
 }
 
-int launch_dw_panels(const NormalArgs& a, bool do_dw, bool do_nd, const double* v_full, double* hv,
+int launch_dw_panels(const NormalArgs& a, const Switches& sw, bool do_dw, bool do_nd, const double* v_full, double* hv,
                      hipStream_t st, bool alpha, int* nblocks) {
   if (!do_dw && !do_nd && !alpha) return 0;
   if (do_nd && a.nterms > kMaxNdTerms) {
@@ -1221,26 +1209,23 @@ int launch_dw_panels(const NormalArgs& a, bool do_dw, bool do_nd, const double* 
                      (!do_nd || a.tl_has_nd);
   PanelArgs p;
   if (vec2) {
-    int wmax = 128;
-    if (const char* e = getenv("EDIGPU_PANEL_W")) {
-      wmax = atoi(e) & ~1;
-      if (wmax < 2 || wmax > 128) wmax = 128;
-    }
+    int wmax = sw.panel_w.value_or(128) & ~1;
+    if (wmax < 2 || wmax > 128) wmax = 128;
     int np = (int)((a.dim_up + 8 * wmax - 1) / (8 * wmax)) * 8;
     if (np < 8) np = 8;
     p.width = (int)((a.dim_up + np - 1) / np);
     p.width += p.width & 1;
     p.npanels = (int)((a.dim_up + p.width - 1) / p.width);
   } else {
-    plan_panels(p, a.dim_up);
+    plan_panels(p, a.dim_up, sw);
   }
   p.col_first = 0;
   p.ncol = a.dim_up;
   p.stride = a.dim_up;
   p.halo = 0;
   p.tile_rows = 0;
-  int bpp = panel_resident_blocks();
-  if (vec2 && !getenv("EDIGPU_PANEL_BPP")) bpp = 256;  // half as many panels: twice the workgroups on each (measured)
+  int bpp = panel_resident_blocks(sw);
+  if (vec2 && !sw.panel_bpp) bpp = 256;  // half as many panels: twice the workgroups on each (measured)
   p.rows_per_block = (int)((a.dw_count + bpp - 1) / bpp);
   if (p.rows_per_block < 16) p.rows_per_block = 16;
   bpp = (int)((a.dw_count + p.rows_per_block - 1) / p.rows_per_block);
@@ -1265,9 +1250,9 @@ int launch_dw_panels(const NormalArgs& a, bool do_dw, bool do_nd, const double* 
     // more than there are tasks
     const int64_t ntasks = (int64_t)panel_groups * bpp * 8;
     // workgroup size: 512 threads (4 per CU) while a chunk fits their registers, else 1024 (2 per CU, twice the rows);
-    // EDIGPU_TILE_PERSIST=1: a persistent grid (as many workgroups as stay resident, each looping over its tasks)
+    // Switches::tile_persist: a persistent grid (as many workgroups as stay resident, each looping over its tasks)
     // instead of one task per workgroup -- measured 3-5 % slower on config 2 and the Ns=15 ladder
-    static const bool persist = getenv("EDIGPU_TILE_PERSIST") && atoi(getenv("EDIGPU_TILE_PERSIST")) != 0;
+    const bool persist = sw.tile_persist;
     const bool big = p.tile_rows > kTileRowsPerWave * (kPanelNT / 64);
 #define EDIGPU_LAUNCH_P3T(NTV, ND, AL)                                                                         \
   do {                                                                                                         \

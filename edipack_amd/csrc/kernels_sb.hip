@@ -14,13 +14,8 @@ int sb_cols_3(const IbDev* d, const SbArgs& a, int mode, const double* v, double
 // low bath levels folded into the blocks, per orbital count: the kernels are built for 5 local levels
 int sb_nb0(int norb) { return norb >= 1 && norb <= 3 ? 5 - norb : 0; }
 
-// columns kernel: blocks per wave-slot (8: two columns per lane, 256 threads; 4: one column per lane, 512 threads) and waves
-// per workgroup.  EDIGPU_SB_CW = 1 / 2 chooses (tuning)
-int sb_cols_gs() {
-  const char* e = getenv("EDIGPU_SB_CW");  // (read per sector set-up)
-  return e && atoi(e) == 1 ? 4 : 8;
-}
-int sb_cols_waves() { return sb_cols_gs() == 4 ? 8 : SB_COLS_NT2 / 64; }
+// columns kernel: waves per workgroup (blocks per wave-slot: sb_cols_gs, host_sb.hpp)
+int sb_cols_waves(int cw) { return sb_cols_gs(cw) == 4 ? 8 : SB_COLS_NT2 / 64; }
 
 size_t sb_rows_lds(int nbw, int rimg_len, bool top) { return sb_rows_lds_bytes(nbw, rimg_len, top); }
 
@@ -30,13 +25,11 @@ size_t sb_cols_lds(int nbw, int nloc, int max_chunk_rows, int max_chunk_slots, i
 
 // threads per workgroup / blocks per thread of the rows kernel for `slots` wave-slots, rows of plen columns (padded) and a
 // row image of class stride cs; false: no instantiation fits (the caller keeps the impurity-block kernels).
-// EDIGPU_SB_NT / EDIGPU_SB_NBT force one.
-bool sb_rows_config(int norb, int slots, int plen, int cs, int* nt_out, int* nbt_out) {
+// force_nt / force_nbt (Switches::sb_nt, sb_nbt), when not 0, force one.
+bool sb_rows_config(int norb, int slots, int plen, int cs, int force_nt, int force_nbt, int* nt_out, int* nbt_out) {
   const int nloc = norb + sb_nb0(norb);
   const int maxm = sb::binom(nloc, nloc / 2);
-  int fnt = 0, fnbt = 0;
-  if (const char* e = getenv("EDIGPU_SB_NT")) fnt = atoi(e);
-  if (const char* e = getenv("EDIGPU_SB_NBT")) fnbt = atoi(e);
+  const int fnt = force_nt, fnbt = force_nbt;
 #define EDIGPU_SB_ONE(NT, NBT, CS)                                                                              \
   if (cs == CS && (!fnt || fnt == NT) && (!fnbt || fnbt == NBT) && slots <= (NT / 64) * NBT &&                    \
       plen / 2 <= NT * sb_rows_nld(NBT, maxm)) {                                                                \
@@ -143,8 +136,7 @@ int launch_sb_rows_half(const edigpu_sector* s, int h, const double* v, double* 
 int launch_sb(const edigpu_sector* s, const double* v, double* hv, hipStream_t st) {
   SbArgs a;
   fill_sb_args(s->ib, a);
-  static const bool stamp = getenv("EDIGPU_SB_STAMP") != nullptr;
-  if (stamp) {  // measurement aid: cycles per phase of the rows kernel, workgroup 0, printed per launch
+  if (s->sw.sb_stamp) {  // measurement aid: cycles per phase of the rows kernel, workgroup 0, printed per launch
     static long long* dbg = nullptr;
     if (!dbg) EDIGPU_HIP(hipMalloc((void**)&dbg, 32 * 8 * sizeof(long long)));
     EDIGPU_HIP(hipMemsetAsync(dbg, 0, 32 * 8 * sizeof(long long), st));
@@ -189,9 +181,8 @@ int launch_sb_lanczos(const edigpu_sector* s, const double* P, double* Q, double
   // The fused rows kernel (x formed while the row is staged, - beta P_old subtracted when the result leaves: three more
   // streams of pieces) fits its registers in the 256- and 512-thread geometries.  In the 768-thread geometry of the longest
   // rows it spills (2.4 ms per launch at Ns = 16 against 0.83 plain): there the new vector is its own pass, the plain rows
-  // kernel follows, and the columns kernel joins - beta P_old to the rows kernel's part.  EDIGPU_SB_STEP=2 forces that form.
-  const char* es = getenv("EDIGPU_SB_STEP");
-  if (s->ib->sb->rows_nt == 768 || (es && atoi(es) == 2)) {
+  // kernel follows, and the columns kernel joins - beta P_old to the rows kernel's part.  LoopSwitches::sb_step == 2 forces that form.
+  if (s->ib->sb->rows_nt == 768 || s->lz.sb_step == 2) {
     if (lz_next_vector(P, Q, X, s->ib->len, scal, lazy_axpy, st) || rows(s->ib, a, 0, X, Q, nullptr, st)) return 1;
     a.pold = P;
     return cols(s->ib, a, 1, X, Q, st, npartial);

@@ -86,14 +86,15 @@ struct NormalArgs {
 
 // B: (Hdw (x) 1) + factored Hnd as an L2-blocked column-panel sweep (kernels_panel.hip).
 // alpha: also write the per-workgroup partials of <v|hv> and <hv|hv> (fused Lanczos step).
-int launch_dw_panels(const NormalArgs& a, bool do_dw, bool do_nd, const double* v_full, double* hv,
+// sw (here and below): the sector's set-up snapshot, from which the launchers take their grid shapes.
+int launch_dw_panels(const NormalArgs& a, const Switches& sw, bool do_dw, bool do_nd, const double* v_full, double* hv,
                      hipStream_t st, bool alpha = false, int* nblocks = nullptr);
 
 // the same sweep on vectors in the panel-major layout (a.blk_shift > 0)
-int launch_dw_blocked(const NormalArgs& a, bool do_nd, const double* v, double* hv, hipStream_t st, bool alpha,
+int launch_dw_blocked(const NormalArgs& a, const Switches& sw, bool do_nd, const double* v, double* hv, hipStream_t st, bool alpha,
                       int* nblocks);
 
-int launch_dw_panel_cols(const NormalArgs& a, bool do_nd, int64_t col_first, int64_t ncol, int64_t stride, int halo,
+int launch_dw_panel_cols(const NormalArgs& a, const Switches& sw, bool do_nd, int64_t col_first, int64_t ncol, int64_t stride, int halo,
                          const double* w, double* hv, hipStream_t st);
 
 }  // namespace edigpu

@@ -10,6 +10,7 @@
 #include "host_build.hpp"
 #include "host_ib.hpp"
 #include "ib_core.hpp"
+#include "switches.cpp"  // (compiled into this shim: it samples the environment at every call, like the C-ABI builders)
 using namespace edigpu;
 
 static std::string g_err;
@@ -153,7 +154,7 @@ void emulate_cols(const HostIb& ib, const std::vector<double>& v, std::vector<do
 extern "C" int host_ib_check2(const edigpu_model* m, int nup, int ndw, int max_chunk_rows, int lds_budget, int32_t* info,
                               double* maxdiff) {
   HostNormal hn;
-  g_err = build_normal(*m, nup, ndw, 0, -1, hn, true);
+  g_err = build_normal(*m, nup, ndw, 0, -1, hn, true, !Switches::sample().nd_no_merge);
   if (!g_err.empty()) return 2;
   HostIb ib;
   build_ib(hn, max_chunk_rows, ib, lds_budget);

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "host_build.hpp"
+#include "switches.cpp"  // (compiled into this shim: it samples the environment at every call, like the C-ABI builders)
 using namespace edigpu;
 
 static std::string g_err;
@@ -16,7 +17,7 @@ extern "C" const char* host_image_error() { return g_err.c_str(); }
 // out: dim x dim row-major, zeroed here.  form 0 = explicit arrays, 1 = factored tables.
 extern "C" int host_normal_dense(const edigpu_model* m, int nup, int ndw, int form, double* out, int64_t dim) {
   HostNormal hn;
-  g_err = build_normal(*m, nup, ndw, 0, -1, hn, form == 0);
+  g_err = build_normal(*m, nup, ndw, 0, -1, hn, form == 0, !Switches::sample().nd_no_merge);
   if (!g_err.empty()) return 1;
   const int64_t du = hn.dim_up, dd = hn.dim_dw;
   if (du * dd != dim) { g_err = "host_normal_dense: dim mismatch"; return 2; }
@@ -69,7 +70,7 @@ extern "C" int host_flat_dense(const edigpu_model* m, int sector, double* out, i
 // the on-the-fly image (term list + diagonal tables of build_direct) evaluated the way direct_rows_kernel does
 extern "C" int host_direct_dense(const edigpu_model* m, int sector, double* out, int64_t dim) {
   HostDirect hd;
-  g_err = build_direct(*m, sector, 0, -1, hd);
+  g_err = build_direct(*m, sector, 0, -1, hd, false, 0, !Switches::sample().direct_nosort);
   if (!g_err.empty()) return 1;
   if (hd.dim != dim) { g_err = "host_direct_dense: dim mismatch"; return 2; }
   std::memset(out, 0, sizeof(double) * 2 * dim * dim);
@@ -95,7 +96,7 @@ extern "C" int host_direct_dense(const edigpu_model* m, int sector, double* out,
 
 extern "C" int host_direct_refuses(const edigpu_model* m, int sector) {
   HostDirect hd;
-  g_err = build_direct(*m, sector, 0, -1, hd);
+  g_err = build_direct(*m, sector, 0, -1, hd, false, 0, !Switches::sample().direct_nosort);
   return g_err.empty() ? 0 : 1;
 }
 
@@ -143,7 +144,7 @@ extern "C" int host_flat_jz_dense(const edigpu_model* m, int ntot, int twojz, do
 // its position in the map.
 extern "C" int host_direct_jz_dense(const edigpu_model* m, int ntot, int twojz, double* out, int64_t dim) {
   HostDirect hd;
-  g_err = build_direct(*m, ntot, 0, -1, hd, true, twojz);
+  g_err = build_direct(*m, ntot, 0, -1, hd, true, twojz, !Switches::sample().direct_nosort);
   if (!g_err.empty()) return 1;
   if (hd.dim != dim) { g_err = "host_direct_jz_dense: dim mismatch"; return 2; }
   const int ns = hd.ns;
@@ -172,7 +173,7 @@ extern "C" int host_direct_jz_dense(const edigpu_model* m, int ntot, int twojz, 
 // complex layout read as real
 extern "C" int host_normal_doubled_dense(const edigpu_model* m, int nup, int ndw, double* out, int64_t dim2, int* nterms) {
   HostNormal hn;
-  g_err = build_normal_doubled(*m, nup, ndw, hn, 16);
+  g_err = build_normal_doubled(*m, nup, ndw, hn, 16, !Switches::sample().nd_no_merge);
   if (!g_err.empty()) return 1;
   const int64_t du = hn.dim_up, dd = hn.dim_dw;
   if (du * dd != dim2) { g_err = "host_normal_doubled_dense: dim mismatch"; return 2; }

@@ -8,6 +8,7 @@
 
 #include "host_build.hpp"
 #include "host_pack.hpp"
+#include "switches.cpp"  // (compiled into this shim: it samples the environment at every call, like the C-ABI builders)
 using namespace edigpu;
 
 namespace {
@@ -54,7 +55,7 @@ const char* hp_error() { return g_err.c_str(); }
 // the sector (nup, ndw) of a model; dims: dim_up, dim_dw, nnz(Hup), nnz(Hdw), Hnd terms
 int hp_build_normal(const edigpu_model* m, int nup, int ndw, int64_t* dims) {
   g_hn = HostNormal();
-  g_err = build_normal(*m, nup, ndw, 0, -1, g_hn, false);
+  g_err = build_normal(*m, nup, ndw, 0, -1, g_hn, false, !Switches::sample().nd_no_merge);
   if (!g_err.empty()) return 1;
   dims[0] = g_hn.dim_up;
   dims[1] = g_hn.dim_dw;

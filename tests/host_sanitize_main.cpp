@@ -1,12 +1,16 @@
 // CPU-side sanitizer harness (ASan + UBSan) for the host builders of libedigpu (csrc/host_build.cpp): every bath type,
 // mode and sector of a few small models, shards included; the image encoders of the generic kernels (csrc/host_pack.cpp)
-// on one sector with Hnd terms.  Built and run by tests/test_host_sanitizers.py.
+// on one sector with Hnd terms; the three snapshots of the environment switches (csrc/switches.cpp).  Built and run by
+// tests/test_host_sanitizers.py.
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <random>
+#include <string>
 #include "host_build.hpp"
 #include "host_ib.hpp"
 #include "host_pack.hpp"
+#include "switches.hpp"
 using namespace edigpu;
 static void fill(edigpu_model& m, int mode, int bath, int norb, int nbath) {
   memset(&m, 0, sizeof(m));
@@ -52,8 +56,30 @@ static int pack_images() {
   printf("host_pack: %d of 7 ELL, %d of 9 SELL, %d of 12 tile / merged lists, %d of 6 block lists, col_halo %d\n", nell, nsell, nlist, nblk, halo);
   return 1;
 }
+// the three snapshots with an empty environment, with every switch set to "" and to 4 KiB of digits (out of every range)
+static int switch_snapshots() {
+  int n = 0, bad = 0;
+  const SwitchRow* rows = switch_table(&n);
+  const std::string digits(4096, '7');
+  clearenv();
+  for (const char* text : {(const char*)nullptr, "", digits.c_str()}) {
+    for (int i = 0; text && i < n; i++) setenv(rows[i].name, text, 1);
+    const Switches sw = Switches::sample();
+    const CommSwitches cs = CommSwitches::sample();
+    const LoopSwitches ls = LoopSwitches::sample();
+    const bool given = text != nullptr, empty = given && !text[0];
+    bad += sw.lanczos_unfused != given || cs.force_collectives != given || ls.lanczos_exactbeta != given;  // presence
+    bad += sw.ell16 != !empty || sw.posrows != (given && !empty) || sw.normal_explicit;                    // atoi, first character
+    bad += sw.rows_td.has_value() != given || ls.trl_thr.has_value() != given;                              // derived defaults
+    if (!given || empty)  // (what atoi makes of 4 KiB of digits is the C library's business: only that nothing breaks)
+      bad += sw.ib_rows != (empty ? 4 : 480) || sw.tile_rows != (empty ? 8 : 32) || sw.ib_min_row_bytes() != (empty ? 0 : 40 * 1024);
+  }
+  clearenv();
+  if (bad) printf("switch snapshots: %d wrong values\n", bad);
+  return bad != 0;
+}
 int main() {
-  int nfail = pack_images(), nib = 0, njz = 0;
+  int nfail = pack_images() + switch_snapshots(), nib = 0, njz = 0;
   for (int bath = 0; bath < 4; bath++) for (int norb = 1; norb <= 3; norb++) for (int nbath = 1; nbath <= 3; nbath++) {
     edigpu_model m; fill(m, 0, bath, norb, nbath);
     int ns = model_ns(m);

@@ -11,6 +11,7 @@
 #include "host_ib.hpp"
 #include "host_sb.hpp"
 #include "sb_core.hpp"
+#include "switches.cpp"  // (compiled into this shim: it samples the environment at every call, like the C-ABI builders)
 using namespace edigpu;
 
 static std::string g_err;
@@ -309,7 +310,8 @@ extern "C" int host_sb_check_split(const edigpu_model* m, int nup, int ndw, int 
 static int sb_check(const edigpu_model* m, int nup, int ndw, int nb0, int max_chunk_rows, int rows_nt, int rows_nbt,
                     int cols_nw, int cols_gs, int lds_budget, int32_t* info, double* maxdiff) {
   HostNormal hn;
-  g_err = build_normal(*m, nup, ndw, 0, -1, hn, true);
+  const Switches sw = Switches::sample();
+  g_err = build_normal(*m, nup, ndw, 0, -1, hn, true, !sw.nd_no_merge);
   if (!g_err.empty()) return 2;
   HostIb ib;
   build_ib(hn, max_chunk_rows, ib, lds_budget);
@@ -319,7 +321,7 @@ static int sb_check(const edigpu_model* m, int nup, int ndw, int nb0, int max_ch
     return 1;
   }
   HostSb sbt;
-  build_sb(hn, ib, nb0, max_chunk_rows, rows_nt, rows_nbt, cols_nw, sbt, cols_gs);
+  build_sb(hn, ib, nb0, max_chunk_rows, rows_nt, rows_nbt, cols_nw, sbt, cols_gs, sw.sb_amode);
   if (!sbt.valid) {
     g_err = sbt.why;
     return 1;
@@ -387,7 +389,8 @@ extern "C" int host_sb_check_shard(const edigpu_model* m, int nup, int ndw, int 
                                    int cols_nw, int cols_gs, int world, int32_t* info, double* maxdiff) {
   std::memset(info, 0, 8 * sizeof(int32_t));
   HostNormal hn;
-  g_err = build_normal(*m, nup, ndw, 0, -1, hn, true);
+  const Switches sw = Switches::sample();
+  g_err = build_normal(*m, nup, ndw, 0, -1, hn, true, !sw.nd_no_merge);
   if (!g_err.empty()) return 2;
   HostIb ib;
   build_ib(hn, max_chunk_rows, ib, 0);
@@ -396,7 +399,7 @@ extern "C" int host_sb_check_shard(const edigpu_model* m, int nup, int ndw, int 
     return 1;
   }
   HostSb sbt;
-  build_sb(hn, ib, nb0, max_chunk_rows, rows_nt, rows_nbt, cols_nw, sbt, cols_gs);
+  build_sb(hn, ib, nb0, max_chunk_rows, rows_nt, rows_nbt, cols_nw, sbt, cols_gs, sw.sb_amode);
   if (!sbt.valid) {
     g_err = sbt.why;
     return 1;
