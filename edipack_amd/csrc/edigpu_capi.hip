@@ -3276,6 +3276,7 @@ int edigpu_destroy(edigpu_handle s) {
   dev_free(s->d_dir_xtab);
   free_occ(s);
   free_rdm(s);
+  free_rdm_flat(s);
   dev_free(s->d_vin);
   dev_free(s->d_vout);
   dev_free(s->d_tmp);

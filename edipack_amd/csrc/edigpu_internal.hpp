@@ -189,6 +189,10 @@ void free_rdm(edigpu_sector* s);
 // device bytes of those tables (made lazily: the sector cache adds them like occ_table_bytes)
 int64_t rdm_table_bytes(const edigpu_sector* s);
 
+// The same of edigpu_imp_rdm_flat on a library-built whole superc / nonsu2 sector (host_rdm_flat.hpp; kernels_rdm_flat.hip).
+struct RdmFlatDev;
+void free_rdm_flat(edigpu_sector* s);
+
 }  // namespace edigpu
 
 struct edigpu_sector {
@@ -289,6 +293,7 @@ struct edigpu_sector {
   edigpu::OccDev* occ = nullptr;
   // ---- impurity reduced density matrix (lazily built) ----
   edigpu::RdmDev* rdm = nullptr;
+  edigpu::RdmFlatDev* rdm_flat = nullptr;
   // ---- Lanczos workspace (lazily allocated) ----
   int64_t partial_cap = 0;      // doubles in d_partial
   double* d_vin = nullptr;

@@ -4,6 +4,7 @@
 
 #include "edigpu_internal.hpp"
 #include "host_rdm.hpp"
+#include "host_rdm_flat.hpp"
 
 namespace edigpu {
 
@@ -257,5 +258,22 @@ size_t rdm_lds_bytes(const RdmArgs& a);
 // blocks of pstride doubles; groups: host array.  Enqueued on st, no synchronisation.
 int launch_imp_rdm(const RdmArgs& a, int nwork, const RdmGroup* groups, int ngroups, const double* v, int64_t vstride,
                    int nvec, double* partial, int64_t pstride, double* out, int64_t ostride, hipStream_t st);
+
+// ---- the same of superc / nonsu2 vectors (kernels_rdm_flat.hip; tables and work list: host_rdm_flat.hpp) ----
+struct RdmFlatArgs {  // the device copies of an RdmFlatPlan
+  int cw = 1, norb = 0, stage_max = 0, ept_max = 0, rel_max = 0;
+  int64_t dim_el = 0;
+  const int64_t* rowstart = nullptr;
+  const int32_t* bdw = nullptr;
+  const uint16_t* rel = nullptr;
+  const uint32_t* ent = nullptr;
+  const RdmFlatPanel* panels = nullptr;
+  const RdmFlatWork* work = nullptr;
+};
+// dynamic LDS of the tiles kernel: staged slab, accumulators, the panel's run starts
+size_t rdm_flat_lds_bytes(const RdmFlatArgs& a);
+// as launch_imp_rdm
+int launch_imp_rdm_flat(const RdmFlatArgs& a, int nwork, const RdmGroup* groups, int ngroups, const double* v, int64_t vstride,
+                        int nvec, double* partial, int64_t pstride, double* out, int64_t ostride, hipStream_t st);
 
 }  // namespace edigpu

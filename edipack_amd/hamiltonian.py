@@ -526,6 +526,22 @@ class SectorHamiltonian:
         capi.check(capi.lib().edigpu_time_rdm(self._h, v_ptr, warmup, steps, C.byref(ms)), "edigpu_time_rdm")
         return float(ms.value)
 
+    def imp_rdm_flat(self, v_ptr: int, nvec: int = 1):
+        """imp_rdm of a superc / nonsu2 sector (edigpu_imp_rdm_flat): (rho[nvec, D, D], norm2[nvec]) with the reference's
+        fermionic sign, rho in the basis |Iup Idw> (edipack_amd.observables.rdm_anomalous / rdm_magx read it)."""
+        d = 4 ** (self.norb or capi.MAXORB)
+        rho = np.zeros((nvec, d, d), dtype=np.complex128 if self.is_complex else np.float64)
+        nrm = np.zeros(nvec)
+        capi.check(capi.lib().edigpu_imp_rdm_flat(self._h, v_ptr, nvec, rho.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  capi.pd(nrm)), "edigpu_imp_rdm_flat")
+        return rho, nrm
+
+    def time_rdm_flat(self, v_ptr: int, warmup: int, steps: int) -> float:
+        """ms of the imp_rdm_flat kernels on one vector: the median over `steps` runs, HIP events; the vector is unchanged."""
+        ms = C.c_double(0.0)
+        capi.check(capi.lib().edigpu_time_rdm_flat(self._h, v_ptr, warmup, steps, C.byref(ms)), "edigpu_time_rdm_flat")
+        return float(ms.value)
+
     def lanczos_eigh(self, nitermax: int = 512, tol: float = 1e-12, check_every: int = 10,
                      v0: np.ndarray | None = None, want_vector: bool = True):
         """sp_lanc_eigh semantics (lowest eigenpair)."""

@@ -17,7 +17,9 @@ U = M[:n, :n] (up-up), D = M[n:, n:] (down-down), X = M[:n, n:] (up-down)
 ``SectorHamiltonian.imp_rdm`` (edigpu_imp_rdm) gives the other family, the impurity reduced density matrix
 rho = Tr_bath |v><v| in the ordering io = Iup + 2^norb Idw (imp_rdm_normal, ED_NORMAL/ED_RDM_NORMAL.f90): rdm_average
 normalises and averages it as that routine's loop over the states does, rdm_occupations reads its diagonal,
-entanglement_entropy its spectrum.
+entanglement_entropy its spectrum.  ``SectorHamiltonian.imp_rdm_flat`` (edigpu_imp_rdm_flat) is the same of superc /
+nonsu2 vectors (imp_rdm_superc, imp_rdm_nonsu2) in the basis |Iup Idw>; its blocks couple different (N_up, N_dw), and
+rdm_anomalous / rdm_magx read the anomalous amplitudes and the transverse magnetisation off it.
 
 Pure numpy: O(norb^2) numbers per vector (16^norb for the density matrix) reach the host."""
 from __future__ import annotations
@@ -89,6 +91,48 @@ def rdm_occupations(rho, norb: int):
     up = np.array([(io >> a) & 1 for a in range(n)], dtype=np.float64)
     dw = np.array([(io >> (n + a)) & 1 for a in range(n)], dtype=np.float64)
     return up @ p, dw @ p, (up * dw) @ p
+
+
+def _impurity_annihilators(norb: int):
+    """c_l of the 2 norb impurity levels (up 0 .. norb-1, then down 0 .. norb-1) in the 4^norb occupation space, bit l of
+    the state index = level l, with the Jordan-Wigner sign (-1)^(occupied levels below l)."""
+    n = int(norb)
+    D = 4 ** n
+    io = np.arange(D)
+    ops = []
+    for l in range(2 * n):
+        sel = io[(io >> l) & 1 == 1]
+        below = np.zeros(sel.size, dtype=np.int64)
+        for m in range(l):
+            below += (sel >> m) & 1
+        c = np.zeros((D, D))
+        c[sel ^ (1 << l), sel] = 1.0 - 2.0 * (below & 1)
+        ops.append(c)
+    return ops
+
+
+def _rdm_checked(rho, norb: int, who: str):
+    n = int(norb)
+    rho = np.asarray(rho)
+    if rho.shape != (4 ** n, 4 ** n):
+        raise ValueError(f"{who}: expected [{4 ** n}, {4 ** n}], got {rho.shape}")
+    return n, rho
+
+
+def rdm_anomalous(rho, norb: int) -> np.ndarray:
+    """phi[a, b] = <c_{b,up} c_{a,dw}> = tr(rho c_{b,up} c_{a,dw}) of the (normalised) rho[D, D] of imp_rdm_flat; complex.
+    The real part is phisc of the superc observables (ED_OBSERVABLES_SUPERC.f90)."""
+    n, rho = _rdm_checked(rho, norb, "rdm_anomalous")
+    c = _impurity_annihilators(n)
+    return np.array([[np.trace(rho @ (c[b] @ c[n + a])) for b in range(n)] for a in range(n)], dtype=np.complex128)
+
+
+def rdm_magx(rho, norb: int) -> np.ndarray:
+    """magX[a] = 2 Re <c+_{a,up} c_{a,dw}> = 2 Re tr(rho c+_{a,up} c_{a,dw}) of the (normalised) rho[D, D] of imp_rdm_flat
+    (ED_OBSERVABLES_NONSU2.f90)."""
+    n, rho = _rdm_checked(rho, norb, "rdm_magx")
+    c = _impurity_annihilators(n)
+    return np.array([2.0 * np.real(np.trace(rho @ (c[a].T @ c[n + a]))) for a in range(n)])
 
 
 def entanglement_entropy(rho) -> float:

@@ -252,6 +252,13 @@ module EDIGPU_SHIM
        real(c_double), intent(inout) :: rdm(*), norm2(*)
        integer(c_int) :: ierr
      end function edigpu_imp_rdm
+     function edigpu_imp_rdm_flat(h, v_dev, nvec, rdm, norm2) bind(C, name="edigpu_imp_rdm_flat") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, v_dev
+       integer(c_int), value :: nvec
+       real(c_double), intent(inout) :: rdm(*), norm2(*)
+       integer(c_int) :: ierr
+     end function edigpu_imp_rdm_flat
      function edigpu_apply_cops_normal(src, dst, v_src_dev, v_dst_dev, nops, coef, create, iorb, ispin, stream) &
           bind(C, name="edigpu_apply_cops_normal") result(ierr)
        import :: c_ptr, c_int, c_int32_t, c_double
@@ -424,7 +431,7 @@ module EDIGPU_SHIM
   public :: gpu_sp_lanc_eigh_d, gpu_sp_lanc_eigh_c, gpu_sp_eigh_d, gpu_sp_eigh_c
   public :: gpu_vec_alloc, gpu_vec_free, gpu_vec_upload_d, gpu_vec_download_d, gpu_vec_upload_c, gpu_vec_download_c
   public :: gpu_sp_lanc_eigh_dev, gpu_apply_op, gpu_apply_cops, gpu_lanc_tridiag_dev
-  public :: gpu_apply_op_N, gpu_apply_op_Sz, gpu_occ_moments, gpu_imp_rdm
+  public :: gpu_apply_op_N, gpu_apply_op_Sz, gpu_occ_moments, gpu_imp_rdm, gpu_imp_rdm_flat
   ! N > 1: communicator + the MPI twins of the product and of the tridiagonalisation
   public :: gpu_comm_unique_id, gpu_comm_create, gpu_comm_create_shm, gpu_comm_destroy, gpu_shard_plan
   public :: spMatVec_mpi_gpu_d, spMatVec_mpi_gpu_c, gpu_lanc_tridiag_mpi_d, gpu_lanc_tridiag_mpi_c
@@ -912,6 +919,15 @@ contains
     if (size(rdm, 3) /= size(norm2) .or. size(rdm, 1) /= size(rdm, 2)) stop "gpu_imp_rdm: shapes"
     call gpu_check(edigpu_imp_rdm(h, v_dev, int(size(norm2), c_int), rdm, norm2), "gpu_imp_rdm")
   end subroutine gpu_imp_rdm
+
+  !> The same of real vectors of a superc / nonsu2 sector (imp_rdm_superc, imp_rdm_nonsu2) with the reference's fermionic
+  !! sign: rho in the basis |Iup Idw>.  Complex handles return interleaved (re, im): call edigpu_imp_rdm_flat.
+  subroutine gpu_imp_rdm_flat(h, v_dev, rdm, norm2)
+    type(c_ptr), intent(in) :: h, v_dev
+    real(8), intent(inout) :: rdm(:, :, :), norm2(:)
+    if (size(rdm, 3) /= size(norm2) .or. size(rdm, 1) /= size(rdm, 2)) stop "gpu_imp_rdm_flat: shapes"
+    call gpu_check(edigpu_imp_rdm_flat(h, v_dev, int(size(norm2), c_int), rdm, norm2), "gpu_imp_rdm_flat")
+  end subroutine gpu_imp_rdm_flat
 
   !> vvinit = apply_Cops(v_state, coefs, Os, orbs, spins, isector, jsector) (ED_SECTOR.f90:839-960; the mixed seeds
   !! of the off-diagonal Green's functions, ED_NORMAL/ED_GF_NORMAL.f90:216-261): Os(i) = +1 for c^+, -1 for c

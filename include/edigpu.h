@@ -481,14 +481,39 @@ int edigpu_time_occ(edigpu_handle h, double *v_dev, int warmup, int steps, doubl
  *
  * Handles: whole sectors from edigpu_normal_build (phonon sectors included) and edigpu_normal_build_z, norb = 1 ..
  * EDIGPU_MAXORB.  Refused: superc / nonsu2 handles, stored or on the fly ("only ed_mode=normal sectors are supported":
- * those modes carry fermionic signs in the reference), and, with the messages of edigpu_occ_moments, ed_total_ud=F
- * handles, hand-over handles and shards.
+ * those modes carry fermionic signs in the reference and are served by edigpu_imp_rdm_flat below), and, with the messages
+ * of edigpu_occ_moments, ed_total_ud=F handles, hand-over handles and shards.
  */
 int edigpu_imp_rdm(edigpu_handle h, const double *v_dev, int nvec, double *rdm_host, double *norm2_host);
 /* Measurement helper for scripts/time_rdm.py: `warmup` untimed and `steps` timed runs of the device work of
  * edigpu_imp_rdm on one vector (all kernels, without the copy of the result) on the handle's stream, each run between
  * two HIP events; *ms = the median in milliseconds.  v_dev is left unchanged. */
 int edigpu_time_rdm(edigpu_handle h, const double *v_dev, int warmup, int steps, double *ms);
+
+/*
+ * The same of device vectors of a superc or nonsu2 sector (imp_rdm_superc, ED_SUPERC/ED_RDM_SUPERC.f90:54-183;
+ * imp_rdm_nonsu2, ED_NONSU2/ED_RDM_NONSU2.f90:54-188).  The blocks of this rho couple impurity states of different
+ * (N_up, N_dw), so it carries the anomalous amplitudes (phisc) and the transverse magnetisation (magX).
+ *
+ * A state of the sector map is s = iup + 2^Ns idw, iup = Iup + 2^norb Bup, idw = Idw + 2^norb Bdw.  For nvec consecutive
+ * device vectors (they must be complete when the call is made)
+ *   rdm[k][io][jo] = sum_{Bup, Bdw (, iph)} sgn v_k(Iup Bup Idw Bdw) conj v_k(Jup Bup Jdw Bdw),   norm2[k] = <v_k|v_k>
+ *   sgn = (-1)^( popcount(Bup) (popcount(Idw) + popcount(Jdw)) )
+ *   io = Iup + 2^norb Idw,  jo = Jup + 2^norb Jdw,  D = 4^norb
+ * sgn is the reference's signI signJ: it moves c+(Idw) in front of c+(Bup), so rho is in the basis |Iup Idw> (level order
+ * up 0 .. norb-1, then down 0 .. norb-1).  NOT divided by norm2; the phonon blocks of a phonon sector are traced.
+ * rdm_host, norm2_host, Hermiticity, the fixed summation order, the stream and the lazily built tables (freed by
+ * edigpu_destroy) are as for edigpu_imp_rdm; v_dev may be 8-byte aligned only and is left untouched.
+ *
+ * Handles: whole sectors from edigpu_flat_build and edigpu_direct_build, superc (sector = Sz) and nonsu2 (sector = Ntot),
+ * real or complex, norb = 1 .. 4.  Refused, each with a message that starts with the entry point's name: normal-mode
+ * handles ("use edigpu_imp_rdm"), Jz_basis handles (edigpu_flat_build_jz, edigpu_direct_build_jz: their rows are not plain
+ * particle-number maps), norb = 5 (a diagonal block of up to 252 x 252 per bath word does not fit the on-chip
+ * accumulators), and, with the messages of edigpu_occ_moments, ed_total_ud=F handles, hand-over handles and shards.
+ */
+int edigpu_imp_rdm_flat(edigpu_handle h, const double *v_dev, int nvec, double *rdm_host, double *norm2_host);
+/* Measurement helper for scripts/time_rdm.py, as edigpu_time_rdm: the device work of edigpu_imp_rdm_flat on one vector. */
+int edigpu_time_rdm_flat(edigpu_handle h, const double *v_dev, int warmup, int steps, double *ms);
 
 /*
  * Lowest eigenpair by plain Lanczos (lanc_method="lanczos": sp_lanc_eigh call
