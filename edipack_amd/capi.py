@@ -119,6 +119,9 @@ SIGNATURES = {
     "edigpu_time_rdm": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _pd]),
     "edigpu_imp_rdm_flat": (C.c_int, [_vp, _vp, C.c_int, _pd, _pd]),
     "edigpu_time_rdm_flat": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _pd]),
+    "edigpu_apply_xph": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "edigpu_ph_rdm": (C.c_int, [_vp, _vp, C.c_int, _pd, _pd]),
+    "edigpu_time_ph": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _pd]),
     "edigpu_vec_work_doubles": (C.c_int, []),
     "edigpu_vec_rotate": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
     "edigpu_vec_add_dot": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -3277,6 +3277,7 @@ int edigpu_destroy(edigpu_handle s) {
   free_occ(s);
   free_rdm(s);
   free_rdm_flat(s);
+  free_ph(s);
   dev_free(s->d_vin);
   dev_free(s->d_vout);
   dev_free(s->d_tmp);

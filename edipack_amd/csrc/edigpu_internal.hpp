@@ -193,6 +193,11 @@ int64_t rdm_table_bytes(const edigpu_sector* s);
 struct RdmFlatDev;
 void free_rdm_flat(edigpu_sector* s);
 
+// Tables and workspace of edigpu_apply_xph / edigpu_ph_rdm on a library-built whole phonon sector (host_ph.hpp;
+// kernels_ph.hip), made and uploaded by the first call on the handle and kept until edigpu_destroy.
+struct PhDev;
+void free_ph(edigpu_sector* s);
+
 }  // namespace edigpu
 
 struct edigpu_sector {
@@ -294,6 +299,8 @@ struct edigpu_sector {
   // ---- impurity reduced density matrix (lazily built) ----
   edigpu::RdmDev* rdm = nullptr;
   edigpu::RdmFlatDev* rdm_flat = nullptr;
+  // ---- phonon displacement seed and phonon density matrix (lazily built) ----
+  edigpu::PhDev* ph = nullptr;
   // ---- Lanczos workspace (lazily allocated) ----
   int64_t partial_cap = 0;      // doubles in d_partial
   double* d_vin = nullptr;

@@ -243,6 +243,22 @@ int occ_moment_waves(const OccTables& t, int ncu);
 int launch_occ_moments(const OccTables& t, const OccSlots& sl, const OccRuns& rn, const double* v, int nvec, int nwaves,
                        double* partial, double* sums, hipStream_t st);
 
+// ---- phonon operators (kernels_ph.hip; tables and work list: host_ph.hpp) ----
+struct PhUnit;
+// what the kernels read of a phonon sector: dimph blocks of dim_el elements (interleaved complex when cplx); the Gram
+// kernel's element of (sorted row r, sorted column j) is rorder[r] * dim_cols + corder[j]
+struct PhTables {
+  int cplx = 0, dimph = 0, nunits = 0, ncls = 0;
+  int64_t dim_el = 0, dim_cols = 0;
+  const double* sq = nullptr;  // ph_sqrt_table: dimph + 1 entries
+  const int32_t *rorder = nullptr, *corder = nullptr, *ubeg = nullptr;
+  const PhUnit* units = nullptr;
+};
+// dst(i_el, n) = sq[n+1] src(i_el, n+1) + sq[n] src(i_el, n-1); enqueued on st, no synchronisation; dst must not overlap src
+int launch_apply_xph(const PhTables& t, const double* src, double* dst, hipStream_t st);
+// sums[ncls][ph_slots(dimph) (* 2)] of one vector; partial: nunits * ph_slots(dimph) (* 2) doubles
+int launch_ph_rdm(const PhTables& t, const double* v, double* partial, double* sums, hipStream_t st);
+
 // ---- impurity reduced density matrix (kernels_rdm.hip; tables and work list: host_rdm.hpp) ----
 struct RdmArgs {  // the device copies of an RdmPlan
   int cw = 1, stride = 0, ld_max = 0, ept_max = 0, rel_max = 0;

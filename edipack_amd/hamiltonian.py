@@ -171,10 +171,11 @@ def _csr_args(rowptr, col, val, cplx=False):
 class SectorHamiltonian:
     """One sector Hamiltonian resident on the GPU (an ``edigpu_handle``)."""
 
-    def __init__(self, handle: C.c_void_p, owned: bool = True, norb: int = 0):
+    def __init__(self, handle: C.c_void_p, owned: bool = True, norb: int = 0, nph: int = 0):
         self._h = handle
         self._owned = owned        # False: the handle belongs to a SectorCache
         self.norb = int(norb)      # of the model the sector was built from (0: hand-over arrays)
+        self.nph = int(nph)        # of that model: vectors hold nph + 1 electronic blocks
         info = (C.c_int64 * 10)()
         capi.check(capi.lib().edigpu_info(self._h, info), "edigpu_info")
         (self.dim, self.nloc, self.row_first, cplx, self.kind, self.dim_up, self.dim_dw,
@@ -190,7 +191,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_normal_build(C.byref(h), C.byref(cm), nup, ndw, dw_first, dw_count),
                    "edigpu_normal_build")
-        return cls(h, norb=model.norb)
+        return cls(h, norb=model.norb, nph=model.nph)
 
     @classmethod
     def normal_cmplx_from_model(cls, model: ImpurityModel, nup: int, ndw: int) -> "SectorHamiltonian":
@@ -199,7 +200,7 @@ class SectorHamiltonian:
         h = C.c_void_p()
         cm = model.to_c()
         capi.check(capi.lib().edigpu_normal_build_z(C.byref(h), C.byref(cm), nup, ndw), "edigpu_normal_build_z")
-        return cls(h, norb=model.norb)
+        return cls(h, norb=model.norb, nph=model.nph)
 
     @classmethod
     def flat_from_model(cls, model: ImpurityModel, sector: int, row_first: int = 0,
@@ -208,7 +209,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_flat_build(C.byref(h), C.byref(cm), sector, row_first, row_count),
                    "edigpu_flat_build")
-        return cls(h, norb=model.norb)
+        return cls(h, norb=model.norb, nph=model.nph)
 
     @classmethod
     def flat_jz_from_model(cls, model: ImpurityModel, ntot: int, twojz: int, row_first: int = 0,
@@ -218,7 +219,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_flat_build_jz(C.byref(h), C.byref(cm), ntot, twojz, row_first, row_count),
                    "edigpu_flat_build_jz")
-        return cls(h, norb=model.norb)
+        return cls(h, norb=model.norb, nph=model.nph)
 
     @classmethod
     def direct_jz_from_model(cls, model: ImpurityModel, ntot: int, twojz: int, row_first: int = 0,
@@ -228,7 +229,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_direct_build_jz(C.byref(h), C.byref(cm), ntot, twojz, row_first, row_count),
                    "edigpu_direct_build_jz")
-        return cls(h, norb=model.norb)
+        return cls(h, norb=model.norb, nph=model.nph)
 
     @classmethod
     def direct_from_model(cls, model: ImpurityModel, sector: int, row_first: int = 0,
@@ -238,7 +239,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_direct_build(C.byref(h), C.byref(cm), sector, row_first, row_count),
                    "edigpu_direct_build")
-        return cls(h, norb=model.norb)
+        return cls(h, norb=model.norb, nph=model.nph)
 
     @classmethod
     def orbs_from_model(cls, model: ImpurityModel, nups, ndws, row_first: int = 0,
@@ -254,7 +255,7 @@ class SectorHamiltonian:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_orbs_build_rows(C.byref(h), C.byref(cm), capi.pi32(a), capi.pi32(b), row_first,
                                                      row_count), "edigpu_orbs_build")
-        return cls(h, norb=model.norb)
+        return cls(h, norb=model.norb, nph=model.nph)
 
     @classmethod
     def orbs_from_arrays(cls, dims, hd, factors) -> "SectorHamiltonian":
@@ -542,6 +543,31 @@ class SectorHamiltonian:
         capi.check(capi.lib().edigpu_time_rdm_flat(self._h, v_ptr, warmup, steps, C.byref(ms)), "edigpu_time_rdm_flat")
         return float(ms.value)
 
+    # ---- phonon displacement seed and phonon density matrix (edigpu_apply_xph, edigpu_ph_rdm) ---
+    def apply_xph(self, v_src_ptr: int, v_dst_ptr: int, stream: int = 0) -> None:
+        """|dst> = (b + b^dagger) |src> on device vectors of this phonon sector, the seed of the phonon Green's function
+        (lanc_build_gf_phonon_main); dst must not overlap src; enqueued on `stream`, no synchronisation."""
+        capi.check(capi.lib().edigpu_apply_xph(self._h, v_src_ptr, v_dst_ptr, stream if stream else None),
+                   "edigpu_apply_xph")
+
+    def ph_rdm(self, v_ptr: int, nvec: int = 1):
+        """(rho[nvec, 3^norb, DimPh, DimPh], norm2[nvec]) of nvec consecutive device vectors: the phonon reduced density
+        matrix per impurity occupation class, rho[k, c, n, m] = sum_{i_el in c} v_k(i_el, n) conj v_k(i_el, m), not
+        normalised; float64, or complex128 on a complex handle (edipack_amd.observables.from_ph_rdm / phonon_pdf read it)."""
+        ncls, dimph = 3 ** (self.norb or capi.MAXORB), self.nph + 1   # unserved handles are refused by the library
+        rho = np.zeros((nvec, ncls, dimph, dimph), dtype=np.complex128 if self.is_complex else np.float64)
+        nrm = np.zeros(nvec)
+        capi.check(capi.lib().edigpu_ph_rdm(self._h, v_ptr, nvec, rho.ctypes.data_as(C.POINTER(C.c_double)), capi.pd(nrm)),
+                   "edigpu_ph_rdm")
+        return rho, nrm
+
+    def time_ph(self, v_ptr: int, w_ptr: int, warmup: int, steps: int):
+        """(ms of the ph_rdm kernels on the vector at v_ptr, ms of apply_xph from v_ptr into w_ptr): medians over `steps`
+        runs, HIP events; the vector at w_ptr is overwritten."""
+        ms = (C.c_double * 2)()
+        capi.check(capi.lib().edigpu_time_ph(self._h, v_ptr, w_ptr, warmup, steps, ms), "edigpu_time_ph")
+        return float(ms[0]), float(ms[1])
+
     def lanczos_eigh(self, nitermax: int = 512, tol: float = 1e-12, check_every: int = 10,
                      v0: np.ndarray | None = None, want_vector: bool = True):
         """sp_lanc_eigh semantics (lowest eigenpair)."""
@@ -687,7 +713,7 @@ class SectorCache:
         cm = model.to_c()
         capi.check(capi.lib().edigpu_cache_get(self._c, C.byref(cm), self.KINDS[kind], q1, q2, C.byref(h)),
                    "edigpu_cache_get")
-        return SectorHamiltonian(h, owned=False, norb=model.norb)
+        return SectorHamiltonian(h, owned=False, norb=model.norb, nph=model.nph)
 
     def stats(self) -> dict:
         a = (C.c_int64 * 5)()

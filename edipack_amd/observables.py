@@ -21,7 +21,13 @@ entanglement_entropy its spectrum.  ``SectorHamiltonian.imp_rdm_flat`` (edigpu_i
 nonsu2 vectors (imp_rdm_superc, imp_rdm_nonsu2) in the basis |Iup Idw>; its blocks couple different (N_up, N_dw), and
 rdm_anomalous / rdm_magx read the anomalous amplitudes and the transverse magnetisation off it.
 
-Pure numpy: O(norb^2) numbers per vector (16^norb for the density matrix) reach the host."""
+``SectorHamiltonian.ph_rdm`` (edigpu_ph_rdm) gives the phonon side: rho[c, n, m] = sum over the electronic states of
+impurity occupation class c of v(i_el, n) conj v(i_el, m).  from_ph_rdm reads prob_ph, dens_ph, X_ph, X2_ph off it
+(ED_OBSERVABLES_NORMAL.f90:184-199), phonon_pdf the displacement distribution of prob_distr_ph (:1235-1298), and
+phonon_gf turns the tridiagonalisation seeded with ``apply_xph`` into D(z) (ED_GF_NORMAL.f90:434-483, 616-690).
+
+Pure numpy: O(norb^2) numbers per vector (16^norb for the density matrix, 3^norb DimPh^2 for the phonon one) reach the
+host."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -140,3 +146,92 @@ def entanglement_entropy(rho) -> float:
     p = np.linalg.eigvalsh(np.asarray(rho))
     p = p[p > 1e-300]
     return float(-np.sum(p * np.log(p)))
+
+
+@dataclass
+class PhononObservables:
+    prob_ph: np.ndarray     # [DimPh] probability of n phonons
+    dens_ph: float          # <b+ b>
+    x_ph: float             # <X>, X = (b + b+) / sqrt(2)
+    x2_ph: float            # <X^2>
+    prob_class: np.ndarray  # [3^norb] weight of the impurity occupation class c = sum_a nt_a 3^a
+
+
+def _ph_rdm_average(rho, norm2, who: str) -> np.ndarray:
+    """rho[C, D, D] of one state or the average of rho[k, C, D, D] over a manifold, each divided by its norm2 (None: the
+    vectors were normalised), as from_moments forms it"""
+    rho = np.asarray(rho)
+    if rho.ndim not in (3, 4) or rho.shape[-1] != rho.shape[-2]:
+        raise ValueError(f"{who}: expected rho[..., classes, DimPh, DimPh], got {rho.shape}")
+    if norm2 is not None:
+        rho = rho / np.asarray(norm2, dtype=np.float64).reshape(rho.shape[:-3] + (1, 1, 1))
+    return rho.mean(axis=0) if rho.ndim == 4 else rho
+
+
+def from_ph_rdm(rho, norm2=None) -> PhononObservables:
+    """prob_ph, dens_ph, X_ph, X2_ph of ED_OBSERVABLES_NORMAL.f90:184-199 from the phonon density matrix of ph_rdm,
+    rho[C, D, D] or a manifold rho[k, C, D, D] with norm2 as ph_rdm returns it.  On R = sum_c rho[c]:
+    prob_ph[n] = R_nn, dens_ph = sum n R_nn, X_ph = sqrt(2) sum_n sqrt(n+1) Re R[n, n+1],
+    X2_ph = 1/2 sum (2n+1) R_nn + sum_n sqrt((n+1)(n+2)) Re R[n, n+2]   (v conj v throughout)."""
+    rho = _ph_rdm_average(rho, norm2, "from_ph_rdm")
+    R = rho.sum(axis=0)
+    d = R.shape[0]
+    n = np.arange(d, dtype=np.float64)
+    p = np.real(np.diag(R)).copy()
+    x = np.sqrt(2.0) * float(np.sum(np.sqrt(n[:-1] + 1.0) * np.real(np.diag(R, 1))))
+    x2 = 0.5 * float(np.sum((2.0 * n + 1.0) * p))
+    if d > 2:
+        x2 += float(np.sum(np.sqrt((n[:-2] + 1.0) * (n[:-2] + 2.0)) * np.real(np.diag(R, 2))))
+    return PhononObservables(prob_ph=p, dens_ph=float(np.sum(n * p)), x_ph=x, x2_ph=x2,
+                             prob_class=np.real(np.trace(rho, axis1=1, axis2=2)).copy())
+
+
+def hermite_functions(x, dimph: int) -> np.ndarray:
+    """psi[i, n], n = 0 .. dimph - 1: the harmonic-oscillator eigenfunctions at the positions x[i], by the recurrence and
+    with the constant of Hermite (ED_OBSERVABLES_NORMAL.f90:1282-1298)."""
+    x = np.atleast_1d(np.asarray(x, dtype=np.float64))
+    den = 1.331335373062335   # pi^(1/4)
+    psi = np.zeros((x.size, int(dimph)))
+    psi[:, 0] = np.exp(-0.5 * x * x) / den
+    if dimph > 1:
+        psi[:, 1] = np.exp(-0.5 * x * x) * np.sqrt(2.0) * x / den
+    for i in range(2, int(dimph)):
+        psi[:, i] = 2 * x * psi[:, i - 1] / np.sqrt(float(2 * i)) - psi[:, i - 2] * np.sqrt(float(i - 1) / float(i))
+    return psi
+
+
+def phonon_pdf(rho, xmin: float, xmax: float, lpos: int, norm2=None):
+    """(x[lpos], pdf_ph[lpos], pdf_part[lpos, 3^norb]) of prob_distr_ph (ED_OBSERVABLES_NORMAL.f90:1235-1280) on its grid
+    x_i = xmin + i (xmax - xmin) / lpos: pdf_part[i, c] = sum_nm psi_n(x_i) psi_m(x_i) rho[c, n, m], pdf_ph = sum_c."""
+    rho = _ph_rdm_average(rho, norm2, "phonon_pdf")
+    x = xmin + np.arange(int(lpos)) * ((xmax - xmin) / float(lpos))
+    psi = hermite_functions(x, rho.shape[-1])
+    part = np.real(np.einsum("in,cnm,im->ic", psi, rho, psi))
+    return x, part.sum(axis=1), part
+
+
+def phonon_gf(alanc, blanc, norm2: float, e_state: float, z, zeta: float = 1.0, beta: float | None = None) -> np.ndarray:
+    """D(z) of one state from the tridiagonalisation seeded with (b + b+)|state> (apply_xph, lanczos_tridiag_dev).
+    add_to_lanczos_phonon (ED_GF_NORMAL.f90:434-483): poles dE_j = E_j - e_state, weights norm2 Z(1,j)^2 / zeta of the
+    tridiagonal matrix's eigenpairs.  get_impD_normal (ED_GF_NORMAL.f90:616-690) sums them in the bosonic form: only the
+    poles dE > 0 count, each with its mirror image,
+        D(z) = sum_j w_j (1 - exp(-beta dE_j)) (1 / (z - dE_j) - 1 / (z + dE_j)),
+    which on the Matsubara axis is the reference's -w (1 - exp(-beta dE)) 2 dE / (nu^2 + dE^2) (:676-677); a pole with
+    |beta dE| < 1e-8 adds -w beta at z = 0 only (:655-661).  beta = None is zero temperature: the factor is 1 and a
+    zero-energy pole adds nothing."""
+    a = np.asarray(alanc, dtype=np.float64)
+    b = np.asarray(blanc, dtype=np.float64)
+    t = np.diag(a) + np.diag(b[1:], 1) + np.diag(b[1:], -1)
+    e, zv = np.linalg.eigh(t)
+    w = float(norm2) * zv[0, :] ** 2 / float(zeta)
+    de = e - float(e_state)
+    z = np.atleast_1d(np.asarray(z, dtype=np.complex128))
+    out = np.zeros(z.shape, dtype=np.complex128)
+    for wj, dj in zip(w, de):
+        if abs(dj) < (1e-8 / beta if beta is not None else 1e-10):
+            if beta is not None:
+                out[np.abs(z) < 1e-10] -= wj * beta
+        elif dj > 0:
+            f = 1.0 if beta is None else 1.0 - np.exp(-beta * dj)
+            out += wj * f * (1.0 / (z - dj) - 1.0 / (z + dj))
+    return out

@@ -516,6 +516,47 @@ int edigpu_imp_rdm_flat(edigpu_handle h, const double *v_dev, int nvec, double *
 int edigpu_time_rdm_flat(edigpu_handle h, const double *v_dev, int warmup, int steps, double *ms);
 
 /*
+ * Phonon operators on device vectors of ONE phonon sector.  A vector is DimPh = nph + 1 blocks of dim_el electronic
+ * elements, i = i_el + n dim_el, n = 0 .. nph (real doubles in normal mode, interleaved complex for superc / nonsu2).
+ *
+ * edigpu_apply_xph: v_dst(i_el, n) = sqrt(n+1) v_src(i_el, n+1) + sqrt(n) v_src(i_el, n-1), terms outside 0 .. nph absent --
+ * (b + b^dagger)|v>, the seed of the phonon Green's function D(z) (lanc_build_gf_phonon_main, ED_NORMAL/ED_GF_NORMAL.f90:
+ * 278-345, and the same loops of ED_GF_SUPERC.f90:395-415, ED_GF_NONSU2.f90:335-352); edigpu_lanczos_tridiag_dev takes it
+ * from there.  Enqueued on `stream` without synchronising (only the first phonon call on a handle builds and uploads
+ * tables, synchronously).  v_dst_dev must not overlap v_src_dev: an overlap is refused.  The square roots are a host
+ * table of std::sqrt; an output is two products and one sum, not contracted, one product in the two edge blocks: the
+ * result is bit-equal to the same expression in IEEE double arithmetic.  Any DimPh >= 2.
+ *
+ * edigpu_ph_rdm: the phonon reduced density matrix resolved by the impurity occupation class, for nvec consecutive device
+ * vectors (they must be complete when the call is made)
+ *   rho[k][c][n][m] = sum over i_el with class(i_el) == c of v_k(i_el, n) conj v_k(i_el, m),   norm2[k] = <v_k|v_k>
+ *   class(i_el) = sum_a nt_a(i_el) 3^a,  nt_a = n_{a,up} + n_{a,dw},  c = 0 .. 3^norb - 1
+ * class is val - 1 of ED_OBSERVABLES_NORMAL.f90:202-213; the occupation bits are those of edigpu_occ_moments.  prob_ph,
+ * dens_ph, X_ph, X2_ph and pdf_ph / pdf_part of prob_distr_ph (ED_OBSERVABLES_NORMAL.f90:182-214, 1235-1298) are linear in
+ * rho (edipack_amd/observables.py).  The reference's normal / nonsu2 loops write v(i) v(j) without conjg for X_ph and
+ * X2_ph, its superc loop takes real(v conjg v); here it is always v conj v.
+ * rho_host: [nvec][3^norb][DimPh][DimPh] row-major, doubles for real handles, interleaved (re, im) for complex ones, NOT
+ * divided by norm2; one triangle is computed and mirrored (conjugated), so every class block is exactly Hermitian.
+ * norm2_host (nvec doubles) may be NULL; it is the sum of the diagonals over all classes.  The sums are made in a fixed
+ * order without floating-point atomics: two calls on the same input return the same bits, and nvec vectors equal nvec
+ * single calls bit for bit.  Runs on the handle's private stream and returns after synchronising; the first call builds
+ * and uploads the handle's tables (freed by edigpu_destroy), later calls upload nothing.  v_dev may be 8-byte aligned
+ * only and is left untouched.  DimPh <= 32 ("DimPh = .. exceeds the limit of 32" past that).
+ *
+ * Handles: whole sectors from edigpu_normal_build, edigpu_flat_build and edigpu_direct_build with nph > 0, any g_ph.
+ * (edigpu_normal_build_z and the _jz builders do not build phonon sectors.)  Refused, each with a message that starts
+ * with the entry point's name: handles with nph = 0 ("the handle has no phonons"), and, with the messages of
+ * edigpu_occ_moments, ed_total_ud=F handles, hand-over handles and shards.
+ */
+int edigpu_apply_xph(edigpu_handle h, const double *v_src_dev, double *v_dst_dev, void *stream);
+int edigpu_ph_rdm(edigpu_handle h, const double *v_dev, int nvec, double *rho_host, double *norm2_host);
+/* Measurement helper for scripts/time_phonons.py: `warmup` untimed and `steps` timed runs on the handle's stream, each
+ * between two HIP events, of the device work of edigpu_ph_rdm on the vector v_dev (all kernels, without the copy of the
+ * result; ms2[0]) and of edigpu_apply_xph from v_dev into w_dev (ms2[1]); medians in milliseconds.  w_dev is overwritten
+ * and must not overlap v_dev; the limits and refusals of edigpu_ph_rdm apply. */
+int edigpu_time_ph(edigpu_handle h, const double *v_dev, double *w_dev, int warmup, int steps, double *ms2);
+
+/*
  * Lowest eigenpair by plain Lanczos (lanc_method="lanczos": sp_lanc_eigh call
  * sites ED_NORMAL/ED_DIAG_NORMAL.f90:206-214): iterate until the lowest Ritz value
  * moves by less than tol (checked every `check_every` steps) or nitermax, then
