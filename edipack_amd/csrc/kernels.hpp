@@ -259,6 +259,21 @@ int launch_apply_xph(const PhTables& t, const double* src, double* dst, hipStrea
 // sums[ncls][ph_slots(dimph) (* 2)] of one vector; partial: nunits * ph_slots(dimph) (* 2) doubles
 int launch_ph_rdm(const PhTables& t, const double* v, double* partial, double* sums, hipStream_t st);
 
+// ---- fused two-operator products on normal-mode vectors (kernels_pairs.hip; tables: host_pairs.hpp) ----
+// the device copies of a PairsTables: pu[nterms][du_dst], pd[nterms][dd_dst]; a vector is nblk (phonon) blocks of dd rows
+// of du elements; bit t of id_up / id_dw: term t leaves that species alone and its table is not read
+struct PairsArgs {
+  int nterms = 0, nblk = 1;
+  uint32_t id_up = 0, id_dw = 0;
+  int64_t du_src = 0, dd_src = 0, du_dst = 0, dd_dst = 0;
+  double coef[8] = {0};
+  const uint32_t* pu = nullptr;
+  const uint32_t* pd = nullptr;
+};
+// dst[p][jdw][jup] = sum_t coef_t s_t src[p][pd_t(jdw)][pu_t(jup)], acc = 0 then acc = fma(coef_t, +-x_t, acc) for t
+// ascending; every element of dst is written once; enqueued on st, no synchronisation; dst must not overlap src
+int launch_apply_pairs(const PairsArgs& a, const double* src, double* dst, hipStream_t st);
+
 // ---- impurity reduced density matrix (kernels_rdm.hip; tables and work list: host_rdm.hpp) ----
 struct RdmArgs {  // the device copies of an RdmPlan
   int cw = 1, stride = 0, ld_max = 0, ept_max = 0, rel_max = 0;

@@ -161,6 +161,28 @@ def sector_map_jz(model: "ImpurityModel", ntot: int, twojz: int) -> np.ndarray:
     return out
 
 
+def _pairs_args(terms, with_coef: bool = True):
+    """ctypes arrays of a list of (coef, (create, iorb, ispin), (create, iorb, ispin)), the first operator acting first;
+    create truthy = c^+ (passed as +1 / -1, the reference's Os)."""
+    terms = list(terms)
+    n = len(terms)
+    i32 = C.c_int32 * max(n, 1)
+    cols = [i32(*[(1 if t[k][0] else -1) if f == 0 else int(t[k][f]) for t in terms]) for k in (1, 2) for f in (0, 1, 2)]
+    coef = (C.c_double * max(n, 1))(*[float(t[0]) for t in terms])
+    return (n, coef, *cols) if with_coef else (n, *cols)
+
+
+def pairs_sector(model: "ImpurityModel", nup: int, ndw: int, terms):
+    """(nup', ndw', exists) of the sector the two-operator terms (as SectorHamiltonian.apply_pairs_to takes them) lead to
+    from (nup, ndw); exists = False when a particle number leaves [0, Ns] on the way (getCsector / getCDGsector = 0).
+    Host only."""
+    cm = model.to_c()
+    a, b, e = C.c_int(0), C.c_int(0), C.c_int(0)
+    capi.check(capi.lib().edigpu_pairs_sector(C.byref(cm), nup, ndw, *_pairs_args(terms, with_coef=False), C.byref(a),
+                                              C.byref(b), C.byref(e)), "edigpu_pairs_sector")
+    return a.value, b.value, bool(e.value)
+
+
 def _csr_args(rowptr, col, val, cplx=False):
     rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
     col = np.ascontiguousarray(col, dtype=np.int32)
@@ -469,6 +491,22 @@ class SectorHamiltonian:
         fn = capi.lib().edigpu_apply_op_normal if self.kind == 0 else capi.lib().edigpu_apply_op_flat
         capi.check(fn(self._h, dst._h, v_src_ptr, v_dst_ptr, iorb, ispin, int(create),
                       stream if stream else None), "edigpu_apply_op")
+
+    # ---- products of two c / c^+ in one pass (edigpu_apply_pairs_normal) ------------------------
+    def apply_pairs_to(self, dst: "SectorHamiltonian", v_src_ptr: int, v_dst_ptr: int, terms, stream: int = 0) -> None:
+        """|dst> = sum_t coef_t O2_t O1_t |src> on device vectors (self = source sector; dst may be self, the vectors must
+        not overlap): the seeds of the pair and exciton susceptibilities.  terms: up to 8 of (coef, (create, iorb, ispin),
+        (create, iorb, ispin)), the first operator acting first (edipack_amd.observables.pair_chi_seeds / exct_chi_seeds
+        write them).  Returns after `stream` has finished."""
+        capi.check(capi.lib().edigpu_apply_pairs_normal(self._h, dst._h, v_src_ptr, v_dst_ptr, *_pairs_args(terms),
+                                                        stream if stream else None), "edigpu_apply_pairs_normal")
+
+    def time_pairs(self, dst: "SectorHamiltonian", v_src_ptr: int, v_dst_ptr: int, terms, warmup: int, steps: int):
+        """(ms of a whole apply_pairs_to call, ms of its kernel alone): medians over `steps` runs, HIP events."""
+        ms = (C.c_double * 2)()
+        capi.check(capi.lib().edigpu_time_pairs(self._h, dst._h, v_src_ptr, v_dst_ptr, *_pairs_args(terms), warmup, steps, ms),
+                   "edigpu_time_pairs")
+        return float(ms[0]), float(ms[1])
 
     # ---- operators diagonal in the occupation basis (edigpu_apply_occ, edigpu_occ_moments) -----
     def apply_occ(self, v_src_ptr: int, v_dst_ptr: int, w_up, w_dw, stream: int = 0) -> None:

@@ -26,6 +26,11 @@ impurity occupation class c of v(i_el, n) conj v(i_el, m).  from_ph_rdm reads pr
 (ED_OBSERVABLES_NORMAL.f90:184-199), phonon_pdf the displacement distribution of prob_distr_ph (:1235-1298), and
 phonon_gf turns the tridiagonalisation seeded with ``apply_xph`` into D(z) (ED_GF_NORMAL.f90:434-483, 616-690).
 
+``SectorHamiltonian.apply_pairs_to`` (edigpu_apply_pairs_normal) makes the seeds of the pair and exciton susceptibilities
+in one pass; pair_chi_seeds / exct_chi_seeds write their operator products as the reference's loops do
+(ED_NORMAL/ED_CHI_PAIR.f90, ED_CHI_EXCT.f90) and chi_channel turns a seed's tridiagonalisation into its channel's share of
+chi(z).
+
 Pure numpy: O(norb^2) numbers per vector (16^norb for the density matrix, 3^norb DimPh^2 for the phonon one) reach the
 host."""
 from __future__ import annotations
@@ -235,3 +240,85 @@ def phonon_gf(alanc, blanc, norm2: float, e_state: float, z, zeta: float = 1.0, 
             f = 1.0 if beta is None else 1.0 - np.exp(-beta * dj)
             out += wj * f * (1.0 / (z - dj) - 1.0 / (z + dj))
     return out
+
+
+# ---- pair and exciton susceptibilities (ED_NORMAL/ED_CHI_PAIR.f90, ED_CHI_EXCT.f90; real build) ----------------------
+# A term is (coef, O1, O2), O1 acting first, O = (create, iorb, ispin): create 1 = c^+, 0 = c; iorb 0-based; ispin 0 = up,
+# 1 = down -- what SectorHamiltonian.apply_pairs_to takes.  A channel is (terms, isign), channels in the reference's order
+# (ichan = 1, 2, ...: odd = lesser, even = greater).  A term whose sector does not exist (hamiltonian.pairs_sector) is to
+# be left out of the call, and a channel left with no term skipped, as the reference does when getCsector /
+# getCDGsector return 0.
+_UP, _DW = 0, 1
+
+
+def pair_chi_seeds(iorb: int, jorb: int):
+    """The two channels of chi_pair(iorb, jorb): lanc_ed_build_pairChi_diag for jorb == iorb (ED_CHI_PAIR.f90:129-153),
+    lanc_ed_build_pairChi_mix otherwise (:204-241; the channels 3, 4 of the _CMPLX_NORMAL build are not wanted)."""
+    orbs = (iorb,) if iorb == jorb else (iorb, jorb)
+    lesser = [(1.0, (0, a, _DW), (0, a, _UP)) for a in orbs]     # C_a,dw|gs> = |tmp>, C_a,up|tmp>; va + vb
+    greater = [(1.0, (1, a, _UP), (1, a, _DW)) for a in orbs]    # C^+_a,up|gs> = |tmp>, C^+_a,dw|tmp>; va + vb
+    return [(lesser, +1), (greater, -1)]
+
+
+def exct_chi_seeds(indx: int, iorb: int, jorb: int):
+    """The channels of chi_exct(indx, iorb, jorb), indx as the reference counts it: 1 singlet, 2 triplet-XY, 3 triplet-Z.
+    Singlet and triplet-Z (auxiliary_vvinit_manipulation, ED_CHI_EXCT.f90:513-592): two channels, vup + comb_sign vdw
+    with the orbitals swapped in the greater one; triplet-XY (:178-235): four channels of one term each."""
+    if indx == 2:
+        return [([(1.0, (0, jorb, _UP), (1, iorb, _DW))], +1),   # C_b,up|gs>, C^+_a,dw|tmp>: first lesser
+                ([(1.0, (0, iorb, _DW), (1, jorb, _UP))], -1),   # C_a,dw|gs>, C^+_b,up|tmp>: first greater
+                ([(1.0, (0, jorb, _DW), (1, iorb, _UP))], +1),   # C_b,dw|gs>, C^+_a,up|tmp>: second lesser
+                ([(1.0, (0, iorb, _UP), (1, jorb, _DW))], -1)]   # C_a,up|gs>, C^+_b,dw|tmp>: second greater
+    if indx not in (1, 3):
+        raise ValueError("exct_chi_seeds: indx is 1 (singlet), 2 (triplet-XY) or 3 (triplet-Z)")
+    comb_sign = 1.0 if indx == 1 else -1.0
+    out = []
+    for a, b, isign in ((iorb, jorb, +1), (jorb, iorb, -1)):
+        out.append(([(1.0, (0, b, _UP), (1, a, _UP)),            # vup  = C^+_a,up C_b,up|gs>
+                     (comb_sign, (0, b, _DW), (1, a, _DW))],     # vdw  = C^+_a,dw C_b,dw|gs>
+                    isign))
+    return out
+
+
+def chi_channel(alanc, blanc, norm2: float, e_state: float, isign: int, ichan: int, z, beta: float | None,
+                zeta: float = 1.0, mirror: bool = False, axis: str = "m"):
+    """The share of one channel of one state in chi(z), from the tridiagonalisation of the channel's seed
+    (apply_pairs_to, lanczos_tridiag_dev).  add_to_lanczos_pairChi / add_to_lanczos_exctChi (ED_CHI_PAIR.f90:302-368):
+    weights peso_j = norm2 Z(1,j)^2 / zeta, poles de_j = isign (E_j - e_state) of the tridiagonal matrix's eigenpairs (a
+    state's Boltzmann factor is the caller's).  get_Chiab (ED_CHI_PAIR.f90:431-508) sums them: a pole with
+    |beta de| < 1e-8 adds 0.5 peso beta at z = 0 only (axis "r": at Re z = 0); otherwise only the poles with
+    merge(de, -de, mod(ichan, 2) == 1) > 0 count,
+        lesser  (ichan odd):   - peso (1 - exp(-beta de)) / (z - de)
+        greater (ichan even):  + peso (1 - exp(+beta de)) / (z - de).
+    ichan counts from 1.  mirror=True returns (chi, chi_mirror), chi_mirror the share in chi(jorb, iorb) of
+    ED_CHI_EXCT.f90:475-485: the same with (z - de) -> (z + de) and the opposite sign, the zero pole unchanged.
+    beta = None is zero temperature: the thermal factors are 1 and a zero-energy pole (|de| < 1e-10) adds nothing.
+    The imaginary-time axis is not served."""
+    if axis not in ("m", "r"):
+        raise ValueError("chi_channel: axis is 'm' or 'r'")
+    a = np.asarray(alanc, dtype=np.float64)
+    b = np.asarray(blanc, dtype=np.float64)
+    t = np.diag(a) + np.diag(b[1:], 1) + np.diag(b[1:], -1)
+    e, zv = np.linalg.eigh(t)
+    w = float(norm2) * zv[0, :] ** 2 / float(zeta)
+    de = int(isign) * (e - float(e_state))
+    z = np.atleast_1d(np.asarray(z, dtype=np.complex128))
+    at_zero = (np.abs(z) if axis == "m" else np.abs(z.real)) < 1e-10
+    lesser = int(ichan) % 2 == 1
+    out = np.zeros(z.shape, dtype=np.complex128)
+    mir = np.zeros(z.shape, dtype=np.complex128)
+    for wj, dj in zip(w, de):
+        if (abs(beta * dj) < 1e-8) if beta is not None else (abs(dj) < 1e-10):
+            if beta is not None:
+                out[at_zero] += 0.5 * wj * beta
+                mir[at_zero] += 0.5 * wj * beta
+        elif (dj if lesser else -dj) > 0:
+            if lesser:
+                f = wj * (1.0 if beta is None else 1.0 - np.exp(-beta * dj))
+                out -= f / (z - dj)
+                mir += f / (z + dj)
+            else:
+                f = wj * (1.0 if beta is None else 1.0 - np.exp(beta * dj))
+                out += f / (z - dj)
+                mir -= f / (z + dj)
+    return (out, mir) if mirror else out

@@ -268,6 +268,15 @@ module EDIGPU_SHIM
        integer(c_int32_t), intent(in) :: create(*), iorb(*), ispin(*)
        integer(c_int) :: ierr
      end function edigpu_apply_cops_normal
+     function edigpu_apply_pairs_normal(src, dst, v_src_dev, v_dst_dev, nterms, coef, create1, iorb1, ispin1, &
+          create2, iorb2, ispin2, stream) bind(C, name="edigpu_apply_pairs_normal") result(ierr)
+       import :: c_ptr, c_int, c_int32_t, c_double
+       type(c_ptr), value :: src, dst, v_src_dev, v_dst_dev, stream
+       integer(c_int), value :: nterms
+       real(c_double), intent(in) :: coef(*)
+       integer(c_int32_t), intent(in) :: create1(*), iorb1(*), ispin1(*), create2(*), iorb2(*), ispin2(*)
+       integer(c_int) :: ierr
+     end function edigpu_apply_pairs_normal
      function edigpu_info(h, info) bind(C, name="edigpu_info") result(ierr)
        import :: c_ptr, c_int, c_int64_t
        type(c_ptr), value :: h
@@ -432,6 +441,7 @@ module EDIGPU_SHIM
   public :: gpu_vec_alloc, gpu_vec_free, gpu_vec_upload_d, gpu_vec_download_d, gpu_vec_upload_c, gpu_vec_download_c
   public :: gpu_sp_lanc_eigh_dev, gpu_apply_op, gpu_apply_cops, gpu_lanc_tridiag_dev
   public :: gpu_apply_op_N, gpu_apply_op_Sz, gpu_occ_moments, gpu_imp_rdm, gpu_imp_rdm_flat
+  public :: gpu_apply_pairs
   ! N > 1: communicator + the MPI twins of the product and of the tridiagonalisation
   public :: gpu_comm_unique_id, gpu_comm_create, gpu_comm_create_shm, gpu_comm_destroy, gpu_shard_plan
   public :: spMatVec_mpi_gpu_d, spMatVec_mpi_gpu_c, gpu_lanc_tridiag_mpi_d, gpu_lanc_tridiag_mpi_c
@@ -940,6 +950,23 @@ contains
     call gpu_check(edigpu_apply_cops_normal(hsrc, hdst, v_src_dev, v_dst_dev, int(size(Os), c_int), coefs, o, io, is, &
          c_null_ptr), "gpu_apply_cops")
   end subroutine gpu_apply_cops
+
+  !> vvinit = sum_i coefs(i) * O2_i O1_i v_state in one pass, O1_i acting first: the two apply_op_C / apply_op_CDG calls
+  !! through an intermediate sector of ED_NORMAL/ED_CHI_PAIR.f90:129-153, 204-241 and ED_CHI_EXCT.f90:178-235, 513-592.
+  !! Os1(i), Os2(i) = +1 for c^+, -1 for c; orbs and spins count from 1 as in the reference.  hdst may be hsrc (singlet /
+  !! triplet-Z exciton seeds); v_dst_dev must not overlap v_src_dev.  Returns after the device has finished.
+  subroutine gpu_apply_pairs(hsrc, hdst, v_src_dev, v_dst_dev, coefs, Os1, orbs1, spins1, Os2, orbs2, spins2)
+    type(c_ptr), intent(in) :: hsrc, hdst, v_src_dev, v_dst_dev
+    real(8), intent(in) :: coefs(:)
+    integer, intent(in) :: Os1(:), orbs1(:), spins1(:), Os2(:), orbs2(:), spins2(:)
+    integer(c_int32_t) :: o1(size(Os1)), io1(size(Os1)), is1(size(Os1)), o2(size(Os1)), io2(size(Os1)), is2(size(Os1))
+    if (size(coefs) /= size(Os1) .or. size(orbs1) /= size(Os1) .or. size(spins1) /= size(Os1) .or. &
+         size(Os2) /= size(Os1) .or. size(orbs2) /= size(Os1) .or. size(spins2) /= size(Os1)) stop "gpu_apply_pairs: shapes"
+    o1 = int(Os1, c_int32_t); io1 = int(orbs1 - 1, c_int32_t); is1 = int(spins1 - 1, c_int32_t)
+    o2 = int(Os2, c_int32_t); io2 = int(orbs2 - 1, c_int32_t); is2 = int(spins2 - 1, c_int32_t)
+    call gpu_check(edigpu_apply_pairs_normal(hsrc, hdst, v_src_dev, v_dst_dev, int(size(Os1), c_int), coefs, o1, io1, is1, &
+         o2, io2, is2, c_null_ptr), "gpu_apply_pairs")
+  end subroutine gpu_apply_pairs
 
   !> tridiag_Hv_sector_*(jsector, vvinit, alfa_, beta_, norm2) with the seed already on the device: the live sector
   !! is the one the seed belongs to; norm2 = <vvinit|vvinit> as the reference returns it

@@ -557,6 +557,51 @@ int edigpu_ph_rdm(edigpu_handle h, const double *v_dev, int nvec, double *rho_ho
 int edigpu_time_ph(edigpu_handle h, const double *v_dev, double *w_dev, int warmup, int steps, double *ms2);
 
 /*
+ * Products of two fermion operators on device vectors of normal-mode sectors, in one pass: the seeds of the pair and
+ * exciton susceptibilities (ED_NORMAL/ED_CHI_PAIR.f90:129-153, 204-241; ED_NORMAL/ED_CHI_EXCT.f90:178-235, 513-592),
+ * which the reference makes by two apply_op_C / apply_op_CDG calls through an intermediate sector.
+ *
+ *   v_dst = sum_t coef[t] * O2_t O1_t v_src,   t = 0 .. nterms - 1,   1 <= nterms <= 8
+ *
+ * O1_t acts first.  Each O is c^+ (create > 0) or c (create <= 0; the reference's Os = +1 / -1) of orbital iorb
+ * (0-based) and spin ispin (0 up, 1 down); its sign counts the electrons of its own spin below its level, as
+ * edigpu_apply_op_normal.  Every term must lead from the source sector to the same destination sector.  An element is
+ * acc = 0, then acc = fma(coef[t], +-v_src(partner_t), acc) for t ascending, terms without a preimage skipped: with
+ * coefficients +-1 and one term the result is exact, and any result is reproducible bit for bit.  Every element of v_dst
+ * is written (zeros included); v_src is only read.
+ *
+ * edigpu_pairs_sector (host only, no GPU needed): the sector (nup_dst, ndw_dst) the terms lead to from (nup, ndw) of a
+ * normal-mode model, and exists = 0 when a particle number leaves [0, Ns] after either operator of some term
+ * (getCsector / getCDGsector returning 0: the reference skips such a channel).  Refused: orbital / spin out of range,
+ * terms that lead to different sectors, nterms outside 1 .. 8.
+ *
+ * edigpu_apply_pairs_normal: src and dst are whole real normal-mode sectors built from a model (edigpu_normal_build) of
+ * the same model; phonon sectors are served (the product acts in every phonon block); src == dst is the usual case of
+ * the singlet / triplet-Z exciton seeds.  The call builds the O(DimUp + DimDw) tables on the host, uploads them,
+ * enqueues one kernel on `stream` and RETURNS AFTER `stream` HAS FINISHED: the tables are per call and are freed only
+ * then (no table stays on the handle).  v_dst_dev must not overlap v_src_dev.  Vectors may be 8-byte aligned only.
+ * Refused, each with a message that starts with the entry point's name: complex handles (edigpu_normal_build_z; "is a
+ * complex normal-mode sector"), superc / nonsu2 handles ("is a superc / nonsu2 sector"), ed_total_ud=F handles ("is an
+ * ed_total_ud=F sector"), hand-over handles ("must be built from a model"), shards ("must hold the whole sector"),
+ * sectors of different models ("sectors of different models"), a destination handle that is not the sector the terms
+ * lead to ("the terms lead to"), a destination that does not exist ("leaves the Fock space"), nterms > 8 ("nterms must
+ * be 1 .. 8"), overlapping vectors ("overlaps").
+ *
+ * edigpu_time_pairs: measurement helper for scripts/time_pairs.py.  `warmup` untimed and `steps` timed runs on the source
+ * handle's stream, each between two HIP events; medians in milliseconds.  ms2[0]: the whole of edigpu_apply_pairs_normal
+ * as a caller pays it (host tables, upload, kernel, wait, free); ms2[1]: the kernel alone on resident tables.
+ */
+int edigpu_pairs_sector(const edigpu_model *model, int nup, int ndw, int nterms, const int32_t *create1, const int32_t *iorb1,
+                        const int32_t *ispin1, const int32_t *create2, const int32_t *iorb2, const int32_t *ispin2,
+                        int *nup_dst, int *ndw_dst, int *exists);
+int edigpu_apply_pairs_normal(edigpu_handle src, edigpu_handle dst, const double *v_src_dev, double *v_dst_dev, int nterms,
+                              const double *coef, const int32_t *create1, const int32_t *iorb1, const int32_t *ispin1,
+                              const int32_t *create2, const int32_t *iorb2, const int32_t *ispin2, void *stream);
+int edigpu_time_pairs(edigpu_handle src, edigpu_handle dst, const double *v_src_dev, double *v_dst_dev, int nterms,
+                      const double *coef, const int32_t *create1, const int32_t *iorb1, const int32_t *ispin1,
+                      const int32_t *create2, const int32_t *iorb2, const int32_t *ispin2, int warmup, int steps, double *ms2);
+
+/*
  * Lowest eigenpair by plain Lanczos (lanc_method="lanczos": sp_lanc_eigh call
  * sites ED_NORMAL/ED_DIAG_NORMAL.f90:206-214): iterate until the lowest Ritz value
  * moves by less than tol (checked every `check_every` steps) or nitermax, then
