@@ -1801,6 +1801,8 @@ int edigpu_orbs_build_rows(edigpu_handle* h, const edigpu_model* model, const in
   }
   s->row_first = row_first;  // the factored tables describe the whole sector; only the rows computed differ
   s->nloc = row_count;
+  s->orbs_nups.assign(nups, nups + model->norb);
+  s->orbs_ndws.assign(ndws, ndws + model->norb);
   *h = s.release();
   return 0;
 }
@@ -2407,8 +2409,13 @@ static int apply_op_flat_term(edigpu_handle src, edigpu_handle dst, const double
     set_error(w + ": both handles must be superc / nonsu2 sectors built by edigpu_flat_build or edigpu_direct_build");
     return 1;
   }
-  if (src->nph > 0 || dst->nph > 0) {
-    set_error(w + ": phonon sectors are not supported");
+  if (src->nph != dst->nph || src->model.nph != dst->model.nph) {
+    set_error(w + ": the two handles have different nph (" + std::to_string(src->nph) + " and " + std::to_string(dst->nph) + ")");
+    return 1;
+  }
+  const int nblk = src->nph + 1;
+  if (nblk > 1 && (src->nloc != src->dim || dst->nloc != dst->dim || fd != 0 || cd >= 0)) {
+    set_error(w + ": phonon sectors are served as whole sectors only (no shards, no row window)");
     return 1;
   }
   const edigpu_model& m = src->model;
@@ -2446,7 +2453,7 @@ static int apply_op_flat_term(edigpu_handle src, edigpu_handle dst, const double
   rc |= dev_upload(&d_rk, hs.rk_up.data(), hs.rk_up.size());
   if (!rc)
     rc = launch_apply_op_flat(cd, ns, 1u << (iorb + ispin * ns), create, d_states + fd, d_off, d_rk, v_src_dev, v_dst_dev, st,
-                              cre, cim, accumulate);
+                              cre, cim, accumulate, nblk, hs.dim);  // phonon sectors: every electronic block, one launch
   (void)hipStreamSynchronize(st);
   dev_free(d_states);
   dev_free(d_off);
@@ -2484,6 +2491,12 @@ int edigpu_apply_op_normal(edigpu_handle src, edigpu_handle dst, const double* v
     set_error("edigpu_apply_op_normal: NULL argument");
     return 1;
   }
+  if (axisop_route(src, dst)) {  // phonon, complex and ed_total_ud=F sectors: kernels_axisop.hip
+    const int32_t cr = create ? 1 : -1, io = iorb, sp = ispin;
+    const double one = 1.0;
+    return axisop_apply(src, dst, v_src_dev, v_dst_dev, 1, &one, nullptr, &cr, &io, &sp, (hipStream_t)stream,
+                        "edigpu_apply_op_normal");
+  }
   return apply_op_normal_term(src, dst, v_src_dev, v_dst_dev, iorb, ispin, create, 1.0, 0, (hipStream_t)stream,
                               "edigpu_apply_op_normal");
 }
@@ -2495,6 +2508,9 @@ int edigpu_apply_cops_normal(edigpu_handle src, edigpu_handle dst, const double*
     set_error("edigpu_apply_cops_normal: bad argument");
     return 1;
   }
+  if (axisop_route(src, dst))  // phonon, complex and ed_total_ud=F sectors: all operators in one pass (kernels_axisop.hip)
+    return axisop_apply(src, dst, v_src_dev, v_dst_dev, nops, coef, nullptr, create, iorb, ispin, (hipStream_t)stream,
+                        "edigpu_apply_cops_normal");
   for (int s = 0; s < nops; s++)
     if (apply_op_normal_term(src, dst, v_src_dev, v_dst_dev, iorb[s], ispin[s], create[s] > 0, coef[s], s > 0,
                              (hipStream_t)stream, "edigpu_apply_cops_normal"))
@@ -3278,6 +3294,7 @@ int edigpu_destroy(edigpu_handle s) {
   free_rdm(s);
   free_rdm_flat(s);
   free_ph(s);
+  free_axisop(s);
   dev_free(s->d_vin);
   dev_free(s->d_vout);
   dev_free(s->d_tmp);

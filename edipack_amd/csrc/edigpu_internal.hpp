@@ -198,6 +198,19 @@ void free_rdm_flat(edigpu_sector* s);
 struct PhDev;
 void free_ph(edigpu_sector* s);
 
+// Scratch buffer of the partner tables of the one-axis c / c^+ route (edigpu_axisop.hip; host_axisop.hpp,
+// kernels_axisop.hip), kept by the DESTINATION handle of a call and grown on demand, until edigpu_destroy.
+struct AxisDev;
+void free_axisop(edigpu_sector* s);
+// true: this pair of handles is not the real, phonon-free, library-built normal-mode pair that apply_op_normal_kernel
+// serves; axisop_apply then makes every check and serves phonon, complex (kind 4) and ed_total_ud=F (kind 3) pairs.
+// cim = null: real coefficients; else complex ones on kind-4 handles (edigpu_apply_cops_normal_z).  Returns after the
+// stream has finished.
+bool axisop_route(const edigpu_sector* src, const edigpu_sector* dst);
+int axisop_apply(edigpu_sector* src, edigpu_sector* dst, const double* v_src, double* v_dst, int nops, const double* cre,
+                 const double* cim, const int32_t* create, const int32_t* iorb, const int32_t* ispin, hipStream_t st,
+                 const char* who);
+
 }  // namespace edigpu
 
 struct edigpu_sector {
@@ -285,6 +298,7 @@ struct edigpu_sector {
   edigpu::OrbsArgs orbs;
   std::vector<edigpu::HostCsr> h_orbs_fac;  // kept for export (tiny)
   std::vector<double> h_orbs_hd;            // explicit diagonal when handed over
+  std::vector<int> orbs_nups, orbs_ndws;    // library-built (edigpu_orbs_build): the sector's labels, Norb entries each
   // ---- direct (on-the-fly) ----
   int dir_ns = 0, dir_norb = 0, dir_nterms = 0;
   int32_t* d_dir_states = nullptr;
@@ -301,6 +315,8 @@ struct edigpu_sector {
   edigpu::RdmFlatDev* rdm_flat = nullptr;
   // ---- phonon displacement seed and phonon density matrix (lazily built) ----
   edigpu::PhDev* ph = nullptr;
+  // ---- c / c^+ along one axis: table scratch of calls with this handle as destination (lazily built) ----
+  edigpu::AxisDev* axis = nullptr;
   // ---- Lanczos workspace (lazily allocated) ----
   int64_t partial_cap = 0;      // doubles in d_partial
   double* d_vin = nullptr;

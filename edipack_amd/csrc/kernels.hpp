@@ -184,7 +184,8 @@ int launch_phonon_rows(const edigpu_sector* s, int64_t dw_first, int64_t dw_coun
                        hipStream_t st);
 int launch_apply_op_flat(int64_t ndst, int ns, uint32_t bit, int create, const int32_t* dst_states,
                          const int32_t* src_offdw, const int32_t* src_rkup, const double* src, double* dst,
-                         hipStream_t st, double cre = 1.0, double cim = 0.0, int accumulate = 0);
+                         hipStream_t st, double cre = 1.0, double cim = 0.0, int accumulate = 0, int nblk = 1,
+                         int64_t nsrc = 0);  // nblk > 1: phonon blocks of ndst (destination) / nsrc (source) elements
 // apply_Cops on a window of destination units (edigpu_capi.hip): v_dst_rows = sum_s coef_s O_s v_src for the
 // destination's down rows (normal mode) / rows (superc, nonsu2) [first, first + count); v_src_full holds the WHOLE source
 // vector in the reference's layout; coef2 = (re, im) per operator (normal mode: real).  Returns after the stream finished.
@@ -273,6 +274,19 @@ struct PairsArgs {
 // dst[p][jdw][jup] = sum_t coef_t s_t src[p][pd_t(jdw)][pu_t(jup)], acc = 0 then acc = fma(coef_t, +-x_t, acc) for t
 // ascending; every element of dst is written once; enqueued on st, no synchronisation; dst must not overlap src
 int launch_apply_pairs(const PairsArgs& a, const double* src, double* dst, hipStream_t st);
+
+// ---- c / c^+ along one axis of a vector [O][A][I] (kernels_axisop.hip; tables: host_axisop.hpp) ----
+// the device copy of an AxisTables (part[nterms][a_dst]) and the coefficients; I in doubles
+struct AxisArgs {
+  int nterms = 0;
+  int64_t I = 0, a_src = 0, a_dst = 0, O = 0;
+  double cre[8] = {0}, cim[8] = {0};
+  const uint32_t* part = nullptr;
+};
+// dst[o][j][i] = sum_t coef_t s_t(j) src[o][part_t(j)][i] in the order stated in kernels_axisop.hip; cplx_coef: elements
+// are double2 and the coefficients complex (I even), else cim is not read; every element of dst is written once; enqueued
+// on st, no synchronisation; dst must not overlap src
+int launch_apply_axisop(const AxisArgs& a, int cplx_coef, const double* src, double* dst, hipStream_t st);
 
 // ---- impurity reduced density matrix (kernels_rdm.hip; tables and work list: host_rdm.hpp) ----
 struct RdmArgs {  // the device copies of an RdmPlan

@@ -409,12 +409,19 @@ class SectorHamiltonian:
     def apply_cops_to(self, dst: "SectorHamiltonian", v_src_ptr: int, v_dst_ptr: int, coefs, creates, iorbs, ispins,
                       stream: int = 0) -> None:
         """apply_Cops on device vectors: |dst> = sum_s coefs[s] * c^(+)_{iorbs[s], ispins[s]} |src> (normal mode;
-        creates[s] truthy = c^+)."""
+        creates[s] truthy = c^+).  On a complex handle (normal_cmplx_from_model) the coefficients may be complex
+        (edigpu_apply_cops_normal_z)."""
         n = len(coefs)
-        a = (C.c_double * n)(*[float(x) for x in coefs])
         o = (C.c_int32 * n)(*[1 if x else -1 for x in creates])
         io = (C.c_int32 * n)(*[int(x) for x in iorbs])
         sp = (C.c_int32 * n)(*[int(x) for x in ispins])
+        if self.is_complex and any(complex(c).imag != 0.0 for c in coefs):
+            z = (C.c_double * (2 * n))(*[x for c in coefs for x in (complex(c).real, complex(c).imag)])
+            capi.check(capi.lib().edigpu_apply_cops_normal_z(self._h, dst._h, v_src_ptr, v_dst_ptr, n, z, o, io, sp,
+                                                             stream if stream else None), "edigpu_apply_cops_normal_z")
+            return
+        # a coefficient with an imaginary part on a real handle is a TypeError, as before
+        a = (C.c_double * n)(*[float(complex(x).real) if complex(x).imag == 0.0 else float(x) for x in coefs])
         capi.check(capi.lib().edigpu_apply_cops_normal(self._h, dst._h, v_src_ptr, v_dst_ptr, n, a, o, io, sp,
                                                        stream if stream else None), "edigpu_apply_cops_normal")
 
@@ -488,9 +495,18 @@ class SectorHamiltonian:
     def apply_op_to(self, dst: "SectorHamiltonian", v_src_ptr: int, v_dst_ptr: int, iorb: int, ispin: int,
                     create: bool, stream: int = 0) -> None:
         """apply_op_C / apply_op_CDG on device vectors: |dst> = c^(+)_{iorb,ispin} |src> (self = source sector)."""
-        fn = capi.lib().edigpu_apply_op_normal if self.kind == 0 else capi.lib().edigpu_apply_op_flat
+        fn = capi.lib().edigpu_apply_op_normal if self.kind in (0, 3, 4) else capi.lib().edigpu_apply_op_flat
         capi.check(fn(self._h, dst._h, v_src_ptr, v_dst_ptr, iorb, ispin, int(create),
                       stream if stream else None), "edigpu_apply_op")
+
+    def time_apply_op(self, dst: "SectorHamiltonian", v_src_ptr: int, v_dst_ptr: int, iorb: int, ispin: int, create: bool,
+                      warmup: int, steps: int):
+        """(ms of a whole apply_op_to call, ms of its kernel alone) between normal-mode handles (kinds 0, 3, 4): medians
+        over `steps` runs, HIP events."""
+        ms = (C.c_double * 2)()
+        capi.check(capi.lib().edigpu_time_apply_op(self._h, dst._h, v_src_ptr, v_dst_ptr, iorb, ispin, int(create), warmup,
+                                                   steps, ms), "edigpu_time_apply_op")
+        return float(ms[0]), float(ms[1])
 
     # ---- products of two c / c^+ in one pass (edigpu_apply_pairs_normal) ------------------------
     def apply_pairs_to(self, dst: "SectorHamiltonian", v_src_ptr: int, v_dst_ptr: int, terms, stream: int = 0) -> None:

@@ -268,6 +268,15 @@ module EDIGPU_SHIM
        integer(c_int32_t), intent(in) :: create(*), iorb(*), ispin(*)
        integer(c_int) :: ierr
      end function edigpu_apply_cops_normal
+     function edigpu_apply_cops_normal_z(src, dst, v_src_dev, v_dst_dev, nops, coef_re_im, create, iorb, ispin, stream) &
+          bind(C, name="edigpu_apply_cops_normal_z") result(ierr)
+       import :: c_ptr, c_int, c_int32_t, c_double
+       type(c_ptr), value :: src, dst, v_src_dev, v_dst_dev, stream
+       integer(c_int), value :: nops
+       real(c_double), intent(in) :: coef_re_im(*)
+       integer(c_int32_t), intent(in) :: create(*), iorb(*), ispin(*)
+       integer(c_int) :: ierr
+     end function edigpu_apply_cops_normal_z
      function edigpu_apply_pairs_normal(src, dst, v_src_dev, v_dst_dev, nterms, coef, create1, iorb1, ispin1, &
           create2, iorb2, ispin2, stream) bind(C, name="edigpu_apply_pairs_normal") result(ierr)
        import :: c_ptr, c_int, c_int32_t, c_double
@@ -442,6 +451,7 @@ module EDIGPU_SHIM
   public :: gpu_sp_lanc_eigh_dev, gpu_apply_op, gpu_apply_cops, gpu_lanc_tridiag_dev
   public :: gpu_apply_op_N, gpu_apply_op_Sz, gpu_occ_moments, gpu_imp_rdm, gpu_imp_rdm_flat
   public :: gpu_apply_pairs
+  public :: gpu_apply_cops_z
   ! N > 1: communicator + the MPI twins of the product and of the tridiagonalisation
   public :: gpu_comm_unique_id, gpu_comm_create, gpu_comm_create_shm, gpu_comm_destroy, gpu_shard_plan
   public :: spMatVec_mpi_gpu_d, spMatVec_mpi_gpu_c, gpu_lanc_tridiag_mpi_d, gpu_lanc_tridiag_mpi_c
@@ -950,6 +960,26 @@ contains
     call gpu_check(edigpu_apply_cops_normal(hsrc, hdst, v_src_dev, v_dst_dev, int(size(Os), c_int), coefs, o, io, is, &
          c_null_ptr), "gpu_apply_cops")
   end subroutine gpu_apply_cops
+
+  !> apply_Cops with complex coefficients on the complex normal-mode sectors of the _CMPLX_NORMAL build: the [one, xi]
+  !! combinations of the off-diagonal Green's function (ED_NORMAL/ED_GF_NORMAL.f90:250-263).  Os(i) = +1 for c^+, -1 for
+  !! c; orbs and spins count from 1; at most 8 operators; v_dst_dev must not overlap v_src_dev.
+  subroutine gpu_apply_cops_z(hsrc, hdst, v_src_dev, v_dst_dev, coefs, Os, orbs, spins)
+    type(c_ptr), intent(in) :: hsrc, hdst, v_src_dev, v_dst_dev
+    complex(8), intent(in) :: coefs(:)
+    integer, intent(in) :: Os(:), orbs(:), spins(:)
+    integer(c_int32_t) :: o(size(Os)), io(size(Os)), is(size(Os))
+    real(c_double) :: ri(2 * size(Os))
+    integer :: k
+    if (size(coefs) /= size(Os) .or. size(orbs) /= size(Os) .or. size(spins) /= size(Os)) stop "gpu_apply_cops_z: shapes"
+    do k = 1, size(Os)
+       ri(2 * k - 1) = real(coefs(k), c_double)
+       ri(2 * k) = aimag(coefs(k))
+    end do
+    o = int(Os, c_int32_t); io = int(orbs - 1, c_int32_t); is = int(spins - 1, c_int32_t)
+    call gpu_check(edigpu_apply_cops_normal_z(hsrc, hdst, v_src_dev, v_dst_dev, int(size(Os), c_int), ri, o, io, is, &
+         c_null_ptr), "gpu_apply_cops_z")
+  end subroutine gpu_apply_cops_z
 
   !> vvinit = sum_i coefs(i) * O2_i O1_i v_state in one pass, O1_i acting first: the two apply_op_C / apply_op_CDG calls
   !! through an intermediate sector of ED_NORMAL/ED_CHI_PAIR.f90:129-153, 204-241 and ED_CHI_EXCT.f90:178-235, 513-592.

@@ -420,6 +420,35 @@ int edigpu_apply_op_flat(edigpu_handle src, edigpu_handle dst, const double *v_s
 int edigpu_apply_cops_flat(edigpu_handle src, edigpu_handle dst, const double *v_src_dev, double *v_dst_dev, int nops,
                            const double *coef_re_im, const int32_t *create, const int32_t *iorb, const int32_t *ispin,
                            void *stream);
+/*
+ * c / c^+ along one axis (kernels_axisop.hip).  edigpu_apply_op_normal / edigpu_apply_cops_normal also
+ * serve, with source and destination of the same kind, model, device and nph:
+ *   - real normal-mode phonon sectors (edigpu_normal_build with model.nph > 0): the operator in every phonon block;
+ *   - complex normal-mode sectors (edigpu_normal_build_z), real coefficients, interleaved complex vectors;
+ *   - ed_total_ud=F sectors (edigpu_orbs_build): the destination is the source with +-1 particle of spin ispin in orbital
+ *     iorb; the sign is always plus (the impurity is level 0 of its orbital's chain, ED_SECTOR.f90:487-488, 522).
+ * On these routes all operators of a call are applied in one pass, nops is 1 .. 8, v_dst_dev must not overlap v_src_dev,
+ * and the partner tables go through a scratch buffer the destination handle keeps (no allocation per call after the
+ * first).  The real, phonon-free edigpu_normal_build pairs keep their kernel and results.
+ * edigpu_apply_cops_normal_z: the same on complex normal-mode sectors with COMPLEX coefficients coef_re_im[2 s], [2 s + 1]
+ * (the [one, xi] combinations of the off-diagonal Green's function, ED_NORMAL/ED_GF_NORMAL.f90:250-263); other kinds of
+ * handle are refused by name.  edigpu_apply_op_flat / edigpu_apply_cops_flat serve whole superc / nonsu2 phonon sectors
+ * with the same nph on both sides.  All return after the stream has finished.
+ * Refusals: hand-over handles ("hand-over handle"), shards ("is a shard"), handles of different kinds ("different
+ * kinds"), models ("different models"), devices ("different devices") or nph ("different nph"), a destination that is not
+ * the sector the operators lead to ("the operators lead to"), overlapping vectors ("overlaps"), nops outside 1 .. 8
+ * ("nops must be 1 .. 8").
+ *
+ * edigpu_time_apply_op: measurement helper for scripts/time_axisop.py.  `warmup` untimed and `steps` timed runs on the
+ * source handle's stream, each between two HIP events; medians in milliseconds.  ms2[0]: the whole of
+ * edigpu_apply_op_normal as a caller pays it (checks, host table, upload, kernel, wait); ms2[1]: the kernel alone on the
+ * resident table.  Serves every pair edigpu_apply_op_normal serves.
+ */
+int edigpu_apply_cops_normal_z(edigpu_handle src, edigpu_handle dst, const double *v_src_dev, double *v_dst_dev, int nops,
+                               const double *coef_re_im, const int32_t *create, const int32_t *iorb, const int32_t *ispin,
+                               void *stream);
+int edigpu_time_apply_op(edigpu_handle src, edigpu_handle dst, const double *v_src_dev, double *v_dst_dev, int iorb, int ispin,
+                         int create, int warmup, int steps, double *ms2);
 /* edigpu_lanczos_tridiag with the seed in device memory (e.g. the output of edigpu_apply_op_normal; it must be
  * complete when the call is made) and norm2 = <vin|vin> returned as tridiag_Hv_sector_* does.
  * edigpu_lanczos_eigh likewise accepts device pointers for v0 and for the eigenvector. */
