@@ -140,6 +140,8 @@ SIGNATURES = {
     "edigpu_lanczos_bench": (C.c_int, [_vp, C.c_int, C.c_int, _pd, _pd]),
     "edigpu_apply_loop_d": (C.c_int, [_vp, _i64, _pd, _pd]),
     "edigpu_tile_task_map": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _pi32, _pi32, _pi32, _pi32, _pi32]),
+    "edigpu_ell16_images": (C.c_int, [_i64, _pi64, _pi32, _pd, _pi64, _vp, _vp, _pi64]),
+    "edigpu_finalize_ab": (C.c_int, [C.c_int32, _pd, _i64, _pd, _pd, C.c_int32, _pd, C.c_int32, C.c_int32]),
     "edigpu_membw": (C.c_int, [_i64, _pd]),
     "edigpu_sector_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pi32, _pi64]),
     "edigpu_cache_create": (C.c_int, [C.POINTER(_vp), _i64]),

@@ -76,8 +76,11 @@ struct DevEll {
   uint32_t* pk = nullptr;
   double* coef = nullptr;
   // typed LDS image of a row of at most 4095 columns, beside pk: 16-bit entries (15-bit byte offset | sign << 15), two
-  // consecutive slots of a column per word, (width + 1) / 2 * pitch words (upload_ell)
+  // consecutive slots of a column per word, (width + 1) / 2 * pitch16 words (upload_ell).  Odd nrow: words in column
+  // order, pitch16 = pitch; even nrow: in the order in which the rows kernel's threads own the columns
+  // (host_pack.hpp: ell16_owned_col), pitch16 = nrow rounded up to 256
   uint32_t* pk16 = nullptr;
+  int64_t pitch16 = 0;
   // plain image (fallback when > 127 distinct |values| or nrow >= 2^24)
   int32_t* col = nullptr;   // width*pitch, padding: col=row, val=0
   double* val = nullptr;

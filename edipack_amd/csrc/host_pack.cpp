@@ -87,6 +87,17 @@ HostEll encode_ell(const HostCsr& a, bool lds, bool allow_typed, bool allow_16) 
           uint32_t& wd = pk16[(size_t)(k >> 1) * e.pitch + i];
           wd = (k & 1) ? (wd & 0xFFFFu) | h << 16 : (wd & 0xFFFF0000u) | h;
         }
+      if (a.nrow % 2 == 0) {
+        // the same words in ownership order (ell16_owned_col); a thread that owns a column below nrow reads four
+        // words of its 256-position block, so the pitch rounds up to 256; positions of columns past the row are dead
+        e.pitch16o = (a.nrow + 255) / 256 * 256;
+        e.pk16o.assign((size_t)np * e.pitch16o, dead | dead << 16);
+        for (int q = 0; q < np; q++)
+          for (int64_t pos = 0; pos < e.pitch16o; pos++) {
+            const int64_t c = ell16_owned_col(pos);
+            if (c < a.nrow) e.pk16o[(size_t)q * e.pitch16o + pos] = pk16[(size_t)q * e.pitch + c];
+          }
+      }
       e.pk16 = std::move(pk16);
     }
     e.pk = std::move(pk);

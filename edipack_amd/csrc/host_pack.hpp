@@ -22,9 +22,21 @@ struct HostEll {
   std::vector<uint32_t> pk;
   std::vector<double> coef;
   std::vector<uint32_t> pk16;
+  // even nrow: the words of pk16 in the order in which the rows kernel's threads own the columns, (width + 1) / 2
+  // * pitch16o words -- the image such a sector's kernel reads; pk16 (column order) is what an odd nrow reads
+  std::vector<uint32_t> pk16o;
+  int64_t pitch16o = 0;
   std::vector<int32_t> col;
   std::vector<double> val;
 };
+// Ownership order of the 16-bit image (normal_rows_kernel, LINES): a pass of the kernel covers 2048 columns with 512
+// threads; lane l of wave w owns the column pairs {2l, 2l + 1} of the pass's blocks 2w and 2w + 1 of 128 columns, so
+// that a wave's 16-byte-per-lane vector accesses are whole 1 KiB pieces.  The word at position 4 t + e of a pass
+// belongs to the e-th column thread t = 64 w + l owns; this is the column of position pos (it may lie past the row).
+inline int64_t ell16_owned_col(int64_t pos) {
+  const int64_t pass = pos >> 11, t = (pos & 2047) >> 2, e = pos & 3;
+  return (pass << 11) + ((2 * (t >> 6) + (e >> 1)) << 7) + 2 * (t & 63) + (e & 1);
+}
 // lds: the sector's row kernel stages V rows in LDS; the packed layouts then hold byte offsets into
 // the staged row instead of columns, and dead typed slots name its zero slot (index nrow).
 HostEll encode_ell(const HostCsr& a, bool lds, bool allow_typed, bool allow_16);

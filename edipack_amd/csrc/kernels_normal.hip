@@ -27,6 +27,7 @@
 // No MFMA: ~0.25 flop/byte, bandwidth bound.
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 #include "kernels.hpp"
 #include "normal_args.hpp"
@@ -38,11 +39,12 @@ namespace edigpu {
 constexpr int kE = 4;        // adjacent columns owned by one thread per pass (16/32-byte accesses)
 
 // VEC: DimUp even => every (row, 2-column pair) is 16-byte aligned and never straddles a row end
+// dB: distance from a thread's first column pair to its second (2: four adjacent columns; LINES in normal_rows_kernel for the other)
 template <bool VEC>
-__device__ inline void load4(const double* __restrict__ base, int64_t i0, const bool* ok, double* out) {
+__device__ inline void load4(const double* __restrict__ base, int64_t i0, const bool* ok, double* out, int64_t dB = 2) {
   if (VEC) {
     const double2 a = ok[0] ? *reinterpret_cast<const double2*>(base + i0) : make_double2(0.0, 0.0);
-    const double2 b = ok[2] ? *reinterpret_cast<const double2*>(base + i0 + 2) : make_double2(0.0, 0.0);
+    const double2 b = ok[2] ? *reinterpret_cast<const double2*>(base + i0 + dB) : make_double2(0.0, 0.0);
     out[0] = a.x;
     out[1] = a.y;
     out[2] = b.x;
@@ -99,6 +101,22 @@ __global__ void __launch_bounds__(NT)
   double* coef_s = vs + (USE_LDS ? TD * S : 0);
   const int64_t r0 = (int64_t)blockIdx.x * TD;  // first local row of this block
   const int tid = threadIdx.x;
+  // LINES (even DimUp on the 16-bit image): a thread owns two column PAIRS 128 columns apart instead of four adjacent
+  // columns -- lane l of wave w the pairs {2l, 2l + 1} of the blocks 2w and 2w + 1 (128 columns each) of a pass -- so
+  // that every global access of a wave (P, Q, eux loads, P and Q stores) and its LDS staging write is 16 bytes per lane,
+  // consecutive across the wave: one whole 1 KiB piece, where four adjacent columns as two 16-byte accesses touch
+  // sixteen 128-byte lines twice and use half of each.  The image a.ell_pk16 is then in ownership order (encode_ell:
+  // ell16_owned_col), so the table access stays one 16-byte load per lane and slot pair.  Same columns, slots and fma
+  // chains: the same bits.
+  constexpr bool LINES = E16 && VEC;
+  static_assert(!LINES || NT * kE == 2048, "the ownership order of the 16-bit image is that of 512 threads");
+  const int colT = LINES ? ((tid >> 6) << 8) + ((tid & 63) << 1) : tid * kE;  // first owned column of a pass
+  constexpr int cB = LINES ? 128 : 2;                                          // from the first pair to the second
+  // ... and in elements of a vector: in the panel-major layout the two pairs lie in one panel or whole panels apart
+  const int64_t dB = !LINES ? 2 : (bsh >= 1 && bsh <= 7) ? ((int64_t)128 >> bsh) * bps : 128;
+  // (32-bit column arithmetic there: the 64-bit one costs the two registers that the pair map would otherwise add)
+  using col_t = typename std::conditional<LINES, int, int64_t>::type;
+  auto cole = [&](int e) -> int { return (e >> 1) * cB + (e & 1); };  // e-th owned column, from the first
   int nr = TD;
   if (r0 + nr > a.dw_count) nr = (int)(a.dw_count - r0);
   double beta = 0.0, ibeta = 1.0;
@@ -122,14 +140,14 @@ __global__ void __launch_bounds__(NT)
     if (tid == 0) vs[sc] = 0.0;
 #pragma unroll
     for (int ps = 0; ps < 2; ps++) {
-      const int64_t col0 = (int64_t)ps * NT * kE + (int64_t)tid * kE;
+      const col_t col0 = (col_t)ps * NT * kE + colT;
       bool ok[kE];
 #pragma unroll
-      for (int e = 0; e < kE; e++) ok[e] = col0 + e < DimUp;
+      for (int e = 0; e < kE; e++) ok[e] = col0 + cole(e) < (col_t)DimUp;
       const int64_t cs = ok[0] ? col0 : 0;  // a valid address for the index arithmetic of idle lanes
       double q[kE];
-      load4<VEC>(v_src, vix(r0, cs), ok, q);
-      load4<VEC>(v_local, vix(r0, cs), ok, pkeep[ps]);
+      load4<VEC>(v_src, vix(r0, cs), ok, q, dB);
+      load4<VEC>(v_local, vix(r0, cs), ok, pkeep[ps], dB);
 #pragma unroll
       for (int e = 0; e < kE; e++) {
         q[e] -= alpha * pkeep[ps][e];
@@ -137,7 +155,7 @@ __global__ void __launch_bounds__(NT)
       }
       if (VEC) {
         if (ok[0]) *reinterpret_cast<double2*>(vs + col0) = make_double2(q[0], q[1]);
-        if (ok[2]) *reinterpret_cast<double2*>(vs + col0 + 2) = make_double2(q[2], q[3]);
+        if (ok[2]) *reinterpret_cast<double2*>(vs + col0 + cB) = make_double2(q[2], q[3]);
       } else {
 #pragma unroll
         for (int e = 0; e < kE; e++)
@@ -204,13 +222,13 @@ __global__ void __launch_bounds__(NT)
   __syncthreads();
 
   for (int64_t c0 = 0; c0 < DimUp; c0 += (int64_t)NT * kE) {
-    const int64_t col0 = c0 + (int64_t)tid * kE;
-    if (col0 >= DimUp) break;  // no barrier below: safe to leave
+    const col_t col0 = (col_t)c0 + colT;
+    if (col0 >= (col_t)DimUp) break;  // no barrier below: safe to leave (LINES: the second pair lies further right)
     double acc[TD][kE];
     bool ok[kE];
 #pragma unroll
     for (int e = 0; e < kE; e++) {
-      ok[e] = col0 + e < DimUp;
+      ok[e] = col0 + cole(e) < (col_t)DimUp;
 #pragma unroll
       for (int r = 0; r < TD; r++) acc[r][e] = 0.0;
     }
@@ -224,17 +242,20 @@ __global__ void __launch_bounds__(NT)
           if (HDF) {
             const int64_t g = a.dw_first + r0 + r;
             const double edr = a.ed[g];
-            load4<VEC>(a.eux, (int64_t)a.impd[g] * DimUp + col0, ok, h);
+            // (LINES: uniform row pointer + unsigned 32-bit lane offset, so that no 64-bit lane address is formed)
+            if (LINES) load4<VEC>(a.eux + (int64_t)a.impd[g] * DimUp, (int64_t)(uint32_t)col0, ok, h, cB);
+            else load4<VEC>(a.eux, (int64_t)a.impd[g] * DimUp + col0, ok, h, cB);
 #pragma unroll
             for (int e = 0; e < kE; e++) h[e] += edr;
           } else {
-            load4<VEC>(a.hd, (r0 + r) * DimUp + col0, ok, h);
+            if (LINES) load4<VEC>(a.hd + (r0 + r) * DimUp, (int64_t)(uint32_t)col0, ok, h, cB);
+            else load4<VEC>(a.hd, (r0 + r) * DimUp + col0, ok, h, cB);
           }
           if (USE_LDS && !SPLIT) {
 #pragma unroll
-            for (int e = 0; e < kE; e++) x[e] = ok[e] ? vs[r * S + col0 + e] : 0.0;
+            for (int e = 0; e < kE; e++) x[e] = ok[e] ? vs[r * S + col0 + cole(e)] : 0.0;
           } else {
-            load4<VEC>(v_local, vix(r0 + r, col0), ok, x);
+            load4<VEC>(v_local, vix(r0 + r, col0), ok, x, dB);
           }
 #pragma unroll
           for (int e = 0; e < kE; e++) acc[r][e] = (SPLIT && sf != 0) ? 0.0 : h[e] * x[e];  // the diagonal: first part only
@@ -252,8 +273,11 @@ __global__ void __launch_bounds__(NT)
         // 16-bit entries: the KU slots in flight are two 16-byte loads (slot pairs k0 / k0 + 2), a word = the entries
         // of slots 2q (low half) and 2q + 1 (high half) of one column.  Pairs past the table: clamped address,
         // amplitude 0; the dead slot that pads an odd width reads the zero slot with amplitude 0.
-        const uint32_t* __restrict__ epk = a.ell_pk16 + col0;
-        const int epitch = (int)a.ell_pitch;
+        // (LINES: the word at c0 + 4 t + e of a slot pair belongs to the e-th column thread t owns)
+        // (there as a 32-bit lane offset from the uniform pointer of the slot pair: no 64-bit lane address is kept)
+        const uint32_t* __restrict__ epk = a.ell_pk16 + (LINES ? 0 : col0);
+        const uint32_t eoff = (uint32_t)((int)c0 + tid * kE) * 4u;
+        const int epitch = (int)a.ell_pitch16;
         const int np = (a.ell_w + 1) >> 1;
         // measured on config 2: 4 slots in flight beat 2 (43.7 against 46.6 us, plain product); with P kept in registers
         // only 2 fit the 64 VGPRs of 8 waves per SIMD (fused step 70.5 us against 74.2 with 4 slots at 88 VGPRs)
@@ -264,7 +288,8 @@ __global__ void __launch_bounds__(NT)
 #pragma unroll
           for (int u = 0; u < KU / 2; u++) {
             const int q = (k0 >> 1) + u < np ? (k0 >> 1) + u : np - 1;
-            pk2[u] = *reinterpret_cast<const uint4*>(epk + q * epitch);
+            pk2[u] = LINES ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.ell_pk16 + q * epitch) + eoff)
+                           : *reinterpret_cast<const uint4*>(epk + q * epitch);
           }
 #pragma unroll
           for (int u = 0; u < KU; u++) tk[u] = coef_s[k0 + u < 127 ? k0 + u : 127];  // LDS broadcast
@@ -395,7 +420,7 @@ __global__ void __launch_bounds__(NT)
     if (ND) {
       // ---- Hnd: short CSR rows with global columns ----
       if (a.has_nd) {
-        int64_t rp[TD][kE + 1];
+        int64_t rp[TD][kE + 1], rp2[TD][LINES ? 3 : 1];
 #pragma unroll
         for (int r = 0; r < TD; r++)
           if (r < nr) {
@@ -405,6 +430,13 @@ __global__ void __launch_bounds__(NT)
               const int64_t i = (e == 0 || ok[e - 1]) ? i0 + e : i0;  // stays inside the row pointers
               rp[r][e] = a.nd_rp64 ? a.nd_rp64[i] : (int64_t)a.nd_rp32[i];
             }
+            if (LINES) {  // the second pair is not adjacent: its three row pointers
+#pragma unroll
+              for (int e = 0; e < 3; e++) {
+                const int64_t i = ok[2] ? i0 + cB + e : i0;
+                rp2[r][e] = a.nd_rp64 ? a.nd_rp64[i] : (int64_t)a.nd_rp32[i];
+              }
+            }
           }
 #pragma unroll
         for (int r = 0; r < TD; r++)
@@ -413,7 +445,9 @@ __global__ void __launch_bounds__(NT)
             for (int e = 0; e < kE; e++)
               if (ok[e]) {
                 double s = 0.0;
-                for (int64_t jj = rp[r][e]; jj < rp[r][e + 1]; jj++)
+                const bool second = LINES && e >= 2;
+                const int64_t jb = second ? rp2[r][e - 2] : rp[r][e], je = second ? rp2[r][e - 1] : rp[r][e + 1];
+                for (int64_t jj = jb; jj < je; jj++)
                   s += a.nd_val[jj] * v_full[a.nd_col[jj]];
                 acc[r][e] += s;
               }
@@ -426,7 +460,7 @@ __global__ void __launch_bounds__(NT)
         double* dst = hv + vix(r0 + r, col0);
         if (!LOCAL || (SPLIT && sf != 0)) {
           double old[kE];
-          load4<VEC>(hv, vix(r0 + r, col0), ok, old);
+          load4<VEC>(hv, vix(r0 + r, col0), ok, old, dB);
 #pragma unroll
           for (int e = 0; e < kE; e++) acc[r][e] += old[e];
         }
@@ -437,14 +471,14 @@ __global__ void __launch_bounds__(NT)
 #pragma unroll
             for (int e = 0; e < kE; e++) pold[e] = c0 == 0 ? pkeep[0][e] : pkeep[1][e];
           } else {
-            load4<VEC>(v_local, vix(r0 + r, col0), ok, pold);
+            load4<VEC>(v_local, vix(r0 + r, col0), ok, pold, dB);
           }
           double* pdst = (a.xout ? a.xout : const_cast<double*>(v_local)) + vix(r0 + r, col0);
 #pragma unroll
           for (int e = 0; e < kE; e++) acc[r][e] -= beta * pold[e];
           if (VEC) {
             if (ok[0]) *reinterpret_cast<double2*>(pdst) = make_double2(vs[r * S + col0], vs[r * S + col0 + 1]);
-            if (ok[2]) *reinterpret_cast<double2*>(pdst + 2) = make_double2(vs[r * S + col0 + 2], vs[r * S + col0 + 3]);
+            if (ok[2]) *reinterpret_cast<double2*>(pdst + dB) = make_double2(vs[r * S + col0 + cB], vs[r * S + col0 + cB + 1]);
           } else {
 #pragma unroll
             for (int e = 0; e < kE; e++)
@@ -453,7 +487,7 @@ __global__ void __launch_bounds__(NT)
         }
         if (VEC) {
           if (ok[0]) *reinterpret_cast<double2*>(dst) = make_double2(acc[r][0], acc[r][1]);
-          if (ok[2]) *reinterpret_cast<double2*>(dst + 2) = make_double2(acc[r][2], acc[r][3]);
+          if (ok[2]) *reinterpret_cast<double2*>(dst + dB) = make_double2(acc[r][2], acc[r][3]);
         } else {
 #pragma unroll
           for (int e = 0; e < kE; e++)
@@ -613,6 +647,7 @@ static void fill_args(const edigpu_sector* s, NormalArgs& a) {
   a.ell_w = s->up_ell.width;
   a.ell_typed = s->up_ell.typed;
   a.ell_pitch = s->up_ell.pitch;
+  a.ell_pitch16 = s->up_ell.pitch16;
   a.dw_rowptr = s->dw.rowptr32;
   a.dw_col = s->dw.col;
   a.dw_val = s->dw.val;

@@ -24,6 +24,7 @@ struct NormalArgs {
   int ell_typed;  // packed ELL whose slot k holds the hop with amplitude ell_coef[k]
   int64_t split_first, split_count;  // SPLIT row kernel: the columns staged by this launch
   int64_t ell_pitch;
+  int64_t ell_pitch16;  // words per slot pair of ell_pk16 (DevEll::pitch16)
   const int32_t* dw_rowptr;
   const int32_t* dw_col;
   const double* dw_val;

@@ -832,6 +832,27 @@ int edigpu_tile_task_map(int32_t npanels, int32_t blocks_per_panel, int32_t bala
                          int32_t *panel, int32_t *chunk, int32_t *pos);
 
 /*
+ * Test hook (host only, no device needed): the 16-bit typed LDS images of a square factor matrix given as CSR (nrow
+ * rows, values with at most 127 distinct magnitudes), as the rows kernel's set-up encodes them.  info (5 entries):
+ * slots, words per slot pair of the column-order image, words per slot pair of the ownership-order image (0: none,
+ * nrow is odd or the row is too long), words of either image.  pk16 / pk16o: the column-order image and the one in the
+ * order in which the kernel's threads own the columns (even nrow), info[3] / info[4] words; owned_col (info[2]
+ * entries): the column whose word stands at each position of a slot pair of pk16o.  Any of the three may be null (a
+ * first call for the sizes).
+ */
+int edigpu_ell16_images(int64_t nrow, const int64_t *rowptr, const int32_t *col, const double *val, int64_t *info,
+                        uint32_t *pk16, uint32_t *pk16o, int64_t *owned_col);
+
+/*
+ * Test hook: one launch of the kernel that ends a fused Lanczos step, on host data.  partial: 3 * np per-workgroup
+ * sums (<P|Q> | sum (Q - sg P)^2 | <P|P>, sg = scal[0]); P, Q: n doubles (read only when the difference form of beta^2
+ * loses its digits); scal: the nscal >= 8 + 2 * nlanc device scalars of the recurrence (alpha, beta, stop, steps done,
+ * norm, threshold, ..., then the alphas and betas), updated in place; iter: the step, or < 0 to take it from scal[3].
+ */
+int edigpu_finalize_ab(int32_t np, const double *partial, int64_t n, const double *P, const double *Q, int32_t nscal,
+                       double *scal, int32_t iter, int32_t nlanc);
+
+/*
  * Measurement helper for bench.py: `warmup` + `steps` full Lanczos steps (H*v + the vector
  * recurrence) on a random unit start vector.  *ms_wall_per_step = host wall clock of the timed
  * steps (stream synchronised on both sides) / steps; *ms_hv_per_launch = average duration of the
