@@ -142,6 +142,15 @@ SIGNATURES = {
     "edigpu_tile_task_map": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _pi32, _pi32, _pi32, _pi32, _pi32]),
     "edigpu_ell16_images": (C.c_int, [_i64, _pi64, _pi32, _pd, _pi64, _vp, _vp, _pi64]),
     "edigpu_finalize_ab": (C.c_int, [C.c_int32, _pd, _i64, _pd, _pd, C.c_int32, _pd, C.c_int32, C.c_int32]),
+    "edigpu_trl_dots": (C.c_int, [C.c_int32, _i64, C.c_int32, _pd, C.c_int32, _i64, _i64, _pd, _i64, C.c_int32, _pd, _i64,
+                                  C.c_int32]),
+    "edigpu_trl_norm2": (C.c_int, [C.c_int32, _i64, _pd, _i64, _pd, _i64]),
+    "edigpu_trl_subtract": (C.c_int, [C.c_int32, _i64, C.c_int32, _pd, C.c_int32, _i64, _i64, _pd, _i64, _pd, _i64,
+                                      C.c_int32]),
+    "edigpu_trl_decide": (C.c_int, [_pd, _i64, C.c_int32, C.c_double, C.c_double, _pd, _i64, _pi32]),
+    "edigpu_trl_filter": (C.c_int, [_pd, _i64, C.c_int32, C.c_double]),
+    "edigpu_trl_rotate": (C.c_int, [_i64, C.c_int32, C.c_int32, _pd, _i64, _i64, _pd, C.c_int32, _i64, _pd, _i64, _i64]),
+    "edigpu_trl_scale": (C.c_int, [_i64, _pd, _i64, C.c_double]),
     "edigpu_membw": (C.c_int, [_i64, _pd]),
     "edigpu_sector_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pi32, _pi64]),
     "edigpu_cache_create": (C.c_int, [C.POINTER(_vp), _i64]),

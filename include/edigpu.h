@@ -853,6 +853,45 @@ int edigpu_finalize_ab(int32_t np, const double *partial, int64_t n, const doubl
                        double *scal, int32_t iter, int32_t nlanc);
 
 /*
+ * Test hooks: one call of a launcher of the thick-restart eigensolver's multi-vector kernels (csrc/kernels_trl.hip), as
+ * edigpu_lanczos_eigh_multi calls it, on host data and on the calling thread's current device (edigpu_init).  Every
+ * buffer is a pointer and a length in doubles: the whole length is uploaded, and the whole length of every buffer the
+ * launcher may write is downloaded again, so that sentinels around the payload show every write.  n = real or complex
+ * elements of a vector, len = doubles (complex: 2 n).  Q: ncol columns of len doubles, column c at Q + c * ldq, in qlen
+ * doubles.  skip: -1 = the launcher gets a null pointer, 0 / 1 = a device int of that value (1: the launcher does
+ * nothing).  Bad arguments -- negative sizes, a buffer shorter than what the launcher touches, ldq < len with more than
+ * one column -- are refused with a message before the device is used.
+ *
+ * The contract of h: the sums are written in groups of 16 columns and each group writes all 2 * 16 slots, whatever the
+ * number of its columns (zeros beyond them), so h needs room for 2 * 16 * ceil(ndot / 16) doubles; nothing beyond that
+ * is written.
+ */
+/* Test hook: h[2 c], h[2 c + 1] = <Q_c | w> (re, im) for c < ndot <= ncol (trl_dots).  w_col >= 0: w is column w_col of
+ * the uploaded Q (the solver's <w|w> column) and w / wlen are ignored; w_col < 0: w is a buffer of its own, wlen >= len. */
+int edigpu_trl_dots(int32_t cplx, int64_t n, int32_t ndot, const double *Q, int32_t ncol, int64_t ldq, int64_t qlen,
+                    const double *w, int64_t wlen, int32_t w_col, double *h, int64_t hlen, int32_t skip);
+/* Test hook: h[0] = <w|w>, h[1 .. 31] = 0 (trl_norm2); hlen >= 32. */
+int edigpu_trl_norm2(int32_t cplx, int64_t n, const double *w, int64_t wlen, double *h, int64_t hlen);
+/* Test hook: w -= sum_c h_c Q_c for c < nvec <= ncol, in ascending c (trl_subtract); hlen >= 2 nvec, wlen >= len.
+ * Columns whose coefficient is exactly zero are not read. */
+int edigpu_trl_subtract(int32_t cplx, int64_t n, int32_t nvec, const double *Q, int32_t ncol, int64_t ldq, int64_t qlen,
+                        const double *h, int64_t hlen, double *w, int64_t wlen, int32_t skip);
+/* Test hook: the decision after a first Gram-Schmidt sweep (trl_decide).  h: nvec coefficient pairs, then <w|w>
+ * (hlen >= 2 nvec + 2); hf (hflen >= 2 nvec): the coefficients to subtract; *skip: in = the value the device int holds
+ * before, out = 1 when a second pass is not needed. */
+int edigpu_trl_decide(const double *h, int64_t hlen, int32_t nvec, double eta2, double thr2, double *hf, int64_t hflen,
+                      int32_t *skip);
+/* Test hook: coefficients with |h_c|^2 <= thr2 * <w|w> set to zero in place, the <w|w> slot h[2 nvec], h[2 nvec + 1]
+ * cleared (trl_filter); hlen >= 2 nvec + 2. */
+int edigpu_trl_filter(double *h, int64_t hlen, int32_t nvec, double thr2);
+/* Test hook: out_c = sum_j Y[j * ldy + c] Q_j, c < k, j < m (trl_rotate_basis); Q: m columns at ldq in qlen doubles,
+ * out: k columns at ldo in olen doubles, Y: ylen >= (m - 1) * ldy + k doubles, ldy >= k. */
+int edigpu_trl_rotate(int64_t len, int32_t m, int32_t k, const double *Q, int64_t ldq, int64_t qlen, const double *Y,
+                      int32_t ldy, int64_t ylen, double *out, int64_t ldo, int64_t olen);
+/* Test hook: v[0 .. len) *= f (trl_scale); vlen >= len. */
+int edigpu_trl_scale(int64_t len, double *v, int64_t vlen, double f);
+
+/*
  * Measurement helper for bench.py: `warmup` + `steps` full Lanczos steps (H*v + the vector
  * recurrence) on a random unit start vector.  *ms_wall_per_step = host wall clock of the timed
  * steps (stream synchronised on both sides) / steps; *ms_hv_per_launch = average duration of the
