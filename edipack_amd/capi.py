@@ -114,6 +114,10 @@ SIGNATURES = {
     "edigpu_apply_cops_normal_z": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _pd, _pi32, _pi32, _pi32, _vp]),
     "edigpu_time_apply_op": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _pd]),
     "edigpu_lanczos_tridiag_dev": (C.c_int, [_vp, _vp, C.c_int, _pd, _pd, C.c_double, C.POINTER(C.c_int), _pd]),
+    "edigpu_apply_multi_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "edigpu_batch_set_width": (C.c_int, [_vp, C.c_int]),
+    "edigpu_lanczos_tridiag_batch_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _pd, _pd, C.c_double, C.POINTER(C.c_int), _pd,
+                                                   C.POINTER(C.c_int)]),
     "edigpu_apply_occ": (C.c_int, [_vp, _vp, _vp, _pd, _pd, _vp]),
     "edigpu_occ_moments": (C.c_int, [_vp, _vp, C.c_int, _pd, _pd]),
     "edigpu_time_occ": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _pd]),

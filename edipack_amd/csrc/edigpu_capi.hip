@@ -1085,7 +1085,7 @@ static int tql2(int n, std::vector<double>& d, std::vector<double>& e, std::vect
 }
 
 // enqueue one Lanczos step (iter is 0-based); vin/vout/tmp live in the workspace
-static bool flat_lanczos_fusable(const edigpu_sector* s) {
+bool flat_lanczos_fusable(const edigpu_sector* s) {
   if (s->sw.lanczos_unfused || s->nloc != s->dim || s->nloc == 0 || s->nph > 0) return false;
   if (s->kind == 2) return true;
   return s->kind == 1 && csr_lanczos_fusable(s->loc) && s->nonloc.nnz == 0;
@@ -3350,6 +3350,7 @@ int edigpu_destroy(edigpu_handle s) {
   free_rdm_flat(s);
   free_ph(s);
   free_axisop(s);
+  free_batch(s);
   dev_free(s->d_vin);
   dev_free(s->d_vout);
   dev_free(s->d_tmp);

@@ -214,6 +214,23 @@ int axisop_apply(edigpu_sector* src, edigpu_sector* dst, const double* v_src, do
                  const double* cim, const int32_t* create, const int32_t* iorb, const int32_t* ispin, hipStream_t st,
                  const char* who);
 
+// Interleaved workspace of edigpu_apply_multi_dev / edigpu_lanczos_tridiag_batch_dev (edigpu_batch.hip; kernels_multi.hip):
+// two buffers of W vectors, the per-column partial sums and scalars.  Allocated by the first batch call on the handle,
+// grown when a later call needs more, kept until edigpu_destroy.
+struct BatchDev {
+  int W = 0;                 // columns the two vector buffers hold
+  int64_t len = 0;           // doubles per column (edigpu_sector::ws_len when they were allocated)
+  double *P = nullptr, *Q = nullptr;
+  double* partial = nullptr;
+  int64_t partial_cap = 0;   // in doubles
+  double* scal = nullptr;
+  size_t scal_cap = 0;       // in doubles
+};
+void free_batch(edigpu_sector* s);
+// a flat or on-the-fly sector held whole on this GPU, without phonons, whose product has the fused Lanczos epilogue
+// (edigpu_capi.hip: the sectors whose single-seed step is rotate -> product with partials -> finalize)
+bool flat_lanczos_fusable(const edigpu_sector* s);
+
 }  // namespace edigpu
 
 struct edigpu_sector {
@@ -320,6 +337,9 @@ struct edigpu_sector {
   edigpu::PhDev* ph = nullptr;
   // ---- c / c^+ along one axis: table scratch of calls with this handle as destination (lazily built) ----
   edigpu::AxisDev* axis = nullptr;
+  // ---- interleaved vectors of the batched product and recurrence (lazily built) ----
+  edigpu::BatchDev* batch = nullptr;
+  int batch_force_w = 0;         // edigpu_batch_set_width: 2, 4, 8 = the widest group whatever the size (measurement hook)
   // ---- Lanczos workspace (lazily allocated) ----
   int64_t partial_cap = 0;      // doubles in d_partial
   double* d_vin = nullptr;

@@ -76,6 +76,26 @@ int lz_rotate_lazy(double* P, double* Q, int64_t n, const double* scal, hipStrea
 int lz_next_vector(const double* P, const double* Q, double* X, int64_t n, const double* scal, bool lazy, hipStream_t st);
 int launch_direct(const edigpu_sector* s, const double* v_full, double* hv, hipStream_t st);
 
+// ---- W = 2, 4 or 8 interleaved vectors per sweep over a flat sector (kernels_multi.hip) ----
+// layout: element (row, column j) at Xi[row * W + j] (double, or double2 when cplx); g <= W vectors of nrow elements in
+// the natural layout, one after another; the columns past g are written as zeros
+int launch_interleave_multi(int W, int cplx, int64_t nrow, int g, const double* src, double* dst, hipStream_t st);
+int launch_deinterleave_multi(int W, int cplx, int64_t nrow, int g, const double* src, double* dst, hipStream_t st);
+// Yi = H Xi (lz = false), or Yi += H Xi with the per-column partials [3 * W][*np] of <P|Q>, sum (Q - sg_j P)^2, <P|P>
+// (lz = true; sg_j = scal[j * sstride + SC_ALPHA]); cap: doubles in `partial`, checked before anything is enqueued
+int launch_csr_multi(const DevCsr& a, int cplx, int W, const double* Xi, double* Yi, bool lz, double* partial, int64_t cap,
+                     int* np, const double* scal, int64_t sstride, hipStream_t st);
+int launch_direct_multi(const edigpu_sector* s, int W, const double* Xi, double* Yi, bool lz, double* partial, int64_t cap,
+                        int* np, const double* scal, int64_t sstride, hipStream_t st);
+// the vector kernels of W recurrences in lock-step: column j keeps its SC_* scalars at scal + j * sstride; a column whose
+// stop flag is set is held at exactly zero
+int lz_norm_begin_multi(int W, int cplx, int64_t nrow, double* P, double* partial, int64_t cap, double* scal,
+                        int64_t sstride, hipStream_t st);
+int lz_rotate_lazy_multi(int W, int cplx, int64_t nrow, double* P, double* Q, const double* scal, int64_t sstride,
+                         hipStream_t st);
+int lz_finalize_ab_multi(int W, int cplx, int64_t nrow, const double* P, const double* Q, const double* partial, int np,
+                         double* scal, int64_t sstride, int nlanc, hipStream_t st);
+
 // ---- Lanczos vector kernels (kernels_lanczos.hip); n counts doubles ----
 int lz_norm_begin(double* vin, int64_t n, double* partial, double* scal, hipStream_t st);
 int lz_rotate(double* vin, double* vout, int64_t n, const double* scal, hipStream_t st);

@@ -492,6 +492,32 @@ class SectorHamiltonian:
                                                          C.byref(nd), C.byref(n2)), "edigpu_lanczos_tridiag_dev")
         return a, b, nd.value, n2.value
 
+    def apply_multi_dev(self, x_ptr: int, y_ptr: int, nvec: int, stream: int = 0) -> None:
+        """Y_j = H X_j for nvec consecutive device vectors (natural layout); whole superc / nonsu2 sectors sweep H once
+        per group of up to 8 vectors (edigpu_apply_multi_dev)."""
+        capi.check(capi.lib().edigpu_apply_multi_dev(self._h, int(nvec), x_ptr, y_ptr, stream if stream else None),
+                   "edigpu_apply_multi_dev")
+
+    def batch_set_width(self, width: int) -> None:
+        """Measurement hook: 2, 4 or 8 = the widest interleaved group of apply_multi_dev / lanczos_tridiag_batch_dev on this
+        handle whatever its size, 0 = the measured default (edigpu_batch_set_width)."""
+        capi.check(capi.lib().edigpu_batch_set_width(self._h, int(width)), "edigpu_batch_set_width")
+
+    def lanczos_tridiag_batch_dev(self, vin_ptr: int, nseed: int, nlanc: int, threshold: float = 1e-12):
+        """nseed tridiagonalisations of consecutive device seeds in lock-step (edigpu_lanczos_tridiag_batch_dev):
+        -> (a[nseed, nlanc], b[nseed, nlanc], niter[nseed], norm2[nseed], route); every row is what lanczos_tridiag_dev
+        returns for that seed, route = 0 (one seed after another) or the widest interleaved group (2, 4, 8)."""
+        shape = (max(int(nseed), 0), max(int(nlanc), 0))
+        a = np.zeros(shape)
+        b = np.zeros(shape)
+        nd = np.zeros(shape[0], dtype=np.intc)
+        n2 = np.zeros(shape[0])
+        route = C.c_int(0)
+        capi.check(capi.lib().edigpu_lanczos_tridiag_batch_dev(
+            self._h, int(nseed), vin_ptr, int(nlanc), capi.pd(a), capi.pd(b), threshold,
+            nd.ctypes.data_as(C.POINTER(C.c_int)), capi.pd(n2), C.byref(route)), "edigpu_lanczos_tridiag_batch_dev")
+        return a, b, nd.astype(np.int64), n2, route.value
+
     def apply_op_to(self, dst: "SectorHamiltonian", v_src_ptr: int, v_dst_ptr: int, iorb: int, ispin: int,
                     create: bool, stream: int = 0) -> None:
         """apply_op_C / apply_op_CDG on device vectors: |dst> = c^(+)_{iorb,ispin} |src> (self = source sector)."""

@@ -198,6 +198,18 @@ module EDIGPU_SHIM
        real(c_double), intent(out) :: norm2
        integer(c_int) :: ierr
      end function edigpu_lanczos_tridiag_dev
+     function edigpu_lanczos_tridiag_batch_dev(h, nseed, vin_dev, nlanc, alanc, blanc, threshold, niter, norm2, route) &
+          bind(C, name="edigpu_lanczos_tridiag_batch_dev") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, vin_dev
+       integer(c_int), value :: nseed, nlanc
+       real(c_double), intent(inout) :: alanc(*), blanc(*)
+       real(c_double), value :: threshold
+       integer(c_int), intent(out) :: niter(*)
+       real(c_double), intent(out) :: norm2(*)
+       integer(c_int), intent(out) :: route
+       integer(c_int) :: ierr
+     end function edigpu_lanczos_tridiag_batch_dev
      function edigpu_lanczos_eigh(h, nitermax, tol, check_every, v0, eval, evec, niter) &
           bind(C, name="edigpu_lanczos_eigh") result(ierr)
        import :: c_ptr, c_int, c_double
@@ -448,7 +460,7 @@ module EDIGPU_SHIM
   public :: gpu_cache_create, gpu_cache_clear, gpu_cache_destroy, gpu_cache_stats, gpu_build_cached
   public :: gpu_sp_lanc_eigh_d, gpu_sp_lanc_eigh_c, gpu_sp_eigh_d, gpu_sp_eigh_c
   public :: gpu_vec_alloc, gpu_vec_free, gpu_vec_upload_d, gpu_vec_download_d, gpu_vec_upload_c, gpu_vec_download_c
-  public :: gpu_sp_lanc_eigh_dev, gpu_apply_op, gpu_apply_cops, gpu_lanc_tridiag_dev
+  public :: gpu_sp_lanc_eigh_dev, gpu_apply_op, gpu_apply_cops, gpu_lanc_tridiag_dev, gpu_lanc_tridiag_batch_dev
   public :: gpu_apply_op_N, gpu_apply_op_Sz, gpu_occ_moments, gpu_imp_rdm, gpu_imp_rdm_flat
   public :: gpu_apply_pairs
   public :: gpu_apply_cops_z
@@ -1009,6 +1021,24 @@ contains
     call gpu_check(edigpu_lanczos_tridiag_dev(gpu_sector, vin_dev, int(size(alanc), c_int), alanc, blanc, &
          lanc_threshold, niter, norm2), "gpu_lanc_tridiag_dev")
   end subroutine gpu_lanc_tridiag_dev
+
+  !> The seeds of one jsector in one call: seeds_dev holds nseed consecutive device vectors of the live sector (the
+  !! outputs of gpu_apply_op / gpu_apply_cops into consecutive offsets of one gpu_vec_alloc buffer); alfa(:, k),
+  !! beta(:, k), norm2(k) are what gpu_lanc_tridiag_dev returns for seed k.  Whole superc / nonsu2 sectors advance
+  !! groups of seeds in lock-step through one sweep over H per step (edigpu_lanczos_tridiag_batch_dev); every other
+  !! sector runs the seeds one after another.  Compile-only: fortran/test_shim.f90 does not call it.
+  subroutine gpu_lanc_tridiag_batch_dev(seeds_dev, nseed, alfa, beta, norm2)
+    type(c_ptr), intent(in) :: seeds_dev
+    integer, intent(in) :: nseed
+    real(8), intent(inout) :: alfa(:, :), beta(:, :)   ! (nlanc, nseed): column k = the row of seed k in the C arrays
+    real(8), intent(out) :: norm2(:)
+    integer(c_int) :: niter(nseed), route
+    if (.not. c_associated(gpu_sector)) stop "gpu_lanc_tridiag_batch_dev: Hsector NOT allocated"
+    if (size(alfa, 2) /= nseed .or. size(beta, 2) /= nseed .or. size(beta, 1) /= size(alfa, 1) .or. size(norm2) /= nseed) &
+         stop "gpu_lanc_tridiag_batch_dev: shapes"
+    call gpu_check(edigpu_lanczos_tridiag_batch_dev(gpu_sector, int(nseed, c_int), seeds_dev, int(size(alfa, 1), c_int), &
+         alfa, beta, lanc_threshold, niter, norm2, route), "gpu_lanc_tridiag_batch_dev")
+  end subroutine gpu_lanc_tridiag_batch_dev
 
   ! ---- N > 1: one MPI rank per GPU -------------------------------------------------------------
 

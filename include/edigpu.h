@@ -456,6 +456,57 @@ int edigpu_lanczos_tridiag_dev(edigpu_handle h, const double *vin_dev, int nlanc
                                double threshold, int *niter_done, double *norm2);
 
 /*
+ * Several vectors per sweep over H (superc / nonsu2 sectors; edigpu_batch.hip, kernels_multi.hip).
+ *
+ * The seeds of one Green's-function target sector -- c^+_{a,up}|gs> and c_{a,dw}|gs> of every orbital and their
+ * apply_Cops combinations in superc, every c^+_{a,s}|gs> in nonsu2 -- are tridiagonalised by the same H.  On a stored
+ * flat sector the sweep is bound by the matrix stream and by one gathered line per entry, on an on-the-fly sector by
+ * the integer work per (row, term): neither grows with the number of vectors when these are interleaved element by
+ * element, Xi[row * W + j].  Normal-mode products are bound by the vectors themselves and gain nothing: they take the
+ * single-vector path below.
+ *
+ * edigpu_apply_multi_dev: Y_j = H X_j for nvec consecutive device vectors of the sector's length (natural layout, as
+ * edigpu_lanczos_eigh_multi writes evecs).  Serves every handle edigpu_apply_dev serves.  A whole flat sector without
+ * phonons, stored with the SELL image or on the fly, takes groups of vectors (as wide as the batched recurrence below
+ * takes on that sector) through interleave -> one sweep -> de-interleave (nvec >= 2); every other handle runs nvec plain
+ * products.  Enqueued on `stream`, no synchronisation.
+ *
+ * edigpu_lanczos_tridiag_batch_dev: nseed independent tridiagonalisations in lock-step.  vin_dev: nseed consecutive
+ * seeds (device, complete when the call is made).  alanc, blanc: row-major [nseed][nlanc], each row exactly as
+ * edigpu_lanczos_tridiag_dev fills it.  niter_done[nseed], norm2[nseed].  *route (may be NULL): 0 = the seeds were run
+ * one after another through the single-seed path; 2, 4 or 8 = the widest interleaved group used.
+ *   - It serves every handle edigpu_lanczos_tridiag_dev serves and refuses what that call refuses, with its message.
+ *   - nseed < 1, nlanc <= 0 or a NULL handle, vin_dev, alanc or blanc: "bad argument", before any device work
+ *     (niter_done and norm2 may be NULL, as in the single call).
+ *   - Interleaved route: a whole flat sector on this GPU without phonons, stored with the SELL image (real or complex)
+ *     or on the fly, nseed >= 2, neither EDIGPU_LANCZOS_UNFUSED nor EDIGPU_LANCZOS_EXACTBETA set.  Everything else
+ *     (normal mode, ed_total_ud=F, phonon sectors, CSR images, _CMPLX_NORMAL) is route 0: a loop over the single-seed
+ *     call, whose results it returns unchanged.
+ *   - Seeds go in groups of at most 8; a group of g >= 2 seeds runs at width W = 2, 4 or 8 >= g with zero seeds in the
+ *     spare columns (a last group of one seed takes the single-seed path).  The widest group a sector takes follows the
+ *     measurement, the fastest measured width of each size band: stored 8 up to 13 000 rows, 4 up to
+ *     200 000, 2 (pairs of seeds) above; on the fly 8 up to 4 000 rows, 4 up to 50 000, 2 above.  On large sectors the
+ *     wider groups were measured to lose.
+ *   - Every seed stops on its own |beta| < threshold.  A stopped or zero seed gets the niter_done, norm2 and zeros the
+ *     single call gives; its column is held at exactly zero from then on and the other seeds are unaffected.
+ *   - The interleaved buffers (2 * W vectors) belong to the handle: allocated by the first call, reused, freed by
+ *     edigpu_destroy.  Failing to allocate them is an error, not a silent route 0.
+ *   - On the interleaved route both entries stage through those buffers, so calls on ONE handle that use them must be
+ *     ordered by the caller, as calls that use the handle's Lanczos workspace must: edigpu_apply_multi_dev enqueues on
+ *     `stream` and returns at once, edigpu_lanczos_tridiag_batch_dev runs on the handle's own stream and returns after it
+ *     has finished.  Issue a second edigpu_apply_multi_dev on the same stream, or after that stream has been synchronised;
+ *     synchronise it before edigpu_lanczos_tridiag_batch_dev.  (edigpu_apply_dev has no such shared state.)
+ *
+ * edigpu_batch_set_width: measurement hook of scripts/time_tridiag_batch.py.  width = 2, 4 or 8 makes that the widest
+ * group of the two entries above on this handle whatever its size; 0 returns to the measured default.  Results do not
+ * depend on it, only the time.
+ */
+int edigpu_apply_multi_dev(edigpu_handle h, int nvec, const void *x_dev, void *y_dev, void *stream);
+int edigpu_batch_set_width(edigpu_handle h, int width);
+int edigpu_lanczos_tridiag_batch_dev(edigpu_handle h, int nseed, const double *vin_dev, int nlanc, double *alanc,
+                                     double *blanc, double threshold, int *niter_done, double *norm2, int *route);
+
+/*
  * Operators diagonal in the occupation basis, on device vectors of ONE sector (source = destination sector).
  *
  * edigpu_apply_occ: v_dst(i) = ( sum_a w_up[a] n_{a,up}(i) + w_dw[a] n_{a,dw}(i) ) * v_src(i) -- apply_op_N
