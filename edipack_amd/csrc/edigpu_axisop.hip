@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "host_axisop.hpp"
 #include "kernels.hpp"
 
@@ -19,21 +20,21 @@ struct AxisDev {
 
 void free_axisop(edigpu_sector* s) {
   if (!s || !s->axis) return;
-  if (s->axis->d) (void)hipFree(s->axis->d);
+  dev_free(s->axis->d);
   delete s->axis;
   s->axis = nullptr;
 }
 
 namespace {
 
-bool axis_is_orbs_handover(const edigpu_sector* s) { return s->kind == 3 && s->orbs_nups.empty(); }
+bool axis_is_orbs_handover(const edigpu_sector* s) { return s->kind == kOrbs && s->orbs_nups.empty(); }
 
 const char* axis_kind_name(const edigpu_sector* s) {
   switch (s->kind) {
-    case 0: return s->nph > 0 ? "a real normal-mode phonon sector" : "a real normal-mode sector";
-    case 1: case 2: return "a superc / nonsu2 sector";
-    case 3: return "an ed_total_ud=F sector";
-    case 4: return "a complex normal-mode sector";
+    case kNormal: return s->has_phonons() ? "a real normal-mode phonon sector" : "a real normal-mode sector";
+    case kFlat: case kDirect: return "a superc / nonsu2 sector";
+    case kOrbs: return "an ed_total_ud=F sector";
+    case kCmplxNormal: return "a complex normal-mode sector";
   }
   return "an unknown handle";
 }
@@ -41,11 +42,11 @@ const char* axis_kind_name(const edigpu_sector* s) {
 // one refusal per kind of handle this route does not serve
 int axis_refuse(const edigpu_sector* s, const std::string& who, const char* which) {
   const std::string w = who + ": the " + which + " handle ";
-  if (s->kind == 1 || s->kind == 2) {
+  if (s->is_flat_family()) {
     set_error(w + "is a superc / nonsu2 sector: edigpu_apply_op_flat / edigpu_apply_cops_flat serve those");
     return 1;
   }
-  if (s->kind == 0 && !s->built_by_library) {
+  if (s->kind == kNormal && !s->built_by_library) {
     set_error(w + "is a hand-over handle (edigpu_normal_create): it has no sector labels");
     return 1;
   }
@@ -53,15 +54,15 @@ int axis_refuse(const edigpu_sector* s, const std::string& who, const char* whic
     set_error(w + "is a hand-over handle (edigpu_orbs_create): it has no sector labels");
     return 1;
   }
-  if (s->kind != 0 && s->kind != 3 && s->kind != 4) {
+  if (s->kind != kNormal && s->kind != kOrbs && s->kind != kCmplxNormal) {
     set_error(w + "is not a normal-mode sector");
     return 1;
   }
-  if (s->nloc != s->dim || s->row_first != 0) {
+  if (!s->is_whole() || s->row_first != 0) {
     set_error(w + "is a shard: it must hold the whole sector (shards are not supported)");
     return 1;
   }
-  if (s->kind == 3 && s->nph > 0) {
+  if (s->kind == kOrbs && s->has_phonons()) {
     set_error(w + "is an ed_total_ud=F phonon sector: not supported");
     return 1;
   }
@@ -86,7 +87,7 @@ int axis_prepare(const edigpu_sector* src, const edigpu_sector* dst, const doubl
                  AxisTables& tab) {
   if (need_kind4)
     for (const edigpu_sector* s : {src, dst})
-      if (s->kind != 4) {
+      if (s->kind != kCmplxNormal) {
         set_error(who + ": the " + (s == src ? "source" : "destination") + " handle is " + axis_kind_name(s) +
                   ": complex coefficients are served on complex normal-mode sectors (edigpu_normal_build_z) only");
         return 1;
@@ -117,7 +118,7 @@ int axis_prepare(const edigpu_sector* src, const edigpu_sector* dst, const doubl
   for (int k = 0; k < nops; k++) ops[(size_t)k] = AxisOp{create[k], iorb[k], ispin[k]};
   const edigpu_model& m = src->model;
   std::string why;
-  if (src->kind == 3) {
+  if (src->kind == kOrbs) {
     std::vector<int> nu((size_t)m.norb), nd((size_t)m.norb);
     why = axisop_build_orbs(m.norb, m.nbath, src->orbs_nups.data(), src->orbs_ndws.data(), nops, ops.data(), nu.data(),
                             nd.data(), tab);
@@ -128,7 +129,7 @@ int axis_prepare(const edigpu_sector* src, const edigpu_sector* dst, const doubl
     }
   } else {
     int nu = 0, nd = 0;
-    why = axisop_build_normal(src->sec_a, src->sec_b, model_ns(m), m.norb, src->nph + 1, src->kind == 4, nops, ops.data(), nu,
+    why = axisop_build_normal(src->sec_a, src->sec_b, model_ns(m), m.norb, src->nph + 1, src->kind == kCmplxNormal, nops, ops.data(), nu,
                               nd, tab);
     if (why.empty() && (dst->sec_a != nu || dst->sec_b != nd)) {
       set_error(who + ": the destination handle is the sector (" + std::to_string(dst->sec_a) + ", " + std::to_string(dst->sec_b) +
@@ -159,13 +160,7 @@ int axis_upload(edigpu_sector* dst, const AxisTables& tab, const double* cre, co
   if (!dst->axis) dst->axis = new AxisDev();
   AxisDev* dev = dst->axis;
   const size_t n = std::max<size_t>(tab.part.size(), 1);
-  if (dev->cap < n) {
-    if (dev->d) (void)hipFree(dev->d);
-    dev->d = nullptr;
-    dev->cap = 0;
-    EDIGPU_HIP(hipMalloc((void**)&dev->d, n * sizeof(uint32_t)));
-    dev->cap = n;
-  }
+  if (dev_grow(&dev->d, &dev->cap, n)) return 1;
   if (!tab.part.empty())
     EDIGPU_HIP(hipMemcpyAsync(dev->d, tab.part.data(), tab.part.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   a = AxisArgs();
@@ -195,7 +190,7 @@ int axis_call(edigpu_sector* dst, const AxisTables& tab, const double* cre, cons
 }  // namespace
 
 bool axisop_route(const edigpu_sector* src, const edigpu_sector* dst) {
-  auto old_kind = [](const edigpu_sector* s) { return s->kind == 0 && s->built_by_library && s->nph == 0; };
+  auto old_kind = [](const edigpu_sector* s) { return s->kind == kNormal && s->built_by_library && s->nph == 0; };
   return !(old_kind(src) && old_kind(dst));
 }
 

@@ -2,7 +2,7 @@
 // edigpu_apply_multi_dev, edigpu_lanczos_tridiag_batch_dev): checks, the route, the handle's interleaved workspace and
 // the lock-step loop over kernels_multi.hip.
 //
-// The recurrence is the single-seed one of flat_lanczos_fusable sectors (edigpu_capi.hip: lanczos_step) run on W
+// The recurrence is the single-seed one of flat_lanczos_fusable sectors (edigpu_lanczos.hip: lanczos_step) run on W
 // columns at once: norms and scaling, then per step rotate (later steps) -> Q += H P with the three partial sums per
 // column -> finalize per column.  Nothing waits for the host until the last step is enqueued; a column that stops is
 // held at zero by the kernels, so the host never looks at the stop flags.
@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "kernels.hpp"
 
 namespace edigpu {
@@ -17,8 +18,7 @@ namespace edigpu {
 void free_batch(edigpu_sector* s) {
   if (!s || !s->batch) return;
   BatchDev* b = s->batch;
-  for (void* q : {(void*)b->P, (void*)b->Q, (void*)b->partial, (void*)b->scal})
-    if (q) (void)hipFree(q);
+  dev_free_all(b->P, b->Q, b->partial, b->scal);
   delete b;
   s->batch = nullptr;
 }
@@ -34,9 +34,9 @@ void free_batch(edigpu_sector* s) {
 constexpr int64_t kSellW8Rows = 13000, kSellW4Rows = 200000, kDirW8Rows = 4000, kDirW4Rows = 50000;
 
 static bool multi_sector(const edigpu_sector* s) {
-  if (s->nloc != s->dim || s->nloc == 0 || s->nph > 0) return false;
-  if (s->kind == 2) return true;
-  return s->kind == 1 && csr_lanczos_fusable(s->loc) && s->nonloc.nnz == 0;
+  if (!s->is_whole() || s->nloc == 0 || s->has_phonons()) return false;
+  if (s->kind == kDirect) return true;
+  return s->kind == kFlat && csr_lanczos_fusable(s->loc) && s->nonloc.nnz == 0;
 }
 
 // The widest interleaved group a sector takes: per kind and size band the width that was measured FASTEST per seed and
@@ -48,7 +48,7 @@ static bool multi_sector(const edigpu_sector* s) {
 static int widest_kept(const edigpu_sector* s) {
   if (s->batch_force_w) return s->batch_force_w;
   const int64_t rows = s->nloc;
-  if (s->kind == 2) return rows <= kDirW8Rows ? 8 : rows <= kDirW4Rows ? 4 : 2;
+  if (s->kind == kDirect) return rows <= kDirW8Rows ? 8 : rows <= kDirW4Rows ? 4 : 2;
   return rows <= kSellW8Rows ? 8 : rows <= kSellW4Rows ? 4 : 2;
 }
 
@@ -74,9 +74,7 @@ static int ensure_batch(edigpu_sector* s, int W, size_t nscal, const char* who) 
     return 1;
   };
   if (b->W < W || b->len != len) {
-    if (b->P) (void)hipFree(b->P);
-    if (b->Q) (void)hipFree(b->Q);
-    b->P = b->Q = nullptr;
+    dev_free_all(b->P, b->Q);
     b->W = 0;
     const size_t bytes = (size_t)W * (size_t)len * sizeof(double);
     hipError_t e = hipMalloc((void**)&b->P, bytes);
@@ -86,29 +84,16 @@ static int ensure_batch(edigpu_sector* s, int W, size_t nscal, const char* who) 
     b->len = len;
   }
   const int64_t np = multi_partials(s, W);
-  if (b->partial_cap < np) {
-    if (b->partial) (void)hipFree(b->partial);
-    b->partial = nullptr;
-    b->partial_cap = 0;
-    const hipError_t e = hipMalloc((void**)&b->partial, (size_t)np * sizeof(double));
-    if (e != hipSuccess) return fail("partial sums", e);
-    b->partial_cap = np;
-  }
-  if (b->scal_cap < nscal) {
-    if (b->scal) (void)hipFree(b->scal);
-    b->scal = nullptr;
-    b->scal_cap = 0;
-    const hipError_t e = hipMalloc((void**)&b->scal, nscal * sizeof(double));
-    if (e != hipSuccess) return fail("scalars", e);
-    b->scal_cap = nscal;
-  }
+  // (a failed hipMalloc is the thread's last HIP error: the message names it as before)
+  if (dev_grow(&b->partial, &b->partial_cap, np)) return fail("partial sums", hipGetLastError());
+  if (dev_grow(&b->scal, &b->scal_cap, nscal)) return fail("scalars", hipGetLastError());
   return 0;
 }
 
 // Yi (+)= H Xi on the handle's kind
 static int multi_product(const edigpu_sector* s, int W, const double* Xi, double* Yi, bool lz, double* partial, int64_t cap,
                          int* np, const double* scal, int64_t sstride, hipStream_t st) {
-  if (s->kind == 2) return launch_direct_multi(s, W, Xi, Yi, lz, partial, cap, np, scal, sstride, st);
+  if (s->kind == kDirect) return launch_direct_multi(s, W, Xi, Yi, lz, partial, cap, np, scal, sstride, st);
   return launch_csr_multi(s->loc, s->is_complex, W, Xi, Yi, lz, partial, cap, np, scal, sstride, st);
 }
 

@@ -26,7 +26,7 @@ struct edigpu_cache_s {
     edigpu_model model;
     int kind;        // 0 normal (ed_total_ud = T), 1 stored superc / nonsu2, 2 on-the-fly, 3 normal with complex algebra
     int q1, q2;
-    edigpu_handle h;
+    edigpu::SectorPtr h;  // an entry that leaves the list takes its handle with it
     int64_t bytes;
   };
   std::mutex mu;
@@ -62,7 +62,6 @@ int edigpu_cache_create(edigpu_cache* c, int64_t max_device_bytes) {
 int edigpu_cache_clear(edigpu_cache c) {
   if (!c) return 0;
   std::lock_guard<std::mutex> lk(c->mu);
-  for (auto& e : c->lru) (void)edigpu_destroy(e.h);
   c->lru.clear();
   c->used = 0;
   return 0;
@@ -100,7 +99,7 @@ int edigpu_cache_get(edigpu_cache c, const edigpu_model* model, int kind, int q1
     if (it->kind == kind && it->q1 == q1 && it->q2 == q2 && std::memcmp(&it->model, model, sizeof(edigpu_model)) == 0) {
       c->lru.splice(c->lru.begin(), c->lru, it);
       c->hits++;
-      *h = it->h;
+      *h = it->h.get();
       return 0;
     }
   c->misses++;
@@ -120,15 +119,13 @@ int edigpu_cache_get(edigpu_cache c, const edigpu_model* model, int kind, int q1
   e.kind = kind;
   e.q1 = q1;
   e.q2 = q2;
-  e.h = nh;
+  e.h.reset(nh);
   e.bytes = handle_bytes_estimate(free_before, nh);
-  c->lru.push_front(e);
   c->used += e.bytes;
+  c->lru.push_front(std::move(e));
   // evict from the cold end, never the two most recently returned handles
   while (c->used > c->budget && c->lru.size() > 2) {
-    auto& victim = c->lru.back();
-    (void)edigpu_destroy(victim.h);
-    c->used -= victim.bytes;
+    c->used -= c->lru.back().bytes;
     c->lru.pop_back();
     c->evictions++;
   }

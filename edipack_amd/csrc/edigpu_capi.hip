@@ -1,23 +1,15 @@
-// edigpu_capi.hip -- implementation of the C ABI declared in include/edigpu.h.
-//
-// Host-side orchestration only: device memory layout of a sector, uploads, kernel
-// sequencing on the handle's HIP stream, the device-resident Lanczos driver.
+// edigpu_capi.hip -- the core of the C ABI declared in include/edigpu.h: the calling thread's error string and current
+// device, the queries on a handle and on a model's sectors, raw device memory, edigpu_destroy.  The other jobs of the
+// ABI have a file each (Source layout).
 // There is no CPU compute path: without a usable HIP device every entry point fails.
 #include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <map>
-#include <memory>
 #include <mutex>
 #include <tuple>
 
+#include "dev_mem.hpp"
 #include "host_ib.hpp"
-#include "host_pack.hpp"
-#include "host_sb.hpp"
 #include "kernels.hpp"
-#include "tile_map.hpp"
 
 namespace edigpu {
 
@@ -25,31 +17,10 @@ static thread_local std::string g_err;
 static thread_local int g_device = 0;
 void set_error(const std::string& msg) { g_err = msg; }
 
-template <class T>
-static int dev_upload(T** d, const T* h, size_t n) {
-  *d = nullptr;
-  if (n == 0) return 0;
-  EDIGPU_HIP(hipMalloc((void**)d, n * sizeof(T)));
-  EDIGPU_HIP(hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
+bool have_error() { return !g_err.empty(); }
+int current_device() { return g_device; }
 
-// the row meta of host_pack.hpp as the device reads it
-static const int4* as_int4(const std::vector<HostInt4>& v) {
-  static_assert(sizeof(HostInt4) == sizeof(int4) && offsetof(HostInt4, x) == offsetof(int4, x) &&
-                    offsetof(HostInt4, y) == offsetof(int4, y) && offsetof(HostInt4, z) == offsetof(int4, z) &&
-                    offsetof(HostInt4, w) == offsetof(int4, w),
-                "HostInt4 is uploaded as int4");
-  return reinterpret_cast<const int4*>(v.data());
-}
-
-template <class T>
-static void dev_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-static int ensure_device(int* count_out = nullptr) {
+int ensure_device(int* count_out) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess || n <= 0) {
@@ -61,95 +32,6 @@ static int ensure_device(int* count_out = nullptr) {
   }
   if (count_out) *count_out = n;
   return 0;
-}
-
-// upload a CSR given with int64 row pointers; columns optionally shifted
-static int upload_csr(DevCsr& d, int64_t nrow, const int64_t* rowptr, const int32_t* col,
-                      const double* val, int cplx) {
-  d = DevCsr();
-  d.nrow = nrow;
-  d.nnz = rowptr ? rowptr[nrow] : 0;
-  d.avg_row = nrow > 0 ? (double)d.nnz / (double)nrow : 0.0;
-  if (nrow == 0) return 0;
-  if (d.nnz >= ((int64_t)1 << 31)) {
-    d.wide = 1;
-    if (dev_upload(&d.rowptr64, rowptr, (size_t)nrow + 1)) return 1;
-  } else {
-    std::vector<int32_t> rp((size_t)nrow + 1);
-    for (int64_t i = 0; i <= nrow; i++) rp[i] = (int32_t)rowptr[i];
-    if (dev_upload(&d.rowptr32, rp.data(), rp.size())) return 1;
-  }
-  // 8 zero entries behind the last row: the panel sweep reads a row's list in batches of 8 (kernels_panel.hip)
-  std::vector<int32_t> cpad(col, col + d.nnz);
-  cpad.resize((size_t)d.nnz + 8, 0);
-  std::vector<double> vpad(val, val + (size_t)d.nnz * (cplx ? 2 : 1));
-  vpad.resize(vpad.size() + 8, 0.0);
-  if (dev_upload(&d.col, cpad.data(), cpad.size())) return 1;
-  if (dev_upload(&d.val, vpad.data(), vpad.size())) return 1;
-  return 0;
-}
-
-static void free_ell(DevEll& e) {
-  dev_free(e.pk);
-  dev_free(e.pk16);
-  dev_free(e.coef);
-  dev_free(e.col);
-  dev_free(e.val);
-}
-
-static void free_csr(DevCsr& d) {
-  dev_free(d.sell_ptr);
-  dev_free(d.sell_pk);
-  dev_free(d.sell_dict);
-  dev_free(d.sell_diag);
-  dev_free(d.sell_col);
-  dev_free(d.sell_val);
-  dev_free(d.rowptr32);
-  dev_free(d.rowptr64);
-  dev_free(d.col);
-  dev_free(d.val);
-}
-
-// device copies of the images of host_pack.hpp
-static int upload_ell(DevEll& e, const HostCsr& a, bool lds, const Switches& sw) {
-  e = DevEll();
-  const HostEll h = encode_ell(a, lds, !sw.ell_untyped, sw.ell16);
-  e.nrow = h.nrow;
-  e.pitch = h.pitch;
-  e.width = h.width;
-  e.typed = h.typed;
-  // one 16-bit image per sector: in ownership order where the rows kernel owns column pairs (even nrow)
-  const std::vector<uint32_t>& h16 = h.pk16o.empty() ? h.pk16 : h.pk16o;
-  e.pitch16 = h.pk16o.empty() ? h.pitch : h.pitch16o;
-  return dev_upload(&e.pk, h.pk.data(), h.pk.size()) || dev_upload(&e.coef, h.coef.data(), h.coef.size()) ||
-         dev_upload(&e.pk16, h16.data(), h16.size()) || dev_upload(&e.col, h.col.data(), h.col.size()) ||
-         dev_upload(&e.val, h.val.data(), h.val.size());
-}
-
-static int upload_sell(DevCsr& d, int64_t nrow, int64_t ncol, const int64_t* rowptr, const int32_t* col,
-                       const double* val, int cplx, bool is_loc, const Switches& sw, double max_pad = 1.6) {
-  if (sw.csr_nosell) return 0;
-  const HostSell h = encode_sell(nrow, ncol, rowptr, col, val, cplx, is_loc, max_pad, !sw.csr_unpacked);
-  if (!h.built) return 0;
-  d.sell = 1;
-  d.nslice = h.nslice;
-  d.sell_packed = h.packed ? 1 : 0;
-  return dev_upload(&d.sell_ptr, h.ptr.data(), h.ptr.size()) || dev_upload(&d.sell_pk, h.pk.data(), h.pk.size()) ||
-         dev_upload(&d.sell_dict, h.dict.data(), h.dict.size()) || dev_upload(&d.sell_diag, h.diag.data(), h.diag.size()) ||
-         dev_upload(&d.sell_col, h.col.data(), h.col.size()) || dev_upload(&d.sell_val, h.val.data(), h.val.size());
-}
-
-static std::string check_csr(int64_t nrow, int64_t ncol, const int64_t* rowptr, const int32_t* col,
-                             const char* what) {
-  if (!rowptr) return std::string(what) + ": rowptr is NULL";
-  if (rowptr[0] != 0) return std::string(what) + ": rowptr[0] != 0";
-  for (int64_t i = 0; i < nrow; i++)
-    if (rowptr[i + 1] < rowptr[i]) return std::string(what) + ": rowptr not monotone";
-  const int64_t nnz = rowptr[nrow];
-  if (nnz > 0 && !col) return std::string(what) + ": col is NULL";
-  for (int64_t k = 0; k < nnz; k++)
-    if (col[k] < 0 || col[k] >= ncol) return std::string(what) + ": column index out of range";
-  return "";
 }
 
 int ensure_dynamic_lds(const void* kernel, size_t bytes) {
@@ -199,1069 +81,6 @@ int resident_blocks(const void* kernel, int threads, size_t dyn_lds) {
   return n;
 }
 
-static int finish_handle(edigpu_sector* s) {
-  EDIGPU_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  return 0;
-}
-
-static void free_sb(DevSb* q) {
-  if (!q) return;
-  dev_free(q->urank); dev_free(q->ublist); dev_free(q->uslot); dev_free(q->rmap2); dev_free(q->up_vtab); dev_free(q->up_tloc);
-  dev_free(q->e0); dev_free(q->ebw); dev_free(q->up_korb); dev_free(q->chunk_row); dev_free(q->chunk_slot); dev_free(q->cdesc_off);
-  dev_free(q->cdesc); dev_free(q->dw_vtab); dev_free(q->dw_tloc); dev_free(q->dw_korb); dev_free(q->nd_dw);
-  for (DevSb::Half& h : q->half) {
-    dev_free(h.ublist32); dev_free(h.ugap); dev_free(h.uslot); dev_free(h.rmap2); dev_free(h.ebw);
-  }
-  delete q;
-}
-
-static void free_ib(IbDev* p) {
-  if (!p) return;
-  free_sb(p->sb);
-  p->sb = nullptr;
-  dev_free(p->urank); dev_free(p->rmap2); dev_free(p->ublist); dev_free(p->up_vtab); dev_free(p->up_timp); dev_free(p->up_ebath);
-  dev_free(p->xu); dev_free(p->ed); dev_free(p->impd); dev_free(p->pos); dev_free(p->colof); dev_free(p->chunk_row);
-  dev_free(p->chunk_blk); dev_free(p->dcls); dev_free(p->dblist); dev_free(p->dmeta); dev_free(p->dw_vtab);
-  dev_free(p->dw_timp); dev_free(p->ndcoef); dev_free(p->nd_dw); dev_free(p->nd_up);
-  dev_free(p->up_pmask); dev_free(p->dw_pmask); dev_free(p->up_pt); dev_free(p->dw_pt);
-  free_ell(p->pr.ell);
-  dev_free(p->pr.eux);
-  dev_free(p->urank_low);
-  for (IbDevHalf& h : p->half) {
-    dev_free(h.ublist); dev_free(h.utop); dev_free(h.rmap2);
-  }
-}
-
-// Local-block tables (host_sb.hpp, kernels_sb.hip) on the layout of the impurity-block image d: when the sector is of that
-// form and a geometry of the kernels fits, the product and the fused step of the device-resident loops run on them
-// (Switches::sb off: keep the round-3 impurity-block kernels).
-static int setup_sb(IbDev* d, const HostNormal& hn, const HostIb& h, const Switches& sw) {
-  if (!sw.sb) return 0;
-  const bool verbose = sw.sb_verbose;
-  const int chunk_rows = sw.ib_rows;
-  auto skip = [&](const std::string& why) {
-    if (verbose) fprintf(stderr, "edigpu: no local-block tables: %s\n", why.c_str());
-    return 0;
-  };
-  const bool split = h.nhalf == 2;  // rows staged in halves: the local-block ROWS kernel per half, the impurity-block columns kernel
-  if (split) {
-    // Opt-in (Switches::sb_split): measured at Ns = 17 the local-block rows kernel on half rows takes 3.30 + 3.15 ms against
-    // 2.77 + 2.58 ms for the round-3 kernel (kernels_sb_impl.hpp, TOP) -- the gathers of the hop over the top level cost it
-    // more than the cheaper walk gains.  Kept, tested (CPU shim and GPU), off.
-    if (!sw.sb_split) return skip("rows staged in halves (EDIGPU_SB_SPLIT=1 takes the local-block rows kernel)");
-  }
-  const int nb0 = sb_nb0(h.norb);
-  if (nb0 < 1 || hn.ns - h.norb - nb0 < 2) return skip("too few bath levels");
-  const int slots = sb_rows_slots(hn, nb0, split);
-  if (slots < 1) return skip("not of the local-block form");
-  const int plen_rows = split ? std::max(h.half[0].npanels, h.half[1].npanels) * kIbPanel : h.npanels * kIbPanel;
-  HostSb t;
-  const int gs = sb_cols_gs(sw.sb_cw), waves = sb_cols_waves(sw.sb_cw);
-  build_sb(hn, h, nb0, chunk_rows, 64 * slots, 1, waves, t, gs, sw.sb_amode);  // (the class stride of the row image: needed to choose the geometry)
-  if (!t.valid) return skip(t.why);
-  int nt = 0, nbt = 0;
-  if (!sb_rows_config(h.norb, slots, plen_rows, t.rcs, sw.sb_nt, sw.sb_nbt, &nt, &nbt)) return skip("no geometry of the rows kernel fits");
-  if (split && nbt > 4) return skip("rows staged in halves: more than 4 blocks per thread");
-  build_sb(hn, h, nb0, chunk_rows, nt, nbt, waves, t, gs, sw.sb_amode);
-  if (!t.valid) return skip(t.why);
-  if (split && t.amode != 0) return skip("rows staged in halves: all-orbital walk only");
-  std::unique_ptr<DevSb, void (*)(DevSb*)> q(new DevSb(), free_sb);
-  q->nb0 = t.nb0;
-  q->nloc = t.nloc;
-  q->amode = t.amode;
-  q->nbw_up = t.up.nbw;
-  q->nbw_dw = t.dw.nbw;
-  q->rows_nt = nt;
-  q->rows_nbt = nbt;
-  q->rimg_len = t.rimg_len;
-  q->rcs = t.rcs;
-  q->rows_lds = split ? sb_rows_lds(t.up.nbw - 1, t.rimg_len, true) : sb_rows_lds(t.up.nbw, t.rimg_len);
-  q->nhalf = t.nhalf;
-  q->lowbits = t.lowbits;
-  q->nchunks = (int)t.chunk_row.size() - 1;
-  q->max_chunk_rows = t.max_chunk_rows;
-  q->max_chunk_slots = t.max_chunk_slots;
-  q->cols_gs = t.cols_gs;
-  q->cols_lds = sb_cols_lds(t.dw.nbw, t.nloc, t.max_chunk_rows, t.max_chunk_slots, t.cols_gs);
-  if (q->rows_lds > 158 * 1024 || q->cols_lds > 158 * 1024) return skip("tables larger than the LDS");
-  std::vector<uint32_t> rmap2(t.rmap.size() / 2);
-  for (size_t i = 0; i < rmap2.size(); i++) rmap2[i] = (uint32_t)t.rmap[2 * i] | ((uint32_t)t.rmap[2 * i + 1] << 16);
-  if (split) {
-    for (int hh = 0; hh < 2; hh++) {
-      const SbUpHalf& hf = t.half[hh];
-      DevSb::Half& dh = q->half[hh];
-      dh.panel0 = hf.panel0;
-      dh.npanels = hf.npanels;
-      std::vector<uint32_t> ub(hf.ublist.size()), rm(hf.rmap.size() / 2);
-      for (size_t i = 0; i < ub.size(); i++) ub[i] = (uint32_t)hf.ublist[i] | ((uint32_t)hf.utop[i] << 16);
-      for (size_t i = 0; i < rm.size(); i++) rm[i] = (uint32_t)hf.rmap[2 * i] | ((uint32_t)hf.rmap[2 * i + 1] << 16);
-      if (dev_upload(&dh.ublist32, ub.data(), ub.size()) || dev_upload(&dh.ugap, hf.ugap.data(), hf.ugap.size()) ||
-          dev_upload(&dh.uslot, hf.uslot.data(), hf.uslot.size()) || dev_upload(&dh.rmap2, rm.data(), rm.size()) ||
-          dev_upload(&dh.ebw, hf.ebw.data(), hf.ebw.size()))
-        return 1;
-    }
-  }
-  if (dev_upload(&q->urank, t.urank.data(), t.urank.size()) ||
-      (!split && (dev_upload(&q->ublist, t.ublist.data(), t.ublist.size()) ||
-                  dev_upload(&q->uslot, t.uslot.data(), t.uslot.size()) || dev_upload(&q->rmap2, rmap2.data(), rmap2.size()))) ||
-      dev_upload(&q->up_vtab, t.up.vtab.data(), t.up.vtab.size()) || dev_upload(&q->up_tloc, t.up.tloc.data(), t.up.tloc.size()) ||
-      dev_upload(&q->e0, t.e0.data(), t.e0.size()) || dev_upload(&q->ebw, t.ebw.data(), t.ebw.size()) || dev_upload(&q->up_korb, t.up.korb.data(), t.up.korb.size()) ||
-      dev_upload(&q->chunk_row, t.chunk_row.data(), t.chunk_row.size()) ||
-      dev_upload(&q->chunk_slot, t.chunk_slot.data(), t.chunk_slot.size()) ||
-      dev_upload(&q->cdesc_off, t.cdesc_off.data(), t.cdesc_off.size()) || dev_upload(&q->cdesc, t.cdesc.data(), t.cdesc.size()) ||
-      dev_upload(&q->dw_vtab, t.dw.vtab.data(), t.dw.vtab.size()) || dev_upload(&q->dw_tloc, t.dw.tloc.data(), t.dw.tloc.size()) ||
-      dev_upload(&q->dw_korb, t.dw.korb.data(), t.dw.korb.size()) || dev_upload(&q->nd_dw, t.nd_dw.data(), t.nd_dw.size()))
-    return 1;
-  if (verbose)
-    fprintf(stderr, "edigpu: local-block tables: nb0 %d amode %d rows %d x %d cs %d (%d slots, %zu B LDS) cols low %d chunks %d (%zu B LDS)\n", t.nb0, t.amode,
-            nt, nbt, t.rcs, slots, q->rows_lds, t.lowbits, q->nchunks, q->cols_lds);
-  d->sb = q.release();
-  return 0;
-}
-
-// Short rows (IbDev::PosRows): Hup and the diagonal table in POSITION order for the generic LDS row kernel, which then
-// works on the padded panel layout beside the local-block columns kernel.  Built on request (Switches::posrows) when the
-// sector has local-block tables with whole rows; for rows shorter than Switches::ib_min_row_bytes() the block image is then built for it.
-static int setup_pos_rows(edigpu_sector* s, const HostNormal& hn, const HostIb& h) {
-  IbDev* d = s->ib;
-  if (!d || !d->sb || d->sb->nhalf != 1 || !s->factored || !hn.fac.valid) return 0;
-  // Opt-in.  Measured on config 2: the plain product gains (0.110 against 0.119 ms: 0.43 against 0.40
-  // of the peak) but the fused Lanczos step loses (0.166 against 0.158 ms per step, 6020 against 6350 it/s): on 16-column
-  // panels a row is 215 pieces 439 KB apart, and the fused row kernel's five streams of them take 100-120 us where the
-  // 128-column panels of the default loop (27 pieces per row) take 81.
-  if (!s->sw.posrows) return 0;
-  const int plen = d->plen;
-  const int td = normal_pick_rows_per_block(plen, hn.dim_dw, s->sw.rows_td);
-  if (td < 1) return 0;
-  const HostCsr& up = s->h_up;
-  HostCsr pu;
-  pu.nrow = pu.ncol = plen;
-  pu.rowptr.assign((size_t)plen + 1, 0);
-  std::vector<int32_t> colof((size_t)plen, -1);
-  for (int64_t i = 0; i < hn.dim_up; i++) colof[(size_t)h.pos[(size_t)i]] = (int32_t)i;
-  for (int p = 0; p < plen; p++) {
-    const int32_t i = colof[(size_t)p];
-    pu.rowptr[(size_t)p + 1] = pu.rowptr[(size_t)p] + (i < 0 ? 0 : up.rowptr[(size_t)i + 1] - up.rowptr[(size_t)i]);
-  }
-  pu.col.resize((size_t)pu.rowptr[(size_t)plen]);
-  pu.val.resize(pu.col.size());
-  for (int p = 0; p < plen; p++) {
-    const int32_t i = colof[(size_t)p];
-    if (i < 0) continue;
-    int64_t at = pu.rowptr[(size_t)p];
-    for (int64_t q = up.rowptr[(size_t)i]; q < up.rowptr[(size_t)i + 1]; q++, at++) {
-      pu.col[(size_t)at] = h.pos[(size_t)up.col[(size_t)q]];
-      pu.val[(size_t)at] = up.val[(size_t)q];
-    }
-  }
-  if (upload_ell(d->pr.ell, pu, true, s->sw)) return 1;
-  if (!d->pr.ell.pk || !d->pr.ell.typed) {  // the fast path of the row kernel only
-    free_ell(d->pr.ell);
-    d->pr.ell = DevEll();
-    return 0;
-  }
-  const size_t nimp = hn.fac.eux.size() / (size_t)hn.dim_up;
-  std::vector<double> ex(nimp * (size_t)plen, 0.0);
-  for (size_t c = 0; c < nimp; c++)
-    for (int64_t i = 0; i < hn.dim_up; i++) ex[c * (size_t)plen + (size_t)h.pos[(size_t)i]] = hn.fac.eux[c * (size_t)hn.dim_up + (size_t)i];
-  if (dev_upload(&d->pr.eux, ex.data(), ex.size())) return 1;
-  d->pr.td = td;
-  d->pr.on = true;
-  if (s->sw.sb_verbose) fprintf(stderr, "edigpu: rows half on the generic row kernel in position order (plen %d, %d rows per workgroup, ELL width %d)\n", plen, td, d->pr.ell.width);
-  return 0;
-}
-
-// device copy of the impurity-block image; leaves s->ib null (and returns 0) when the sector is not of that form
-static int setup_ib(edigpu_sector* s, const HostNormal& hn) {
-  const Switches& sw = s->sw;
-  HostIb h;
-  // Rows whose image does not fit the LDS beside the tables are staged one half at a time (host_ib.hpp IbUpHalf);
-  // Switches::ib_split forces that form on any sector (tests) or leaves such sectors to the generic kernels.
-  const int lds_budget = !sw.ib_split ? 156 * 1024 : *sw.ib_split != 0 ? -1 : 0;
-  build_ib(hn, sw.ib_rows, h, lds_budget);
-  if (!h.valid) {
-    if (sw.ib_verbose) fprintf(stderr, "edigpu: no impurity-block image: %s\n", h.why.c_str());
-    return 0;
-  }
-  int nt = 0, nbt = 0;
-  const int plen = h.npanels * kIbPanel;
-  size_t rows_lds = 0;
-  if (h.nhalf == 2) {
-    const IbUpHalf &a = h.half[0], &b = h.half[1];
-    const int rimg = std::max(a.rimg_len, b.rimg_len);
-    if (!ib_rows_config(h.norb, h.up.nb - 1, (int)std::max(a.ublist.size(), b.ublist.size()),
-                        std::max(a.npanels, b.npanels) * kIbPanel, rimg, sw.ib_nt, &nt, &nbt, true))
-      return 0;
-    rows_lds = ib_rows_lds_bytes(h.up.nb - 1, rimg);
-  } else {
-    if (!ib_rows_config(h.norb, h.up.nb, (int)h.ublist.size(), plen, h.rimg_len, sw.ib_nt, &nt, &nbt)) return 0;
-    rows_lds = ib_rows_lds_bytes(h.up.nb, h.rimg_len);
-  }
-  int mcb = 8;
-  for (size_t c = 0; c + 1 < h.chunk_blk.size(); c++) mcb = std::max(mcb, h.chunk_blk[c + 1] - h.chunk_blk[c]);
-  std::unique_ptr<IbDev> d(new IbDev());
-  d->norb = h.norb;
-  d->nb_up = h.up.nb;
-  d->nb_dw = h.dw.nb;
-  d->npanels = h.npanels;
-  d->plen = plen;
-  d->nlist = (int)h.ublist.size();
-  for (int i = 0; i < 5; i++) d->ucls[i] = h.ucls[std::min(i, h.norb + 1)];
-  d->lowbits = h.lowbits;
-  d->nchunks = (int)h.chunk_row.size() - 1;
-  d->max_chunk_rows = h.max_chunk_rows;
-  d->max_chunk_blocks = mcb;
-  // workgroups per chunk of the columns kernel.  Two per chunk make one panel's tasks cover the 64 workgroup slots of an
-  // XCD, so that a single panel is in flight per L2 -- measured SLOWER (Ns = 16: 2.79 against 2.42 ms per product,
-  // Ns = 15: 0.69 against 0.64): staging the chunk twice costs more than the gathers that then hit the L2 save.
-  d->nsub = sw.ib_nsub;
-  d->cols2 = sw.ib_cols2;
-  d->nterms = h.nterms;
-  d->dim_up = hn.dim_up;
-  d->dim_dw = hn.dim_dw;
-  d->ps = hn.dim_dw * kIbPanel;
-  d->ps += (int64_t)sw.ib_pspad / 2 * 2;  // doubles between two panels (tuning)
-  d->len = (int64_t)h.npanels * d->ps;
-  d->rows_nt = nt;
-  d->rows_nbt = nbt;
-  d->rows_lds = rows_lds;
-  for (int i = 0; i < 5; i++) {
-    d->rcb[i] = h.rcb[i];
-    d->rcs[i] = h.rcs[i];
-  }
-  d->rimg_len = h.rimg_len;
-  std::vector<uint32_t> rmap2((size_t)plen / 2);
-  for (size_t i = 0; i < rmap2.size(); i++) rmap2[i] = (uint32_t)h.rmap[2 * i] | ((uint32_t)h.rmap[2 * i + 1] << 16);
-  d->cols_lds = ib_cols_lds_bytes(h.dw.nb, h.max_chunk_rows, mcb);
-  if (d->cols_lds > 158 * 1024) return 0;
-  std::vector<int32_t> colof((size_t)plen, -1);
-  for (int64_t i = 0; i < hn.dim_up; i++) colof[(size_t)h.pos[(size_t)i]] = (int32_t)i;
-  IbDev* p = d.get();
-  if (dev_upload(&p->urank, h.urank.data(), h.urank.size()) || dev_upload(&p->rmap2, rmap2.data(), rmap2.size()) ||
-      dev_upload(&p->ublist, h.ublist.data(), h.ublist.size()) ||
-      dev_upload(&p->up_vtab, h.up.vtab.data(), h.up.vtab.size()) || dev_upload(&p->up_timp, h.up.timp.data(), h.up.timp.size()) ||
-      dev_upload(&p->up_ebath, h.up.ebath.data(), h.up.ebath.size()) || dev_upload(&p->xu, h.xu.data(), h.xu.size()) ||
-      dev_upload(&p->ed, h.ed.data(), h.ed.size()) || dev_upload(&p->impd, h.impd.data(), h.impd.size()) ||
-      dev_upload(&p->pos, h.pos.data(), h.pos.size()) || dev_upload(&p->colof, colof.data(), colof.size()) ||
-      dev_upload(&p->chunk_row, h.chunk_row.data(), h.chunk_row.size()) ||
-      dev_upload(&p->chunk_blk, h.chunk_blk.data(), h.chunk_blk.size()) || dev_upload(&p->dcls, h.dcls.data(), h.dcls.size()) ||
-      dev_upload(&p->dblist, h.dblist.data(), h.dblist.size()) || dev_upload(&p->dmeta, h.dmeta.data(), h.dmeta.size()) ||
-      dev_upload(&p->dw_vtab, h.dw.vtab.data(), h.dw.vtab.size()) || dev_upload(&p->dw_timp, h.dw.timp.data(), h.dw.timp.size()) ||
-      dev_upload(&p->nd_dw, h.nd_dw.data(), h.nd_dw.size()) || dev_upload(&p->nd_up, h.nd_up.data(), h.nd_up.size())) {
-    free_ib(p);
-    return 1;
-  }
-  p->up_np = (int)h.up.pmask.size();
-  p->dw_np = (int)h.dw.pmask.size();
-  if ((p->up_np > 0 && (dev_upload(&p->up_pmask, h.up.pmask.data(), h.up.pmask.size()) || dev_upload(&p->up_pt, h.up.pt.data(), h.up.pt.size()))) ||
-      (p->dw_np > 0 && (dev_upload(&p->dw_pmask, h.dw.pmask.data(), h.dw.pmask.size()) || dev_upload(&p->dw_pt, h.dw.pt.data(), h.dw.pt.size())))) {
-    free_ib(p);
-    return 1;
-  }
-  if (h.nterms > 0 && dev_upload(&p->ndcoef, h.ndcoef.data(), h.ndcoef.size())) {
-    free_ib(p);
-    return 1;
-  }
-  p->nhalf = h.nhalf;
-  if (h.nhalf == 2) {
-    p->top_eps = h.up.vtab[(size_t)(h.up.nb - 1) * 4 + 3];
-    int rc = dev_upload(&p->urank_low, h.urank_low.data(), h.urank_low.size());
-    for (int k = 0; k < 2 && !rc; k++) {
-      const IbUpHalf& src = h.half[k];
-      IbDevHalf& dst = p->half[k];
-      dst.panel0 = src.panel0;
-      dst.npanels = src.npanels;
-      dst.nlist = (int)src.ublist.size();
-      dst.rimg_len = src.rimg_len;
-      for (int i = 0; i < 5; i++) {
-        dst.ucls[i] = src.ucls[std::min(i, h.norb + 1)];
-        dst.rcb[i] = src.rcb[i];
-        dst.rcs[i] = src.rcs[i];
-      }
-      std::vector<uint32_t> m2((size_t)src.npanels * kIbPanel / 2);
-      for (size_t i = 0; i < m2.size(); i++) m2[i] = (uint32_t)src.rmap[2 * i] | ((uint32_t)src.rmap[2 * i + 1] << 16);
-      rc = dev_upload(&dst.ublist, src.ublist.data(), src.ublist.size()) || dev_upload(&dst.utop, src.utop.data(), src.utop.size()) ||
-           dev_upload(&dst.rmap2, m2.data(), m2.size());
-    }
-    if (rc) {
-      free_ib(p);
-      return 1;
-    }
-  }
-  s->ib = d.release();
-  if (setup_sb(s->ib, hn, h, sw)) return 1;
-  return setup_pos_rows(s, hn, h);
-}
-
-static int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_t dw_first,
-                        int64_t dw_count, const double* hd, const HostCsr& up, const HostCsr& dw,
-                        const int64_t* nd_rowptr, const int32_t* nd_col, const double* nd_val,
-                        HostNormal* built = nullptr) {
-  s->kind = 0;
-  s->is_complex = 0;
-  s->device = g_device;
-  s->dim_up = dim_up;
-  s->dim_dw = dim_dw;
-  s->dw_first = dw_first;
-  s->dw_count = dw_count;
-  s->dim = dim_up * dim_dw;
-  s->nloc = dim_up * dw_count;
-  s->row_first = dw_first * dim_up;
-  s->h_up = up;
-  s->h_dw = dw;
-  std::vector<int32_t> tile_starts;  // row chunks of the LDS-tiled panel sweep (empty: not planned)
-  const Switches& sw = s->sw;
-  s->rows_per_block = normal_pick_rows_per_block(dim_up, dw_count, sw.rows_td);
-  // Rows longer than the LDS (rows_per_block == 0): staged in column parts when the typed LDS image exists
-  // (normal_rows_kernel SPLIT); Switches::row_split forces it on any sector (tests) or switches it off.
-  {
-    int parts = 0;
-    if (sw.row_split) {
-      parts = *sw.row_split;
-      if (parts > 1) s->rows_per_block = 0;
-    } else if (s->rows_per_block == 0) {
-      parts = (int)(((dim_up + 2) * 8 + 140 * 1024 - 1) / (140 * 1024));
-    }
-    if (s->rows_per_block == 0 && parts > 1 && dim_up >= 4 * parts) {
-      if (upload_ell(s->up_ell, up, true, sw)) return 1;
-      if (s->up_ell.typed && s->up_ell.pk) {
-        s->row_split = parts;
-      } else {
-        free_ell(s->up_ell);
-        s->up_ell = DevEll();
-      }
-    }
-  }
-  if (s->row_split == 1 && upload_ell(s->up_ell, up, s->rows_per_block != 0, sw)) return 1;
-  if (upload_csr(s->dw, dim_dw, dw.rowptr.data(), dw.col.data(), dw.val.data(), 0)) return 1;
-  for (int64_t i = 0; i < dim_dw; i++)
-    s->dw_maxrow = std::max<int>(s->dw_maxrow, (int)(dw.rowptr[i + 1] - dw.rowptr[i]));
-  {
-    // panel sweep variant (kernels_panel.hip).  Measured: cache-resident sectors are 13 % SLOWER with the two-column
-    // panels (fewer, fatter waves), hence the size gate Switches::panel_vec2_min (tests force the large-sector kernels on
-    // small sectors).  Switches::tile_rows sets the chunk length (KiB of LDS per workgroup), at most kTileMaxRows of
-    // kernels_panel.hip: 4 rows per wave (their results live in registers), 16 waves.
-    if (sw.panel_vec2 && dim_up >= 2 && dim_up * dw_count >= sw.panel_vec2_min) s->panel_mode = 1;
-    if (s->panel_mode == 1 && sw.panel_tile && dw_count > 0 && dim_dw < ((int64_t)1 << 24)) {
-      plan_tile_chunks(dw, dw_first, dw_count, sw.tile_rows, tile_starts, s->tile_rows);
-      s->tile_nchunks = (int)tile_starts.size() - 1;
-      if (dev_upload(&s->d_tile_chunks, tile_starts.data(), tile_starts.size())) return 1;
-      s->panel_mode = 2;
-    }
-  }
-  s->has_nd = nd_rowptr != nullptr && nd_rowptr[s->nloc] > 0;
-  s->nd_nnz = s->has_nd ? nd_rowptr[s->nloc] : 0;
-  if (built && !nd_rowptr) {  // factored-only build: no explicit arrays were made
-    s->has_nd = built->has_nd && built->nd_nnz > 0;
-    s->nd_nnz = s->has_nd ? built->nd_nnz : 0;
-  }
-  // library-built sectors keep the diagonal and Hnd in factored form on the device (the explicit
-  // arrays stay on the host for export); Switches::normal_explicit forces the explicit image.
-  if (built && built->fac.valid && built->fac.nterms <= 16 && !sw.normal_explicit) {
-    const HostFactored& f = built->fac;
-    s->factored = 1;
-    s->fac_nimp = f.nimp;
-    s->fac_nterms = f.nterms;
-    if (dev_upload(&s->d_eux, f.eux.data(), f.eux.size())) return 1;
-    if (dev_upload(&s->d_ed, f.ed.data(), f.ed.size())) return 1;
-    if (dev_upload(&s->d_impd, f.impd.data(), f.impd.size())) return 1;
-    if (f.nterms > 0) {
-      if (dev_upload(&s->d_ndcoef, f.coef.data(), f.coef.size())) return 1;
-      if (dev_upload(&s->d_jup, f.jup.data(), f.jup.size())) return 1;
-      s->col_halo = factored_col_halo(f, dim_up);
-      if (dev_upload(&s->d_jdw, f.jdw.data(), f.jdw.size())) return 1;
-      // merged per-local-row list for the panel kernel: Hdw entries (tag 0) + applicable Hnd terms
-      if (dim_dw < ((int64_t)1 << 24) && f.nterms < 127) {
-        const HostMergedList m = merge_dw_lists(dw, f, dw_first, dw_count, dim_dw);
-        if (dev_upload(&s->d_mx_rowptr, m.rowptr.data(), m.rowptr.size()) || dev_upload(&s->d_mx_col, m.col.data(), m.col.size()) ||
-            dev_upload(&s->d_mx_val, m.val.data(), m.val.size()))
-          return 1;
-      }
-    }
-    s->h_hd = std::move(built->hd);
-    s->h_nd = std::move(built->nd);
-  } else {
-    if (dev_upload(&s->d_hd, hd, (size_t)s->nloc)) return 1;
-    if (s->has_nd && upload_csr(s->nd, s->nloc, nd_rowptr, nd_col, nd_val, 0)) return 1;
-    // Hnd as its own SELL pass after the panel sweep (global columns): keeps the row kernel free of the CSR
-    // row pointers and lets the Lanczos step stay fused (the dot partials move to this last pass)
-    if (s->has_nd && !sw.nd_in_rows &&
-        upload_sell(s->nd, s->nloc, dim_up * dim_dw, nd_rowptr, nd_col, nd_val, 0, false, sw, 16.0))
-      return 1;
-  }
-  if (s->panel_mode == 2) {
-    // per-row lists of the tiled sweep, with the factored Hnd terms when the merged list above exists
-    const HostFactored* f = (s->factored && built) ? &built->fac : nullptr;
-    const bool with_nd = f && f->nterms > 0 && s->d_mx_rowptr != nullptr;
-    const HostTileLists l = build_tile_lists(dw, dim_dw, dw_first, dw_count, tile_starts, with_nd ? f : nullptr);
-    s->tile_list_cap = l.list_cap;
-    const std::vector<HostInt4> meta = tile_meta_live(l, dw_first);  // the kernel gathers the live outside entries only
-    if (dev_upload(&s->d_tile_lbeg, l.lbeg.data(), l.lbeg.size()) || dev_upload(&s->d_tl_meta, as_int4(meta), meta.size()) ||
-        dev_upload(&s->d_tl_col, l.col.data(), l.col.size()) || dev_upload(&s->d_tl_val, l.val.data(), l.val.size()))
-      return 1;
-    s->tl_has_nd = l.has_nd ? 1 : 0;
-  }
-  // Impurity-block image (host_ib.hpp, kernels_ib.hip): whole sectors built from a model whose hops connect impurity
-  // levels with single bath levels (normal / hybrid baths), <= 3 orbitals.  The device-resident Lanczos loops then run
-  // on its padded 16-column panel layout and its two kernels.  Measured (r3): 0.61 against 0.85 ms per product at
-  // Ns = 15, 2.4 against 3.3 ms at Ns = 16, but 0.18 against 0.13 ms on config 2, whose 27 KB rows leave the generic
-  // row kernel four workgroups per CU -- so the default takes it for rows of more than Switches::ib_min_row_bytes()
-  // (40 KB) in sectors of at least Switches::ib_min elements (tests force it on small ones with 0, which also lifts the
-  // row gate).
-  if (s->factored && built && built->norb > 0 && dw_first == 0 && dw_count == dim_dw) {
-    const int64_t min_rows = sw.ib_min;
-    // Replica / general baths (hops between the bath levels of a replica, host_ib.hpp IbSide::pmask): the image and its
-    // kernels hold them as pair hops of whole blocks -- tested, golden-pinned -- but every lane runs through every pair
-    // (half of them idle), which costs as much as the walk over the levels: measured on the 3-orbital x 4-replica sector
-    // of Ns = 15 the product takes 1.16 ms on the blocks against 0.81 ms on the generic kernels.  So the default keeps
-    // such sectors on the generic kernels; Switches::ib_pairs (or ib_min == 0, the tests) takes the image.
-    bool pairs = false;
-    for (int sp = 0; sp < 2 && !pairs; sp++) {
-      const std::vector<double>& a = built->ob_a[sp];
-      const int ns = built->ns;
-      if ((int)a.size() == ns * ns)
-        for (int p = built->norb; p < ns && !pairs; p++)
-          for (int q = p + 1; q < ns; q++)
-            if (a[(size_t)p * ns + q] != 0.0) {
-              pairs = true;
-              break;
-            }
-    }
-    const bool pairs_ok = !pairs || min_rows == 0 || sw.ib_pairs;
-    // Rows below ib_min_row_bytes(): the block ROWS kernels lose to the generic LDS row kernel there; the image is still built
-    // when that kernel can take the rows half on the image's layout (setup_pos_rows), and dropped again when it cannot.
-    const bool short_rows = dim_up * 8 < sw.ib_min_row_bytes();
-    if (sw.ib && pairs_ok && s->nloc >= min_rows && (!short_rows || sw.posrows) && !sw.lanczos_unfused && setup_ib(s, *built))
-      return 1;
-    if (s->ib && short_rows && !s->ib->pr.on) {
-      free_ib(s->ib);
-      delete s->ib;
-      s->ib = nullptr;
-    }
-  }
-  // Panel-major vector layout for the device-resident Lanczos loop (normal_args.hpp): large
-  // factored whole sectors whose rows fit the LDS row kernel.  Default: 128-column panels (1 KiB line-aligned segments)
-  // swept by the LDS-tiled kernel -- measured 6 % (config 2), 14 % (Ns = 15) and 8 % (Ns = 16) faster per product than
-  // the same kernel on the natural layout, whose segments start at arbitrary 8-byte offsets.  Panels of 16 / 32 / 64
-  // columns (Switches::blocked_w) take the narrow-panel sweep (normal_dw_blk_kernel: panels that stay in one L2, fetch
-  // traffic 1.1-1.9x of V + result instead of 1.8-5x, but bound by the L2's gather throughput and 10-60 % slower: an
-  // experiment that is kept, tested, off).
-  if (!s->ib && s->factored && built && dw_first == 0 && dw_count == dim_dw && s->rows_per_block >= 1 && s->row_split == 1 &&
-      dim_dw <= 65535 && dim_up >= 64) {
-    const bool on = sw.blocked;
-    const int64_t min_rows = sw.blocked_min;
-    const int shift = sw.blocked_shift();
-    const HostFactored& f = built->fac;
-    if (on && shift == 7 && s->nloc >= min_rows && s->panel_mode == 2 && (f.nterms == 0 || s->tl_has_nd)) {
-      // 128-column panels: the tiled sweep and its lists as they are, on line-aligned contiguous panels
-      s->blk_shift = 7;
-      s->blk_tail_balance = sw.tile_balance;
-      s->blk_rows = s->tile_rows;
-      s->blk_ps = dim_dw << 7;
-      s->blk_len = ((dim_up + 127) >> 7) * s->blk_ps;
-    } else if (on && shift && shift < 7 && s->nloc >= min_rows && f.nterms <= 16) {
-      // narrow panels: lists over LDS blocks of Switches::blocked_lds_kb KiB of staged segments
-      const HostBlockLists b = build_block_lists(dw, f, dim_dw, shift, sw.blocked_lds_kb);
-      if (b.fits) {
-        s->blk_list_cap = b.list_cap;
-        if (dev_upload(&s->d_bl_lend, b.lend.data(), b.lend.size()) || dev_upload(&s->d_bl_meta, as_int4(b.meta), b.meta.size()) ||
-            dev_upload(&s->d_bl_ent, b.ent.data(), b.ent.size()) || dev_upload(&s->d_bl_wtab, b.wtab.data(), b.wtab.size()))
-          return 1;
-        s->blk_shift = shift;
-        s->blk_rows = b.rows;
-        s->blk_ps = dim_dw << shift;
-        s->blk_len = ((dim_up + ((int64_t)1 << shift) - 1) >> shift) * s->blk_ps;
-      }
-    }
-  }
-  return finish_handle(s);
-}
-
-// split a local-row CSR with global columns into shard-local and non-local blocks
-static int setup_flat(edigpu_sector* s, int64_t nrow_local, int64_t ncol_global, int64_t row_first,
-                      const int64_t* rowptr, const int32_t* col, const double* val, int cplx) {
-  s->kind = 1;
-  s->is_complex = cplx;
-  s->device = g_device;
-  s->dim = ncol_global;
-  s->nloc = nrow_local;
-  s->row_first = row_first;
-  const int w = cplx ? 2 : 1;
-  const int64_t lo = row_first, hi = row_first + nrow_local;
-  std::vector<int64_t> rpl((size_t)nrow_local + 1, 0), rpn((size_t)nrow_local + 1, 0);
-  for (int64_t i = 0; i < nrow_local; i++) {
-    int64_t nl = 0;
-    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; k++)
-      if (col[k] >= lo && col[k] < hi) nl++;
-    rpl[i + 1] = rpl[i] + nl;
-    rpn[i + 1] = rpn[i] + (rowptr[i + 1] - rowptr[i] - nl);
-  }
-  std::vector<int32_t> cl((size_t)rpl[nrow_local]), cn((size_t)rpn[nrow_local]);
-  std::vector<double> vl((size_t)rpl[nrow_local] * w), vn((size_t)rpn[nrow_local] * w);
-  for (int64_t i = 0; i < nrow_local; i++) {
-    int64_t pl = rpl[i], pn = rpn[i];
-    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; k++) {
-      if (col[k] >= lo && col[k] < hi) {
-        cl[pl] = (int32_t)(col[k] - lo);
-        for (int q = 0; q < w; q++) vl[pl * w + q] = val[k * w + q];
-        pl++;
-      } else {
-        cn[pn] = col[k];
-        for (int q = 0; q < w; q++) vn[pn * w + q] = val[k * w + q];
-        pn++;
-      }
-    }
-  }
-  if (upload_csr(s->loc, nrow_local, rpl.data(), cl.data(), vl.data(), cplx)) return 1;
-  if (upload_csr(s->nonloc, nrow_local, rpn.data(), cn.data(), vn.data(), cplx)) return 1;
-  if (upload_sell(s->loc, nrow_local, nrow_local, rpl.data(), cl.data(), vl.data(), cplx, true, s->sw)) return 1;
-  if (upload_sell(s->nonloc, nrow_local, ncol_global, rpn.data(), cn.data(), vn.data(), cplx, false, s->sw)) return 1;
-  return finish_handle(s);
-}
-
-// ed_total_ud = F sector: factor matrices as ELL ([slot][row] per axis, padding col = own row, val = 0),
-// diagonal explicit (hd != null) or as per-axis tables + impurity table
-static int setup_orbs(edigpu_sector* s, const HostOrbs& ho, const double* hd) {
-  s->kind = 3;
-  s->is_complex = 0;
-  s->device = g_device;
-  s->dim = s->nloc = ho.dim;
-  s->row_first = 0;
-  OrbsArgs& a = s->orbs;
-  a = OrbsArgs();
-  a.naxes = ho.naxes;
-  a.dim = ho.dim;
-  std::vector<int32_t> ecol;
-  std::vector<double> eval, eax;
-  std::vector<uint8_t> imp;
-  int64_t stride = 1;
-  for (int k = 0; k < ho.naxes; k++) {
-    const int64_t d = ho.dims[k];
-    a.dims[k] = d;
-    a.stride[k] = stride;
-    stride *= d;
-    const HostCsr& f = ho.fac[k];
-    int w = 0;
-    for (int64_t i = 0; i < d; i++) w = std::max<int>(w, (int)(f.rowptr[i + 1] - f.rowptr[i]));
-    a.width[k] = w;
-    a.elloff[k] = (int64_t)ecol.size();
-    const size_t base = ecol.size();
-    ecol.resize(base + (size_t)w * d);
-    eval.resize(base + (size_t)w * d, 0.0);
-    for (int sl = 0; sl < w; sl++)
-      for (int64_t i = 0; i < d; i++) ecol[base + (size_t)sl * d + i] = (int32_t)i;
-    for (int64_t i = 0; i < d; i++) {
-      int sl = 0;
-      for (int64_t q = f.rowptr[i]; q < f.rowptr[i + 1]; q++, sl++) {
-        ecol[base + (size_t)sl * d + i] = f.col[q];
-        eval[base + (size_t)sl * d + i] = f.val[q];
-      }
-    }
-    a.off[k] = (int)eax.size();
-    if (!hd) {
-      eax.insert(eax.end(), ho.eax[k].begin(), ho.eax[k].end());
-      imp.insert(imp.end(), ho.impbit[k].begin(), ho.impbit[k].end());
-    }
-  }
-  if (ecol.empty()) {  // no off-diagonal element at all: keep valid pointers
-    ecol.push_back(0);
-    eval.push_back(0.0);
-  }
-  int32_t* dcol = nullptr;
-  double *dval = nullptr, *dhd = nullptr, *deax = nullptr, *dx = nullptr;
-  uint8_t* dimp = nullptr;
-  if (dev_upload(&dcol, ecol.data(), ecol.size())) return 1;
-  a.ell_col = dcol;
-  if (dev_upload(&dval, eval.data(), eval.size())) return 1;
-  a.ell_val = dval;
-  if (hd) {
-    if (dev_upload(&dhd, hd, (size_t)ho.dim)) return 1;
-    a.hd = dhd;
-  } else {
-    if (dev_upload(&deax, eax.data(), eax.size())) return 1;
-    a.eax = deax;
-    if (dev_upload(&dimp, imp.data(), imp.size())) return 1;
-    a.impbit = dimp;
-    if (dev_upload(&dx, ho.xtab.data(), ho.xtab.size())) return 1;
-    a.xtab = dx;
-  }
-  s->h_orbs_fac = ho.fac;
-  return finish_handle(s);
-}
-
-// Stored flat image generated on the device from the on-the-fly description (kernels_build.hip).
-// Returns 0 = built, 2 = not applicable (caller falls back to the host CSR builder), 1 = error.
-static int build_flat_on_device(edigpu_sector* s, const HostDirect& hd) {
-  const int nterms = (int)hd.terms.size();
-  const int64_t nrow = hd.row_count;
-  if (nrow == 0 || hd.dim >= ((int64_t)1 << 24)) return 2;  // 24-bit columns in the packed words
-  // ---- value dictionary: ids (2j, 2j+1) = (+v_j, -v_j), j >= 1; ids 0, 1 = 0.0 (padding) ----
-  std::vector<double> dict(4, 0.0);
-  std::vector<uint8_t> vid((size_t)2 * std::max(nterms, 1), 0);
-  auto id_of = [&](double re, double im) -> int {
-    const size_t n = dict.size() / 2;
-    for (size_t k = 2; k < n; k++)
-      if (dict[2 * k] == re && dict[2 * k + 1] == im) return (int)k;
-    if (n + 2 > 256) return -1;
-    dict.push_back(re);
-    dict.push_back(im);
-    dict.push_back(-re);
-    dict.push_back(-im);
-    return (int)n;
-  };
-  for (int t = 0; t < nterms; t++) {
-    const DirectTerm& tm = hd.terms[t];
-    const int f = id_of(tm.cre, tm.cim);
-    const int r = tm.pair ? id_of(tm.c2re, tm.c2im) : f;
-    if (f < 0 || r < 0) return 2;
-    vid[2 * t] = (uint8_t)f;
-    vid[2 * t + 1] = (uint8_t)r;
-  }
-  dict.resize(512, 0.0);
-  // ---- temporaries on the device (the direct image + work arrays) ----
-  struct Tmp {
-    int32_t *states = nullptr, *offdw = nullptr, *rkup = nullptr, *wl = nullptr, *wn = nullptr;
-    DirectTerm* terms = nullptr;
-    uint8_t* vid = nullptr;
-    double *dtab = nullptr, *xtab = nullptr;
-    unsigned long long* totals = nullptr;
-    ~Tmp() {
-      dev_free(states); dev_free(offdw); dev_free(rkup); dev_free(wl); dev_free(wn);
-      dev_free(terms); dev_free(vid); dev_free(dtab); dev_free(xtab); dev_free(totals);
-    }
-  } t;
-  const int64_t nslice = (nrow + 63) / 64;
-  int rc = dev_upload(&t.states, hd.states.data(), hd.states.size());
-  rc |= dev_upload(&t.offdw, hd.off_dw.data(), hd.off_dw.size());
-  rc |= dev_upload(&t.rkup, hd.rk_up.data(), hd.rk_up.size());
-  if (nterms) rc |= dev_upload(&t.terms, hd.terms.data(), hd.terms.size());
-  rc |= dev_upload(&t.vid, vid.data(), vid.size());
-  rc |= dev_upload(&t.dtab, hd.dtab.data(), hd.dtab.size());
-  rc |= dev_upload(&t.xtab, hd.xtab.data(), hd.xtab.size());
-  if (rc) return 1;
-  EDIGPU_HIP(hipMalloc((void**)&t.wl, (size_t)nslice * sizeof(int32_t)));
-  EDIGPU_HIP(hipMalloc((void**)&t.wn, (size_t)nslice * sizeof(int32_t)));
-  EDIGPU_HIP(hipMalloc((void**)&t.totals, 4 * sizeof(unsigned long long)));
-  EDIGPU_HIP(hipMemset(t.totals, 0, 4 * sizeof(unsigned long long)));
-  BuildArgs a;
-  a.nrow = nrow;
-  a.row_first = hd.row_first;
-  a.lo = hd.row_first;
-  a.hi = hd.row_first + nrow;
-  a.ns = hd.ns;
-  a.norb = hd.norb;
-  a.nterms = nterms;
-  a.states = t.states;
-  a.off_dw = t.offdw;
-  a.rk_up = t.rkup;
-  a.terms = t.terms;
-  a.vid = t.vid;
-  a.dtab = t.dtab;
-  a.xtab = t.xtab;
-  if (launch_build_count(a, t.wl, t.wn, t.totals, nullptr)) return 1;
-  std::vector<int32_t> wl((size_t)nslice), wn((size_t)nslice);
-  unsigned long long tot[4];
-  EDIGPU_HIP(hipMemcpy(wl.data(), t.wl, wl.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  EDIGPU_HIP(hipMemcpy(wn.data(), t.wn, wn.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  EDIGPU_HIP(hipMemcpy(tot, t.totals, sizeof(tot), hipMemcpyDeviceToHost));
-  const int maxl = (int)(tot[2] & 0xFFFFFFFFull), maxn = (int)(tot[3] & 0xFFFFFFFFull);
-  if (maxl > 160 || maxn > 160) return 2;  // rows too long for the LDS sort buffers
-  auto finish = [&](DevCsr& d, const std::vector<int32_t>& w, int64_t nent, int maxlen, int which) -> int {
-    d = DevCsr();
-    d.nrow = nrow;
-    d.nnz = nent + (which == 0 ? nrow : 0);  // the loc block also holds the diagonal
-    d.avg_row = (double)d.nnz / (double)nrow;
-    if (nent == 0 && which == 1) return 0;   // no non-local block on a single shard
-    std::vector<int32_t> sp((size_t)nslice + 1, 0);
-    int64_t acc = 0;
-    for (int64_t k = 0; k < nslice; k++) {
-      acc += w[k];
-      if (acc >= ((int64_t)1 << 31) / 64) return 2;
-      sp[k + 1] = (int32_t)acc;
-    }
-    if (nent > 0 && (double)acc * 64.0 > 1.6 * (double)nent) return 2;  // too ragged for SELL
-    d.sell = 1;
-    d.sell_packed = 1;
-    d.nslice = nslice;
-    if (dev_upload(&d.sell_ptr, sp.data(), sp.size())) return 1;
-    if (dev_upload(&d.sell_dict, dict.data(), dict.size())) return 1;
-    EDIGPU_HIP(hipMalloc((void**)&d.sell_pk, (size_t)std::max<int64_t>(acc, 1) * 64 * sizeof(uint32_t)));
-    if (which == 0) EDIGPU_HIP(hipMalloc((void**)&d.sell_diag, (size_t)nrow * 2 * sizeof(double)));
-    return launch_build_fill(a, which, maxlen, d.sell_ptr, d.sell_pk, d.sell_diag, nullptr);
-  };
-  int r0 = finish(s->loc, wl, (int64_t)tot[0], maxl, 0);
-  if (r0) return r0;
-  int r1 = finish(s->nonloc, wn, (int64_t)tot[1], maxn, 1);
-  if (r1) return r1;
-  EDIGPU_HIP(hipDeviceSynchronize());
-  return 0;
-}
-
-static int ensure_workspace(edigpu_sector* s) {
-  const int64_t len = s->nloc * (s->is_complex ? 2 : 1);
-  if (s->d_vin && s->ws_len == len) return 0;
-  dev_free(s->d_vin);
-  dev_free(s->d_vout);
-  dev_free(s->d_tmp);
-  dev_free(s->d_partial);
-  dev_free(s->d_scal);
-  // (the panel-major layout of the Lanczos loop pads the last panel: blk_len >= len)
-  const size_t n = (size_t)std::max<int64_t>(std::max(std::max(len, s->blk_len), s->ib ? s->ib->len : 0), 1);
-  EDIGPU_HIP(hipMalloc((void**)&s->d_vin, n * sizeof(double)));
-  EDIGPU_HIP(hipMalloc((void**)&s->d_vout, n * sizeof(double)));
-  EDIGPU_HIP(hipMalloc((void**)&s->d_tmp, n * sizeof(double)));
-  if (s->ib && s->ib->ps != s->ib->dim_dw * kIbPanel) {
-    // padded panel stride (EDIGPU_IB_PSPAD): the doubles between two panels are never written by a kernel and are part of
-    // the vector sums -- they must be zero
-    EDIGPU_HIP(hipMemset(s->d_vin, 0, n * sizeof(double)));
-    EDIGPU_HIP(hipMemset(s->d_vout, 0, n * sizeof(double)));
-    EDIGPU_HIP(hipMemset(s->d_tmp, 0, n * sizeof(double)));
-  }
-  // per-workgroup partials: three per 256-row workgroup of the SELL dot epilogue is the largest user
-  s->partial_cap = std::max<int64_t>(kMaxPartials, 3 * ((s->nloc + 255) / 256) + 64);
-  EDIGPU_HIP(hipMalloc((void**)&s->d_partial, (size_t)s->partial_cap * sizeof(double)));
-  s->ws_len = len;
-  return 0;
-}
-
-static int apply_eph_operator(const edigpu_sector* s, const double* v, double* hv, int w, hipStream_t st);
-static int apply_any(edigpu_sector* s, const double* v_local, const double* v_full, double* hv,
-                     int phase, hipStream_t st) {
-  if (s->kind == 4) {
-    // _CMPLX_NORMAL: (S + iA)(xr + i xi) = (S xr - A xi) + i (S xi + A xr) on planar work vectors
-    if (phase != 3) {
-      set_error("complex normal-mode sectors are single-shard: use the fused product");
-      return 1;
-    }
-    // one real product on the doubled up index (interleaved complex = real vectors of that sector)
-    if (s->sub_d) return apply_any(s->sub_d, v_full, v_full, hv, 3, st);
-    const int64_t n = s->dim;
-    double *xr = s->d_cz, *xi = xr + n, *yr = xi + n, *yi = yr + n, *t1 = yi + n, *t2 = t1 + n;
-    if (launch_deinterleave(n, v_full, xr, xi, st)) return 1;
-    if (apply_any(s->sub_s, xr, xr, yr, 3, st) || apply_any(s->sub_s, xi, xi, yi, 3, st)) return 1;
-    if (s->sub_a && (apply_any(s->sub_a, xi, xi, t1, 3, st) || apply_any(s->sub_a, xr, xr, t2, 3, st))) return 1;
-    return launch_combine_interleave(n, yr, yi, s->sub_a ? t1 : nullptr, s->sub_a ? t2 : nullptr, hv, st);
-  }
-  if (s->kind == 0 && s->nph > 0) {
-    // phonon branches: the electronic product on every phonon block, then the phonon / electron-phonon pass
-    if (phase != 3) {
-      set_error("phonon sectors are single-shard: use the fused product");
-      return 1;
-    }
-    for (int iph = 0; iph <= s->nph; iph++) {
-      const int64_t o = (int64_t)iph * s->dim_el;
-      if (launch_normal(s, v_local + o, v_full + o, hv + o, 3, st)) return 1;
-    }
-    if (launch_phonon(s, v_full, hv, st)) return 1;
-    return apply_eph_operator(s, v_full, hv, 1, st);
-  }
-  if (s->kind == 0) return launch_normal(s, v_local, v_full, hv, phase, st);
-  if ((s->kind == 1 || s->kind == 2) && s->nph > 0) {
-    // phonon branches of the superc / nonsu2 products: electronic product per phonon block, then the phonon pass
-    if (phase != 3 || s->nloc != s->dim) {
-      set_error("phonon sectors: whole sectors take the fused product, row shards edigpu_apply_sharded_* / "
-                "edigpu_lanczos_tridiag_sharded");
-      return 1;
-    }
-    for (int iph = 0; iph <= s->nph; iph++) {
-      const int64_t o = 2 * (int64_t)iph * s->dim_el;
-      if (s->kind == 2) {
-        if (launch_direct(s, v_full + o, hv + o, st)) return 1;
-      } else if (launch_csr(s->loc, 1, v_full + o, hv + o, 0, st)) {
-        return 1;
-      }
-    }
-    if (launch_phonon(s, v_full, hv, st)) return 1;
-    return apply_eph_operator(s, v_full, hv, 2, st);
-  }
-  if (s->kind == 3) {
-    // ed_total_ud = F.  Whole sector: phase 1 = everything, phase 2 = nothing left to add.  Row shard
-    // (edigpu_orbs_build_rows): like the on-the-fly sectors the whole product needs the gathered vector.
-    if (s->nloc == s->dim) {
-      if (phase == 2) return 0;
-      return launch_orbs(s, v_full, hv, st);
-    }
-    if (phase == 1) return launch_zero(hv, s->nloc, st);
-    return launch_orbs(s, v_full, hv, st);
-  }
-  if (s->kind == 2) {
-    // on-the-fly: like directMatVec_MPI_* the whole product needs the gathered vector
-    // (reference ED_NONSU2/ED_HAMILTONIAN_NONSU2_DIRECT_HxV.f90:220-223: gather first, then compute)
-    if (phase == 1) return launch_zero(hv, s->nloc * 2, st);
-    return launch_direct(s, v_full, hv, st);
-  }
-  // flat: loc block then non-local block
-  if (phase & 1) {
-    if (launch_csr(s->loc, s->is_complex, v_local, hv, 0, st)) return 1;
-  }
-  if (phase & 2) {
-    if (launch_csr(s->nonloc, s->is_complex, v_full, hv, 1, st)) return 1;
-  }
-  return 0;
-}
-
-// One electronic block of a superc / nonsu2 phonon handle (the sharded product: edigpu_shard.hip): phase 1 = the part
-// that needs the rows' own elements only, phase 2 = the part that needs the gathered block
-int apply_flat_block(edigpu_sector* s, const double* v_local, const double* v_full, double* hv, int phase, hipStream_t st) {
-  if (s->kind == 2) {
-    if (phase == 1) return launch_zero(hv, s->dim_el * 2, st);
-    return launch_direct(s, v_full, hv, st);
-  }
-  if (phase == 1) return launch_csr(s->loc, s->is_complex, v_local, hv, 0, st);
-  return launch_csr(s->nonloc, s->is_complex, v_full, hv, 1, st);
-}
-
-// general g_ph(a,b): t = O v[jph] with the electron-phonon operator as its own sector handle (sub_a), then
-// hv[jph+1] += sqrt(jph+1) t, hv[jph-1] += sqrt(jph) t   (stored/H_e_ph.f90 x (b + b^+); w = doubles per element)
-static int apply_eph_operator(const edigpu_sector* s, const double* v, double* hv, int w, hipStream_t st) {
-  if (!s->sub_a) return 0;
-  const int64_t n = s->dim_el * w;
-  for (int jph = 0; jph <= s->nph; jph++) {
-    if (apply_any(s->sub_a, v + jph * n, v + jph * n, s->d_cz, 3, st)) return 1;
-    double* up = jph < s->nph ? hv + (jph + 1) * n : nullptr;
-    double* dn = jph > 0 ? hv + (jph - 1) * n : nullptr;
-    if (launch_eph_scatter(n, s->d_cz, up, sqrt((double)(jph + 1)), dn, sqrt((double)jph), st)) return 1;
-  }
-  return 0;
-}
-
-static int single_shard(const edigpu_sector* s, const char* who) {
-  if (s->nloc != s->dim) {
-    set_error(std::string(who) + ": handle is a shard (local rows != global dim); use the _dev entry points");
-    return 1;
-  }
-  return 0;
-}
-
-// symmetric tridiagonal eigen-decomposition (implicit QL).  d: diagonal (n), e: sub-diagonal
-// e[1..n-1] (e[0] unused).  On return d holds eigenvalues, z (n*n, column-major) eigenvectors.
-static int tql2(int n, std::vector<double>& d, std::vector<double>& e, std::vector<double>& z) {
-  z.assign((size_t)n * n, 0.0);
-  for (int i = 0; i < n; i++) z[(size_t)i * n + i] = 1.0;
-  for (int i = 1; i < n; i++) e[i - 1] = e[i];
-  if (n > 0) e[n - 1] = 0.0;
-  for (int l = 0; l < n; l++) {
-    int iter = 0, m;
-    do {
-      for (m = l; m < n - 1; m++) {
-        const double dd = fabs(d[m]) + fabs(d[m + 1]);
-        if (fabs(e[m]) <= 2.3e-16 * dd) break;
-      }
-      if (m != l) {
-        if (iter++ == 200) return 1;
-        double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
-        double r = hypot(g, 1.0);
-        g = d[m] - d[l] + e[l] / (g + (g >= 0 ? fabs(r) : -fabs(r)));
-        double sn = 1.0, c = 1.0, p = 0.0;
-        int i;
-        for (i = m - 1; i >= l; i--) {
-          double f = sn * e[i], b = c * e[i];
-          e[i + 1] = (r = hypot(f, g));
-          if (r == 0.0) {
-            d[i + 1] -= p;
-            e[m] = 0.0;
-            break;
-          }
-          sn = f / r;
-          c = g / r;
-          g = d[i + 1] - p;
-          r = (d[i] - g) * sn + 2.0 * c * b;
-          d[i + 1] = g + (p = sn * r);
-          g = c * r - b;
-          for (int k = 0; k < n; k++) {
-            f = z[(size_t)(i + 1) * n + k];
-            z[(size_t)(i + 1) * n + k] = sn * z[(size_t)i * n + k] + c * f;
-            z[(size_t)i * n + k] = c * z[(size_t)i * n + k] - sn * f;
-          }
-        }
-        if (r == 0.0 && i >= l) continue;
-        d[l] -= p;
-        e[l] = g;
-        e[m] = 0.0;
-      }
-    } while (m != l);
-  }
-  return 0;
-}
-
-// enqueue one Lanczos step (iter is 0-based); vin/vout/tmp live in the workspace
-bool flat_lanczos_fusable(const edigpu_sector* s) {
-  if (s->sw.lanczos_unfused || s->nloc != s->dim || s->nloc == 0 || s->nph > 0) return false;
-  if (s->kind == 2) return true;
-  return s->kind == 1 && csr_lanczos_fusable(s->loc) && s->nonloc.nnz == 0;
-}
-
-// iter < 0: a later step (not the first) whose index the finalize kernel takes from the device-side counter -- the form
-// that can be captured once and replayed (lanczos_run)
-static int lanczos_step(edigpu_sector* s, int iter, int nlanc, hipStream_t st) {
-  const int64_t len = s->lz_len;
-  const bool later = iter != 0;
-  // (impurity-block image with rows staged in halves: rows_per_block == 0, but launch_ib_lanczos has a step for it)
-  const bool ib_split = s->kind == 0 && s->ib && s->ib->nhalf == 2 && s->lz_blocked;
-  if (normal_lanczos_fusable(s) || ib_split) {
-    // rotate (and the pending axpy) fused into the row kernel, alpha and <Q|Q> into the panel sweep
-    // (kernels_normal.hip); LoopSwitches::lanczos_exactbeta keeps the separate axpy+norm kernel
-    const bool exactbeta = s->lz.lanczos_exactbeta;
-    int np = 0;
-    bool finalized = false;
-    bool in_x = false;
-    if (launch_normal_lanczos(s, s->d_vin, s->d_vout, s->d_scal, s->d_partial, s->partial_cap, iter == 0, !exactbeta, st, &np,
-                              nlanc, &finalized, s->d_tmp, &in_x))
-      return 1;
-    if (in_x) std::swap(s->d_vin, s->d_tmp);  // the new Lanczos vector was written to the third buffer
-    if (finalized) return 0;  // the sweep's last workgroup wrote alpha, beta and the stop flag
-    if (exactbeta) {
-      if (lz_finalize_alpha(s->d_partial, np, s->d_scal, iter, nlanc, st)) return 1;
-      return lz_beta(s->d_vin, s->d_vout, len, s->d_partial, s->d_scal, iter, nlanc, st);
-    }
-    return lz_finalize_alpha_beta(s->d_vin, s->d_vout, len, s->d_partial, np, s->d_scal, iter, nlanc, st);
-  }
-  if (flat_lanczos_fusable(s)) {
-    // flat / direct sectors held whole on this GPU: rotate with the pending axpy, then Q += H*v with
-    // the alpha and <Q|Q> partials in the product's epilogue (no tmp vector, no separate dot kernels)
-    int np = 0;
-    if (later && lz_rotate_lazy(s->d_vin, s->d_vout, len, s->d_scal, st)) return 1;
-    if (s->kind == 2) {
-      if (launch_direct_lanczos(s, s->d_vin, s->d_vout, s->d_partial, s->partial_cap, &np, s->d_scal + SC_ALPHA, st)) return 1;
-    } else if (launch_csr_lanczos(s->loc, s->is_complex, s->d_vin, s->d_vout, s->d_partial, s->partial_cap, &np, s->d_scal + SC_ALPHA, st)) {
-      return 1;
-    }
-    return lz_finalize_alpha_beta(s->d_vin, s->d_vout, len, s->d_partial, np, s->d_scal, iter, nlanc, st);
-  }
-  // no fused product (ed_total_ud = F, phonon branches, complex normal mode, rows staged in column parts, shards): the
-  // product goes to its own buffer; the one-reduction recurrence around it -- lazy rotate with the pending axpy, Q += H P
-  // with the three sums, one finalize -- moves 8 vector passes per step where the literal form moves 11.  The three-sum
-  // beta (k_finalize_ab) is what makes this safe: with beta^2 = <w|w> - alpha^2 the same loop made the lowest Ritz value
-  // jitter at 6e-14 |H| (round 1, removed then).  LoopSwitches::lanczos_exactbeta / Switches::lanczos_unfused: the literal form.
-  auto product = [&]() -> int {  // tmp <- H vin, in the layout lanczos_prepare chose
-    return s->lz_blocked ? launch_normal_blocked(s, s->d_vin, s->d_tmp, st) : apply_any(s, s->d_vin, s->d_vin, s->d_tmp, 3, st);
-  };
-  if (s->sw.lanczos_unfused || s->lz.lanczos_exactbeta) {
-    if (iter > 0 && lz_rotate(s->d_vin, s->d_vout, len, s->d_scal, st)) return 1;
-    if (product()) return 1;
-    if (lz_alpha(s->d_vin, s->d_vout, s->d_tmp, len, s->d_partial, s->d_scal, iter, nlanc, st)) return 1;
-    return lz_beta(s->d_vin, s->d_vout, len, s->d_partial, s->d_scal, iter, nlanc, st);
-  }
-  int np = 0;
-  if (later && lz_rotate_lazy(s->d_vin, s->d_vout, len, s->d_scal, st)) return 1;
-  if (product()) return 1;
-  if (lz_add_dot3(s->d_vin, s->d_vout, s->d_tmp, len, s->d_scal, s->d_partial, &np, st)) return 1;
-  return lz_finalize_alpha_beta(s->d_vin, s->d_vout, len, s->d_partial, np, s->d_scal, iter, nlanc, st);
-}
-
-static int lanczos_prepare(edigpu_sector* s, int nlanc, double threshold, hipStream_t st) {
-  s->lz = LoopSwitches::sample();
-  // the recurrence of a large factored normal-mode sector runs on panel-major vectors (set-up decides, blk_shift)
-  // (the impurity-block image with rows staged in halves: rows_per_block == 0 there, its step is in launch_ib_lanczos)
-  const bool ib_whole = s->kind == 0 && s->ib && s->nph == 0 && s->nloc == s->dim && !s->sw.lanczos_unfused;
-  s->lz_blocked = s->kind == 0 && (s->blk_shift > 0 || s->ib) && s->nph == 0 &&
-                  (normal_lanczos_fusable(s) || (ib_whole && s->ib->nhalf == 2));
-  s->lz_len = s->lz_blocked ? (s->ib ? s->ib->len : s->blk_len) : s->ws_len;
-  const size_t ns = (size_t)SC_AB + 2 * (size_t)nlanc;
-  if (!s->d_scal || s->scal_cap < ns) {  // (kept across runs: a captured graph holds its address)
-    dev_free(s->d_scal);
-    s->scal_cap = 0;
-    EDIGPU_HIP(hipMalloc((void**)&s->d_scal, ns * sizeof(double)));
-    s->scal_cap = ns;
-  }
-  EDIGPU_HIP(hipMemsetAsync(s->d_scal, 0, ns * sizeof(double), st));
-  if (!s->d_lzcnt) EDIGPU_HIP(hipMalloc((void**)&s->d_lzcnt, 64));
-  EDIGPU_HIP(hipMemsetAsync(s->d_lzcnt, 0, 64, st));
-  EDIGPU_HIP(hipMemcpyAsync(s->d_scal + SC_THR, &threshold, sizeof(double), hipMemcpyHostToDevice, st));
-  EDIGPU_HIP(hipMemsetAsync(s->d_vout, 0, (size_t)s->lz_len * sizeof(double), st));
-  return 0;
-}
-
-// start vector of a recurrence into d_vin, in the layout lanczos_prepare chose: src = host or device vector in the
-// natural layout (ws_len doubles), or nullptr for seeded random numbers
-static int lanczos_seed(edigpu_sector* s, const double* src, uint64_t seed, hipStream_t st) {
-  double* dst = s->lz_blocked ? s->d_tmp : s->d_vin;
-  if (src) {
-    EDIGPU_HIP(hipMemcpyAsync(dst, src, (size_t)s->ws_len * sizeof(double), hipMemcpyDefault, st));
-  } else if (lz_fill_random(dst, s->ws_len, seed, st)) {
-    return 1;
-  }
-  if (s->lz_blocked && s->ib) {
-    if (vec_to_ib(s->ib, s->d_tmp, s->d_vin, st)) return 1;
-    if (s->ib->ps != s->ib->dim_dw * kIbPanel) {
-      // padded panel stride (Switches::ib_pspad): the doubles between two panels are written by no kernel and enter the vector
-      // sums; the two other buffers may hold anything there (d_tmp just held the vector in the reference's layout)
-      EDIGPU_HIP(hipMemsetAsync(s->d_tmp, 0, (size_t)s->ib->len * sizeof(double), st));
-      EDIGPU_HIP(hipMemsetAsync(s->d_vout, 0, (size_t)s->ib->len * sizeof(double), st));
-    }
-    return 0;
-  }
-  if (s->lz_blocked) return vec_to_blocked(s->d_tmp, s->d_vin, s->dim_up, s->dim_dw, s->blk_shift, st);
-  return 0;
-}
-
-// Steps [from, to) of the current recurrence.  Switches::lanczos_graph: the later steps of a small sector -- identical
-// launches once the step index lives on the device (k_finalize_ab, iter < 0) -- are captured once as a hipGraph of
-// kGraphSteps steps and replayed; the executable stays with the handle for the next run of the same length.
-// OPT-IN because it buys nothing here: measured on configs 1 / 3 / 4 (10.9 / 20.3 / 23.8 us per step with the graph,
-// 11.4 / 20.4 / 23.1 without), i.e. the three dependent kernels of a step are bound by their own dispatch-to-completion
-// latency on the device, not by host-side launch cost; fusing the finalize into the sweep's last workgroup is what would
-// shorten a small sector's step.
-static int lanczos_run(edigpu_sector* s, int from, int to, int nlanc, hipStream_t st) {
-  constexpr int kGraphSteps = 8;
-  int it = from;
-  if (it == 0 && it < to) {
-    if (lanczos_step(s, 0, nlanc, st)) return 1;
-    it = 1;
-  }
-  const bool eligible = s->sw.lanczos_graph && !s->sw.lanczos_unfused && !s->lz.lanczos_exactbeta && !s->lz_graph_failed &&
-                        s->nloc <= s->sw.lanczos_graph_max &&
-                        s->nph == 0 && s->kind != 4 && to - it >= kGraphSteps + (s->lz_graph ? 0 : 1);
-  if (eligible) {
-    if (s->lz_graph && (s->lz_graph_nlanc != nlanc || s->lz_graph_scal != s->d_scal || s->lz_graph_blocked != s->lz_blocked)) {
-      (void)hipGraphExecDestroy(s->lz_graph);
-      s->lz_graph = nullptr;
-    }
-    if (!s->lz_graph) {
-      // one uncaptured later step first: whatever the launchers set up lazily (function attributes, occupancy
-      // queries) happens outside the capture
-      if (lanczos_step(s, it, nlanc, st)) return 1;
-      it++;
-      hipGraph_t g = nullptr;
-      bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
-      for (int k = 0; ok && k < kGraphSteps; k++) ok = lanczos_step(s, -1, nlanc, st) == 0;
-      if (hipStreamEndCapture(st, &g) != hipSuccess) ok = false;
-      if (ok && g && hipGraphInstantiate(&s->lz_graph, g, nullptr, nullptr, 0) != hipSuccess) {
-        s->lz_graph = nullptr;
-        ok = false;
-      }
-      if (g) (void)hipGraphDestroy(g);
-      if (!ok) {
-        (void)hipGetLastError();
-        s->lz_graph = nullptr;
-        s->lz_graph_failed = true;  // plain launches from here on (the capture enqueued nothing)
-      } else {
-        s->lz_graph_k = kGraphSteps;
-        s->lz_graph_nlanc = nlanc;
-        s->lz_graph_scal = s->d_scal;
-        s->lz_graph_blocked = s->lz_blocked;
-      }
-    }
-    while (s->lz_graph && to - it >= s->lz_graph_k) {
-      EDIGPU_HIP(hipGraphLaunch(s->lz_graph, st));
-      it += s->lz_graph_k;
-    }
-  }
-  for (; it < to; it++)
-    if (lanczos_step(s, it, nlanc, st)) return 1;
-  return 0;
-}
-
-// a vector of the current recurrence (device, lz_len doubles) to a host or device buffer in the natural layout
-static int lanczos_fetch(edigpu_sector* s, const double* v, double* dst, hipStream_t st) {
-  if (s->lz_blocked) {
-    if (s->ib ? vec_from_ib(s->ib, v, s->d_tmp, st) : vec_from_blocked(v, s->d_tmp, s->dim_up, s->dim_dw, s->blk_shift, st)) return 1;
-    v = s->d_tmp;
-  }
-  EDIGPU_HIP(hipMemcpyAsync(dst, v, (size_t)s->ws_len * sizeof(double), hipMemcpyDefault, st));
-  return 0;
-}
-
 }  // namespace edigpu
 
 using namespace edigpu;
@@ -1289,584 +108,6 @@ int edigpu_init(int device) {
   }
   EDIGPU_HIP(hipSetDevice(device));
   g_device = device;
-  return 0;
-}
-
-int edigpu_normal_create(edigpu_handle* h, int64_t dim_up, int64_t dim_dw, int64_t dw_first,
-                         int64_t dw_count, const double* hd, const int64_t* up_rowptr,
-                         const int32_t* up_col, const double* up_val, const int64_t* dw_rowptr,
-                         const int32_t* dw_col, const double* dw_val, const int64_t* nd_rowptr,
-                         const int32_t* nd_col, const double* nd_val) {
-  if (!h) {
-    set_error("edigpu_normal_create: handle pointer is NULL");
-    return 1;
-  }
-  *h = nullptr;
-  if (ensure_device()) return 1;
-  const Switches sw = Switches::sample();
-  if (dim_up <= 0 || dim_dw <= 0 || dw_first < 0 || dw_count < 0 || dw_first + dw_count > dim_dw) {
-    set_error("edigpu_normal_create: inconsistent dimensions");
-    return 1;
-  }
-  if (dim_up * dim_dw >= ((int64_t)1 << 31)) {
-    set_error("edigpu_normal_create: sector dimension >= 2^31");
-    return 1;
-  }
-  if (!hd && dw_count > 0) {
-    set_error("edigpu_normal_create: hd is NULL");
-    return 1;
-  }
-  std::string e = check_csr(dim_up, dim_up, up_rowptr, up_col, "edigpu_normal_create(up)");
-  if (e.empty()) e = check_csr(dim_dw, dim_dw, dw_rowptr, dw_col, "edigpu_normal_create(dw)");
-  if (e.empty() && nd_rowptr)
-    e = check_csr(dim_up * dw_count, dim_up * dim_dw, nd_rowptr, nd_col, "edigpu_normal_create(nd)");
-  if (!e.empty()) {
-    set_error(e);
-    return 1;
-  }
-  HostCsr up, dw;
-  up.nrow = up.ncol = dim_up;
-  up.rowptr.assign(up_rowptr, up_rowptr + dim_up + 1);
-  up.col.assign(up_col, up_col + up_rowptr[dim_up]);
-  up.val.assign(up_val, up_val + up_rowptr[dim_up]);
-  dw.nrow = dw.ncol = dim_dw;
-  dw.rowptr.assign(dw_rowptr, dw_rowptr + dim_dw + 1);
-  dw.col.assign(dw_col, dw_col + dw_rowptr[dim_dw]);
-  dw.val.assign(dw_val, dw_val + dw_rowptr[dim_dw]);
-  // The arrays of an impurity model have the structure the library's own builder emits (separable diagonal, Hnd a short
-  // sum of signed partial permutations): recover it and run the factored kernels; anything else keeps the explicit
-  // image.
-  HostNormal hn;
-  bool fact = false;
-  {
-    if (sw.handover_factor && !sw.normal_explicit)
-      fact = factor_handover(dim_up, dim_dw, dw_first, dw_count, hd, nd_rowptr, nd_col, nd_val, 16, hn.fac);
-    if (fact) {  // the arrays as given stay on the host for edigpu_normal_export
-      const int64_t nloc = dim_up * dw_count;
-      hn.hd.assign(hd, hd + nloc);
-      if (nd_rowptr && nd_rowptr[nloc] > 0) {
-        hn.nd.nrow = nloc;
-        hn.nd.ncol = dim_up * dim_dw;
-        hn.nd.rowptr.assign(nd_rowptr, nd_rowptr + nloc + 1);
-        hn.nd.col.assign(nd_col, nd_col + nd_rowptr[nloc]);
-        hn.nd.val.assign(nd_val, nd_val + nd_rowptr[nloc]);
-      }
-    }
-  }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
-  if (setup_normal(s.get(), dim_up, dim_dw, dw_first, dw_count, hd, up, dw, nd_rowptr, nd_col, nd_val,
-                   fact ? &hn : nullptr)) {
-    edigpu_destroy(s.release());
-    return 1;
-  }
-  *h = s.release();
-  return 0;
-}
-
-static int csr_create_any(edigpu_handle* h, int64_t nrow_local, int64_t ncol_global,
-                          int64_t row_first, const int64_t* rowptr, const int32_t* col,
-                          const double* val, int cplx) {
-  if (!h) {
-    set_error("edigpu_csr_create: handle pointer is NULL");
-    return 1;
-  }
-  *h = nullptr;
-  if (ensure_device()) return 1;
-  const Switches sw = Switches::sample();
-  if (nrow_local < 0 || ncol_global <= 0 || row_first < 0 || row_first + nrow_local > ncol_global) {
-    set_error("edigpu_csr_create: inconsistent dimensions");
-    return 1;
-  }
-  if (ncol_global >= ((int64_t)1 << 31)) {
-    set_error("edigpu_csr_create: dimension >= 2^31");
-    return 1;
-  }
-  std::string e = check_csr(nrow_local, ncol_global, rowptr, col, "edigpu_csr_create");
-  if (!e.empty()) {
-    set_error(e);
-    return 1;
-  }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
-  if (setup_flat(s.get(), nrow_local, ncol_global, row_first, rowptr, col, val, cplx)) {
-    edigpu_destroy(s.release());
-    return 1;
-  }
-  *h = s.release();
-  return 0;
-}
-
-int edigpu_csr_create_d(edigpu_handle* h, int64_t nrow_local, int64_t ncol_global,
-                        int64_t row_first, const int64_t* rowptr, const int32_t* col,
-                        const double* val) {
-  return csr_create_any(h, nrow_local, ncol_global, row_first, rowptr, col, val, 0);
-}
-
-int edigpu_csr_create_z(edigpu_handle* h, int64_t nrow_local, int64_t ncol_global,
-                        int64_t row_first, const int64_t* rowptr, const int32_t* col,
-                        const double* val_re_im) {
-  return csr_create_any(h, nrow_local, ncol_global, row_first, rowptr, col, val_re_im, 1);
-}
-
-int edigpu_normal_build(edigpu_handle* h, const edigpu_model* model, int nup, int ndw,
-                        int64_t dw_first, int64_t dw_count) {
-  if (!h || !model) {
-    set_error("edigpu_normal_build: NULL argument");
-    return 1;
-  }
-  *h = nullptr;
-  if (ensure_device()) return 1;
-  const Switches sw = Switches::sample();
-  HostNormal hn;
-  // the O(Dim) explicit images (hd, Hnd CSR) are skipped when the kernels run on the factored tables
-  bool lazy = !sw.normal_explicit;
-  std::string e = build_normal(*model, nup, ndw, dw_first, dw_count, hn, !lazy, !sw.nd_no_merge);
-  if (e.empty() && lazy && hn.fac.nterms > 16) {
-    lazy = false;
-    e = build_normal(*model, nup, ndw, dw_first, dw_count, hn, true, !sw.nd_no_merge);
-  }
-  if (!e.empty()) {
-    set_error(e);
-    return 1;
-  }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
-  s->model = *model;
-  s->sec_a = nup;
-  s->sec_b = ndw;
-  s->built_by_library = true;
-  s->lazy_export = lazy;
-  if (setup_normal(s.get(), hn.dim_up, hn.dim_dw, hn.dw_first, hn.dw_count, lazy ? nullptr : hn.hd.data(), hn.up,
-                   hn.dw, (!lazy && hn.has_nd) ? hn.nd.rowptr.data() : nullptr, hn.nd.col.data(),
-                   hn.nd.val.data(), &hn)) {
-    edigpu_destroy(s.release());
-    return 1;
-  }
-  if (model->nph > 0) {
-    // phonon branches: (Nph + 1) electronic blocks per vector; density couplings only
-    if (s->dw_count != s->dim_dw) {
-      set_error("edigpu_normal_build: phonons (nph > 0) need the whole sector on one shard");
-      edigpu_destroy(s.release());
-      return 1;
-    }
-    // density couplings g_aa: per-row tables inside the phonon pass.  A general g_ab (GPHFILE in the reference):
-    // the whole electron-phonon operator as its own sector handle (apply_eph_operator), the tables stay zero.
-    const bool offd = eph_offdiagonal(*model);
-    std::vector<double> gu((size_t)hn.dim_up, 0.0), gd((size_t)hn.dim_dw, 0.0);
-    for (int64_t i = 0; !offd && i < hn.dim_up; i++)
-      for (int a = 0; a < model->norb; a++)
-        if ((hn.bup.states[i] >> a) & 1) gu[i] += model->g_ph[a * EDIGPU_MAXORB + a];
-    for (int64_t i = 0; !offd && i < hn.dim_dw; i++)
-      for (int a = 0; a < model->norb; a++)
-        if ((hn.bdw.states[i] >> a) & 1) gd[i] += model->g_ph[a * EDIGPU_MAXORB + a];
-    if (offd) {
-      const edigpu_model om = eph_operator_model(*model);
-      if (edigpu_normal_build(&s->sub_a, &om, nup, ndw, 0, -1) ||
-          hipMalloc((void**)&s->d_cz, (size_t)s->dim * sizeof(double)) != hipSuccess) {
-        if (g_err.empty()) set_error("edigpu_normal_build: electron-phonon operator: out of device memory");
-        edigpu_destroy(s.release());
-        return 1;
-      }
-    }
-    if (dev_upload(&s->d_gu, gu.data(), gu.size()) || dev_upload(&s->d_gd, gd.data(), gd.size())) {
-      edigpu_destroy(s.release());
-      return 1;
-    }
-    if (s->dim * (model->nph + 1) >= ((int64_t)1 << 31)) {
-      set_error("edigpu_normal_build: sector dimension x (Nph+1) >= 2^31");
-      edigpu_destroy(s.release());
-      return 1;
-    }
-    s->nph = model->nph;
-    s->w0_ph = model->w0_ph;
-    s->a_ph = model->a_ph;
-    s->dim_el = s->dim;
-    s->dim *= (model->nph + 1);
-    s->nloc = s->dim;
-  }
-  *h = s.release();
-  return 0;
-}
-
-int edigpu_normal_build_z(edigpu_handle* h, const edigpu_model* model, int nup, int ndw) {
-  if (!h || !model) {
-    set_error("edigpu_normal_build_z: NULL argument");
-    return 1;
-  }
-  *h = nullptr;
-  const Switches sw = Switches::sample();
-  if (model->ed_mode != 0) {
-    set_error("edigpu_normal_build_z: ed_mode must be normal");
-    return 1;
-  }
-  if (model->nph > 0) {
-    set_error("edigpu_normal_build_z: phonons are not supported with complex algebra");
-    return 1;
-  }
-  edigpu_handle hs = nullptr, ha = nullptr;
-  if (edigpu_normal_build(&hs, model, nup, ndw, 0, -1)) return 1;
-  bool any = false;
-  const edigpu_model mi = imag_part_model(*model, any);
-  if (any && edigpu_normal_build(&ha, &mi, nup, ndw, 0, -1)) {
-    edigpu_destroy(hs);
-    return 1;
-  }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
-  s->kind = 4;
-  s->is_complex = 1;
-  s->device = g_device;
-  s->dim = s->nloc = hs->dim;
-  s->dim_up = hs->dim_up;
-  s->dim_dw = hs->dim_dw;
-  s->model = *model;
-  s->sec_a = nup;
-  s->sec_b = ndw;
-  s->built_by_library = true;
-  s->sub_s = hs;
-  s->sub_a = ha;
-  // The complex operator as one real sector on the doubled up index: one pass over 2 Dim elements instead of four
-  // real products and two layout passes.  Switches::cmplx_fourproducts, or more than 16 factored terms (complex replica
-  // matrices with many imaginary inter-orbital hops), keep the composite above.
-  if (!sw.cmplx_fourproducts && !sw.normal_explicit) {
-    HostNormal hd2;
-    const std::string e2 = build_normal_doubled(*model, nup, ndw, hd2, 16, !sw.nd_no_merge);
-    if (e2.empty()) {
-      std::unique_ptr<edigpu_sector> sd(new edigpu_sector(sw));
-      if (setup_normal(sd.get(), hd2.dim_up, hd2.dim_dw, 0, hd2.dim_dw, nullptr, hd2.up, hd2.dw, nullptr, nullptr, nullptr,
-                       &hd2)) {
-        edigpu_destroy(sd.release());
-        edigpu_destroy(s.release());
-        return 1;
-      }
-      s->sub_d = sd.release();
-    }
-  }
-  if (!s->sub_d &&  // planar work vectors of the four-product composite
-      hipMalloc((void**)&s->d_cz, (size_t)6 * (size_t)std::max<int64_t>(s->dim, 1) * sizeof(double)) != hipSuccess) {
-    set_error("edigpu_normal_build_z: out of device memory");
-    edigpu_destroy(s.release());
-    return 1;
-  }
-  if (finish_handle(s.get())) {
-    edigpu_destroy(s.release());
-    return 1;
-  }
-  *h = s.release();
-  return 0;
-}
-
-// phonon branches for a library-built superc / nonsu2 handle: g_el per row from the map of the rows it holds.  A row
-// shard holds the same rows of every phonon block (dim_el = its electronic rows, the local block stride; the layout
-// of spMatVec_mpi_superc_main / _nonsu2_main, i = i_el + (iph - 1) * MpiQ) and serves the sharded library calls only.
-static int attach_phonons_flat(edigpu_sector* s, const edigpu_model& m, const std::vector<int32_t>& states, int ns) {
-  if (m.nph <= 0) return 0;
-  if (s->dim * (m.nph + 1) >= ((int64_t)1 << 31)) {
-    set_error("sector dimension x (Nph+1) >= 2^31");
-    return 1;
-  }
-  const bool offd = eph_offdiagonal(m);
-  if (offd && s->nloc != s->dim) {
-    set_error("phonons with a general g_ph(a,b) need the whole sector on one shard (density couplings shard)");
-    return 1;
-  }
-  if (offd) {
-    // general g_ab: the electron-phonon operator as a sector handle of the same kind (apply_eph_operator)
-    const edigpu_model om = eph_operator_model(m);
-    const int rc = s->kind == 2 ? edigpu_direct_build(&s->sub_a, &om, s->sec_a, 0, -1)
-                                : edigpu_flat_build(&s->sub_a, &om, s->sec_a, 0, -1);
-    if (rc) return 1;
-    if (hipMalloc((void**)&s->d_cz, (size_t)2 * (size_t)s->dim * sizeof(double)) != hipSuccess) {
-      set_error("electron-phonon operator: out of device memory");
-      return 1;
-    }
-  }
-  std::vector<double> gel(states.size(), 0.0);
-  for (size_t i = 0; !offd && i < states.size(); i++)
-    for (int a = 0; a < m.norb; a++)
-      gel[i] += m.g_ph[a * EDIGPU_MAXORB + a] * (double)(((states[i] >> a) & 1) + ((states[i] >> (a + ns)) & 1));
-  if (dev_upload(&s->d_gu, gel.data(), gel.size())) return 1;
-  s->nph = m.nph;
-  s->w0_ph = m.w0_ph;
-  s->a_ph = m.a_ph;
-  s->dim_el = s->nloc;
-  s->dim *= (m.nph + 1);
-  s->nloc *= (m.nph + 1);
-  return 0;
-}
-
-}  // extern "C"
-namespace edigpu {
-// edigpu_flat_build / edigpu_flat_build_jz: the stored image, generated on the device unless Switches::flat_hostbuild
-static int flat_build_common(edigpu_handle* h, const edigpu_model* model, int sector, int64_t row_first, int64_t row_count,
-                             bool jz, int twojz) {
-  if (!h || !model) {
-    set_error("edigpu_flat_build: NULL argument");
-    return 1;
-  }
-  *h = nullptr;
-  if (ensure_device()) return 1;
-  const Switches sw = Switches::sample();
-  if (jz && model->nph > 0) {
-    set_error("edigpu_flat_build_jz: phonon sectors are not built in the Jz basis");
-    return 1;
-  }
-  if (!sw.flat_hostbuild) {
-    // generate the stored image on the device from the on-the-fly description (kernels_build.hip);
-    // the host CSR builder below is the fallback and what edigpu_csr_export materialises
-    HostDirect hd;
-    std::string e = build_direct(*model, sector, row_first, row_count, hd, jz, twojz, !sw.direct_nosort);
-    if (!e.empty()) {
-      set_error(e);
-      return 1;
-    }
-    if (hd.dim == 0) {
-      set_error("edigpu_flat_build: empty sector");
-      return 1;
-    }
-    std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
-    s->kind = 1;
-    s->is_complex = 1;
-    s->device = g_device;
-    s->dim = hd.dim;
-    s->nloc = hd.row_count;
-    s->row_first = hd.row_first;
-    s->model = *model;
-    s->sec_a = sector;
-    s->sec_b = jz ? twojz : 0;
-    s->jz = jz;
-    s->built_by_library = true;
-    s->lazy_export = true;
-    const int rc = build_flat_on_device(s.get(), hd);
-    if (rc == 0) {
-      if (attach_phonons_flat(s.get(), *model, hd.states, hd.ns)) {
-        edigpu_destroy(s.release());
-        return 1;
-      }
-      if (finish_handle(s.get())) {
-        edigpu_destroy(s.release());
-        return 1;
-      }
-      *h = s.release();
-      return 0;
-    }
-    edigpu_destroy(s.release());
-    if (rc == 1) return 1;
-  }
-  HostFlat hf;
-  std::string e = build_flat(*model, sector, row_first, row_count, hf, jz, twojz);
-  if (!e.empty()) {
-    set_error(e);
-    return 1;
-  }
-  if (hf.dim == 0) {
-    set_error("edigpu_flat_build: empty sector");
-    return 1;
-  }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
-  s->model = *model;
-  s->sec_a = sector;
-  s->sec_b = jz ? twojz : 0;
-  s->jz = jz;
-  s->built_by_library = true;
-  if (setup_flat(s.get(), hf.row_count, hf.dim, hf.row_first, hf.h.rowptr.data(), hf.h.col.data(),
-                 hf.h.val.data(), 1)) {
-    edigpu_destroy(s.release());
-    return 1;
-  }
-  if (model->nph > 0) {
-    HostDirect hd;  // for the sector map
-    e = build_direct(*model, sector, row_first, row_count, hd, jz, twojz, !sw.direct_nosort);
-    if (!e.empty()) set_error(e);
-    if (!e.empty() || attach_phonons_flat(s.get(), *model, hd.states, hd.ns)) {
-      edigpu_destroy(s.release());
-      return 1;
-    }
-  }
-  *h = s.release();
-  return 0;
-}
-}  // namespace edigpu
-extern "C" {
-
-int edigpu_flat_build(edigpu_handle* h, const edigpu_model* model, int sector, int64_t row_first,
-                      int64_t row_count) {
-  return flat_build_common(h, model, sector, row_first, row_count, false, 0);
-}
-
-int edigpu_flat_build_jz(edigpu_handle* h, const edigpu_model* model, int ntot, int twojz, int64_t row_first,
-                         int64_t row_count) {
-  return flat_build_common(h, model, ntot, row_first, row_count, true, twojz);
-}
-
-}  // extern "C"
-namespace edigpu {
-static int direct_build_common(edigpu_handle* h, const edigpu_model* model, int sector, int64_t row_first, int64_t row_count,
-                               bool jz, int twojz);
-}
-extern "C" {
-
-int edigpu_direct_build(edigpu_handle* h, const edigpu_model* model, int sector, int64_t row_first,
-                        int64_t row_count) {
-  return direct_build_common(h, model, sector, row_first, row_count, false, 0);
-}
-
-int edigpu_direct_build_jz(edigpu_handle* h, const edigpu_model* model, int ntot, int twojz, int64_t row_first,
-                           int64_t row_count) {
-  return direct_build_common(h, model, ntot, row_first, row_count, true, twojz);
-}
-
-}  // extern "C"
-namespace edigpu {
-static int direct_build_common(edigpu_handle* h, const edigpu_model* model, int sector, int64_t row_first, int64_t row_count,
-                               bool jz, int twojz) {
-  if (!h || !model) {
-    set_error("edigpu_direct_build: NULL argument");
-    return 1;
-  }
-  *h = nullptr;
-  if (ensure_device()) return 1;
-  const Switches sw = Switches::sample();
-  HostDirect hd;
-  std::string e = build_direct(*model, sector, row_first, row_count, hd, jz, twojz, !sw.direct_nosort);
-  if (!e.empty()) {
-    set_error(e);
-    return 1;
-  }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
-  s->kind = 2;
-  s->model = *model;
-  s->sec_a = sector;
-  s->sec_b = jz ? twojz : 0;
-  s->jz = jz;
-  s->built_by_library = true;
-  s->is_complex = 1;
-  s->device = g_device;
-  s->dim = hd.dim;
-  s->nloc = hd.row_count;
-  s->row_first = hd.row_first;
-  s->dir_ns = hd.ns;
-  s->dir_norb = hd.norb;
-  s->dir_nterms = (int)hd.terms.size();
-  int rc = dev_upload(&s->d_dir_states, hd.states.data(), hd.states.size());
-  rc |= dev_upload(&s->d_dir_offdw, hd.off_dw.data(), hd.off_dw.size());
-  rc |= dev_upload(&s->d_dir_rkup, hd.rk_up.data(), hd.rk_up.size());
-  rc |= dev_upload(&s->d_dir_terms, hd.terms.data(), hd.terms.size());
-  {
-    std::vector<uint2> tests((hd.terms.size() + 31) / 32 * 32, make_uint2(0xFFFFFFFFu, 0u));  // padding never matches
-    for (size_t t = 0; t < hd.terms.size(); t++)
-      tests[t] = make_uint2(hd.terms[t].need_set, hd.terms[t].need_set | hd.terms[t].need_clear);
-    if (tests.empty()) tests.assign(32, make_uint2(0xFFFFFFFFu, 0u));
-    rc |= dev_upload(&s->d_dir_tests, tests.data(), tests.size());
-  }
-  rc |= dev_upload(&s->d_dir_dtab, hd.dtab.data(), hd.dtab.size());
-  rc |= dev_upload(&s->d_dir_xtab, hd.xtab.data(), hd.xtab.size());
-  if (rc || attach_phonons_flat(s.get(), *model, hd.states, hd.ns) || finish_handle(s.get())) {
-    edigpu_destroy(s.release());
-    return 1;
-  }
-  *h = s.release();
-  return 0;
-}
-}  // namespace edigpu
-extern "C" {
-
-int edigpu_orbs_build(edigpu_handle* h, const edigpu_model* model, const int32_t* nups, const int32_t* ndws) {
-  return edigpu_orbs_build_rows(h, model, nups, ndws, 0, -1);
-}
-
-int edigpu_orbs_build_rows(edigpu_handle* h, const edigpu_model* model, const int32_t* nups, const int32_t* ndws,
-                           int64_t row_first, int64_t row_count) {
-  if (!h || !model || !nups || !ndws) {
-    set_error("edigpu_orbs_build: NULL argument");
-    return 1;
-  }
-  *h = nullptr;
-  if (ensure_device()) return 1;
-  const Switches sw = Switches::sample();
-  HostOrbs ho;
-  std::string e = build_orbs(*model, nups, ndws, ho);
-  if (!e.empty()) {
-    set_error(e);
-    return 1;
-  }
-  if (ho.dim == 0) {
-    set_error("edigpu_orbs_build: empty sector");
-    return 1;
-  }
-  if (row_count < 0) row_count = ho.dim - row_first;
-  if (row_first < 0 || row_count < 0 || row_first + row_count > ho.dim) {
-    set_error("edigpu_orbs_build_rows: row range outside the sector");
-    return 1;
-  }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
-  s->model = *model;
-  if (setup_orbs(s.get(), ho, nullptr)) {
-    edigpu_destroy(s.release());
-    return 1;
-  }
-  s->row_first = row_first;  // the factored tables describe the whole sector; only the rows computed differ
-  s->nloc = row_count;
-  s->orbs_nups.assign(nups, nups + model->norb);
-  s->orbs_ndws.assign(ndws, ndws + model->norb);
-  *h = s.release();
-  return 0;
-}
-
-int edigpu_orbs_create(edigpu_handle* h, int naxes, const int64_t* dims, const double* hd,
-                       const int64_t* fac_rowptr, const int32_t* fac_col, const double* fac_val) {
-  if (!h || !dims || !hd || !fac_rowptr) {
-    set_error("edigpu_orbs_create: NULL argument");
-    return 1;
-  }
-  *h = nullptr;
-  if (ensure_device()) return 1;
-  const Switches sw = Switches::sample();
-  if (naxes < 2 || naxes > kOrbsMaxAxes || (naxes & 1)) {
-    set_error("edigpu_orbs_create: naxes must be 2*Norb <= 2*EDIGPU_MAXORB");
-    return 1;
-  }
-  HostOrbs ho;
-  ho.naxes = naxes;
-  ho.dims.assign(dims, dims + naxes);
-  ho.fac.resize(naxes);
-  ho.dim = 1;
-  int64_t row0 = 0;
-  for (int k = 0; k < naxes; k++) {
-    const int64_t d = dims[k];
-    if (d < 1 || ho.dim * d >= ((int64_t)1 << 31)) {
-      set_error("edigpu_orbs_create: bad factor dimension / sector dimension >= 2^31");
-      return 1;
-    }
-    ho.dim *= d;
-    HostCsr& f = ho.fac[k];
-    f.nrow = f.ncol = d;
-    f.rowptr.resize(d + 1);
-    const int64_t b0 = fac_rowptr[row0];
-    for (int64_t i = 0; i <= d; i++) {
-      f.rowptr[i] = fac_rowptr[row0 + i] - b0;
-      if (i > 0 && f.rowptr[i] < f.rowptr[i - 1]) {
-        set_error("edigpu_orbs_create: fac_rowptr not monotone");
-        return 1;
-      }
-    }
-    const int64_t nnz = f.rowptr[d];
-    if (nnz > 0 && (!fac_col || !fac_val)) {
-      set_error("edigpu_orbs_create: fac_col/fac_val NULL");
-      return 1;
-    }
-    f.col.assign(fac_col + b0, fac_col + b0 + nnz);
-    f.val.assign(fac_val + b0, fac_val + b0 + nnz);
-    for (int32_t c : f.col)
-      if (c < 0 || c >= d) {
-        set_error("edigpu_orbs_create: column index out of range");
-        return 1;
-      }
-    row0 += d;
-  }
-  std::unique_ptr<edigpu_sector> s(new edigpu_sector(sw));
-  if (setup_orbs(s.get(), ho, hd)) {
-    edigpu_destroy(s.release());
-    return 1;
-  }
-  *h = s.release();
   return 0;
 }
 
@@ -1928,7 +169,7 @@ int edigpu_sector_map_jz(const edigpu_model* model, int ntot, int twojz, int32_t
 }
 
 int edigpu_image_info(edigpu_handle s, int32_t image[6]) {
-  if (!s || !image || s->kind != 0) {
+  if (!s || !image || s->kind != kNormal) {
     set_error("edigpu_image_info: not a normal-mode handle");
     return 1;
   }
@@ -1953,16 +194,16 @@ int edigpu_info(edigpu_handle s, int64_t info[10]) {
   info[4] = s->kind;
   info[5] = s->dim_up;
   info[6] = s->dim_dw;
-  if (s->kind == 0) {
+  if (s->kind == kNormal) {
     info[7] = s->h_up.nnz() + s->h_dw.nnz();
     info[8] = s->nd_nnz;
-  } else if (s->kind == 4) {
+  } else if (s->kind == kCmplxNormal) {
     info[7] = s->sub_s->h_up.nnz() + s->sub_s->h_dw.nnz();  // pattern of Hup / Hdw (A shares it or is a subset)
     info[8] = s->sub_s->nd_nnz;
-  } else if (s->kind == 2) {
+  } else if (s->kind == kDirect) {
     info[7] = s->dir_nterms;
     info[8] = 0;
-  } else if (s->kind == 3) {
+  } else if (s->kind == kOrbs) {
     info[7] = 0;
     for (const HostCsr& f : s->h_orbs_fac) info[7] += f.nnz();
     info[8] = s->orbs.naxes;
@@ -1982,23 +223,23 @@ int edigpu_algorithmic_bytes(edigpu_handle s, double* bytes_hv, double* bytes_st
   // reference storage format, every array read once, v read once, Hv written once
   double b = 0.0;
   const double sz = s->is_complex ? 16.0 : 8.0;
-  if (s->kind == 4) {
+  if (s->kind == kCmplxNormal) {
     // the reference's complex(8) normal-mode arrays: same pattern as the real build, 16-byte values and vectors
     const edigpu_sector* r = s->sub_s;
     const double n = (double)s->nloc;
     b = 3.0 * sz * n;
     if (r->has_nd) b += (sz + 4.0) * (double)r->nd_nnz + 4.0 * (n + 1.0);
     b += (sz + 4.0) * (double)(r->h_up.nnz() + r->h_dw.nnz()) + 4.0 * (double)(r->dim_up + r->dim_dw + 2);
-  } else if (s->kind == 0) {
+  } else if (s->kind == kNormal) {
     const double n = (double)s->nloc;
     b = 3.0 * sz * n;
     if (s->has_nd) b += (sz + 4.0) * (double)s->nd_nnz + 4.0 * (n + 1.0);
     b += (sz + 4.0) * (double)(s->h_up.nnz() + s->h_dw.nnz()) + 4.0 * (double)(s->dim_up + s->dim_dw + 2);
-  } else if (s->kind == 3) {
+  } else if (s->kind == kOrbs) {
     // orbs: diagonal + 2 vectors + the small factor matrices
     b = 3.0 * sz * (double)s->nloc;
     for (const HostCsr& f : s->h_orbs_fac) b += (sz + 4.0) * (double)f.nnz() + 4.0 * (double)(f.nrow + 1);
-  } else if (s->kind == 2) {
+  } else if (s->kind == kDirect) {
     // direct: 2 vectors + the sector map (B = 2*s*Dim + 4*DimEl)
     b = 2.0 * sz * (double)s->nloc + 4.0 * (double)s->nloc;
   } else {
@@ -2008,1187 +249,6 @@ int edigpu_algorithmic_bytes(edigpu_handle s, double* bytes_hv, double* bytes_st
   if (bytes_hv) *bytes_hv = b;
   if (bytes_step) *bytes_step = b + 3.0 * sz * (double)s->nloc;
   return 0;
-}
-
-static int download_csr(const DevCsr& d, int64_t* rowptr, int32_t* col, double* val, int w) {
-  if (rowptr) {
-    if (d.nrow == 0) {
-      rowptr[0] = 0;
-    } else if (d.wide) {
-      EDIGPU_HIP(hipMemcpy(rowptr, d.rowptr64, ((size_t)d.nrow + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    } else {
-      std::vector<int32_t> rp((size_t)d.nrow + 1);
-      EDIGPU_HIP(hipMemcpy(rp.data(), d.rowptr32, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-      for (int64_t i = 0; i <= d.nrow; i++) rowptr[i] = rp[i];
-    }
-  }
-  if (col && d.nnz) EDIGPU_HIP(hipMemcpy(col, d.col, (size_t)d.nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (val && d.nnz) EDIGPU_HIP(hipMemcpy(val, d.val, (size_t)d.nnz * w * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int edigpu_normal_export(edigpu_handle s, double* hd, int64_t* up_rowptr, int32_t* up_col,
-                         double* up_val, int64_t* dw_rowptr, int32_t* dw_col, double* dw_val,
-                         int64_t* nd_rowptr, int32_t* nd_col, double* nd_val) {
-  if (!s || s->kind != 0) {
-    set_error("edigpu_normal_export: not a normal-mode handle");
-    return 1;
-  }
-  EDIGPU_HIP(hipSetDevice(s->device));
-  if (s->lazy_export && s->factored) {
-    // first export of a factored sector: materialise the explicit images from the stored model
-    HostNormal hn;
-    std::string e = build_normal(s->model, s->sec_a, s->sec_b, s->dw_first, s->dw_count, hn, true, !s->sw.nd_no_merge);
-    if (!e.empty()) {
-      set_error(e);
-      return 1;
-    }
-    s->h_hd = std::move(hn.hd);
-    s->h_nd = std::move(hn.nd);
-    s->lazy_export = false;
-  }
-  if (hd && s->nloc) {
-    if (s->factored)
-      std::copy(s->h_hd.begin(), s->h_hd.end(), hd);
-    else
-      EDIGPU_HIP(hipMemcpy(hd, s->d_hd, (size_t)(s->nph > 0 ? s->dim_el : s->nloc) * sizeof(double),
-                           hipMemcpyDeviceToHost));  // the electronic diagonal (one phonon block)
-  }
-  auto cp = [](const HostCsr& a, int64_t* rp, int32_t* c, double* v) {
-    if (rp) std::copy(a.rowptr.begin(), a.rowptr.end(), rp);
-    if (c) std::copy(a.col.begin(), a.col.end(), c);
-    if (v) std::copy(a.val.begin(), a.val.end(), v);
-  };
-  cp(s->h_up, up_rowptr, up_col, up_val);
-  cp(s->h_dw, dw_rowptr, dw_col, dw_val);
-  if (s->has_nd && s->factored) {
-    cp(s->h_nd, nd_rowptr, nd_col, nd_val);
-    return 0;
-  }
-  if (s->has_nd) return download_csr(s->nd, nd_rowptr, nd_col, nd_val, 1);
-  if (nd_rowptr)
-    for (int64_t i = 0; i <= s->nloc; i++) nd_rowptr[i] = 0;
-  return 0;
-}
-
-int edigpu_csr_export(edigpu_handle s, int64_t* rowptr, int32_t* col, double* val) {
-  if (!s || s->kind != 1) {
-    set_error("edigpu_csr_export: not a flat-CSR handle (direct handles store no matrix)");
-    return 1;
-  }
-  EDIGPU_HIP(hipSetDevice(s->device));
-  if (s->lazy_export) {
-    // device-built sector: the CSR image only exists if somebody asks for it
-    HostFlat hf;
-    // (phonon sectors: the electronic block, as edigpu_normal_export hands back the electronic factors)
-    std::string e = build_flat(s->model, s->sec_a, s->row_first, s->nph > 0 ? s->dim_el : s->nloc, hf, s->jz, s->sec_b);
-    if (!e.empty()) {
-      set_error(e);
-      return 1;
-    }
-    if (rowptr) std::copy(hf.h.rowptr.begin(), hf.h.rowptr.end(), rowptr);
-    if (col) std::copy(hf.h.col.begin(), hf.h.col.end(), col);
-    if (val) std::copy(hf.h.val.begin(), hf.h.val.end(), val);
-    return 0;
-  }
-  const int w = s->is_complex ? 2 : 1;
-  const int64_t n = s->nloc;
-  std::vector<int64_t> rl((size_t)n + 1), rn((size_t)n + 1);
-  std::vector<int32_t> cl((size_t)s->loc.nnz), cn((size_t)s->nonloc.nnz);
-  std::vector<double> vl((size_t)s->loc.nnz * w), vn((size_t)s->nonloc.nnz * w);
-  if (download_csr(s->loc, rl.data(), cl.data(), vl.data(), w)) return 1;
-  if (download_csr(s->nonloc, rn.data(), cn.data(), vn.data(), w)) return 1;
-  int64_t p = 0;
-  if (rowptr) rowptr[0] = 0;
-  for (int64_t i = 0; i < n; i++) {
-    for (int64_t k = rl[i]; k < rl[i + 1]; k++, p++) {
-      if (col) col[p] = (int32_t)(cl[k] + s->row_first);
-      if (val)
-        for (int q = 0; q < w; q++) val[p * w + q] = vl[k * w + q];
-    }
-    for (int64_t k = rn[i]; k < rn[i + 1]; k++, p++) {
-      if (col) col[p] = cn[k];
-      if (val)
-        for (int q = 0; q < w; q++) val[p * w + q] = vn[k * w + q];
-    }
-    if (rowptr) rowptr[i + 1] = p;
-  }
-  return 0;
-}
-
-static int apply_host(edigpu_handle s, int64_t nloc, const double* v_host, double* hv_host, int cplx) {
-  if (!s || !v_host || !hv_host) {
-    set_error("edigpu_apply: NULL argument");
-    return 1;
-  }
-  if ((s->is_complex != 0) != (cplx != 0)) {
-    set_error("edigpu_apply: real/complex mismatch between handle and entry point");
-    return 1;
-  }
-  if (nloc != s->nloc) {
-    set_error("edigpu_apply: Nloc does not match the handle's local dimension");
-    return 1;
-  }
-  if (single_shard(s, "edigpu_apply")) return 1;
-  EDIGPU_HIP(hipSetDevice(s->device));
-  if (ensure_workspace(s)) return 1;
-  const size_t bytes = (size_t)s->ws_len * sizeof(double);
-  if (s->kind == 0 && s->ib && s->nph == 0) {
-    // host vectors cross PCIe anyway: take the impurity-block kernels of the device-resident loops (two layout
-    // conversions on the device are small next to the transfers)
-    hipStream_t st = s->stream;
-    EDIGPU_HIP(hipMemcpyAsync(s->d_tmp, v_host, bytes, hipMemcpyHostToDevice, st));
-    if (vec_to_ib(s->ib, s->d_tmp, s->d_vin, st) || launch_ib(s, s->d_vin, s->d_vout, st) || vec_from_ib(s->ib, s->d_vout, s->d_tmp, st))
-      return 1;
-    EDIGPU_HIP(hipMemcpyAsync(hv_host, s->d_tmp, bytes, hipMemcpyDeviceToHost, st));
-    EDIGPU_HIP(hipStreamSynchronize(st));
-    return 0;
-  }
-  EDIGPU_HIP(hipMemcpyAsync(s->d_vin, v_host, bytes, hipMemcpyHostToDevice, s->stream));
-  if (apply_any(s, s->d_vin, s->d_vin, s->d_tmp, 3, s->stream)) return 1;
-  EDIGPU_HIP(hipMemcpyAsync(hv_host, s->d_tmp, bytes, hipMemcpyDeviceToHost, s->stream));
-  EDIGPU_HIP(hipStreamSynchronize(s->stream));
-  return 0;
-}
-
-int edigpu_apply_d(edigpu_handle h, int64_t nloc, const double* v_host, double* hv_host) {
-  return apply_host(h, nloc, v_host, hv_host, 0);
-}
-
-int edigpu_apply_z(edigpu_handle h, int64_t nloc, const double* v_host, double* hv_host) {
-  return apply_host(h, nloc, v_host, hv_host, 1);
-}
-
-int edigpu_apply_dev(edigpu_handle s, const void* v_full_dev, void* hv_dev, void* stream) {
-  if (!s || !v_full_dev || !hv_dev) {
-    set_error("edigpu_apply_dev: NULL argument");
-    return 1;
-  }
-  hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default (null) stream
-  const int w = s->is_complex ? 2 : 1;
-  const double* vf = (const double*)v_full_dev;
-  return apply_any(s, vf + s->row_first * w, vf, (double*)hv_dev, 3, st);
-}
-
-int edigpu_apply_local_dev(edigpu_handle s, const void* v_local_dev, void* hv_dev, void* stream) {
-  if (!s || !v_local_dev || !hv_dev) {
-    set_error("edigpu_apply_local_dev: NULL argument");
-    return 1;
-  }
-  hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default (null) stream
-  return apply_any(s, (const double*)v_local_dev, nullptr, (double*)hv_dev, 1, st);
-}
-
-int edigpu_apply_remote_dev(edigpu_handle s, const void* v_full_dev, void* hv_dev, void* stream) {
-  if (!s || !v_full_dev || !hv_dev) {
-    set_error("edigpu_apply_remote_dev: NULL argument");
-    return 1;
-  }
-  hipStream_t st = (hipStream_t)stream;  // NULL = the HIP default (null) stream
-  return apply_any(s, nullptr, (const double*)v_full_dev, (double*)hv_dev, 2, st);
-}
-
-// ---- transposed exchange (normal mode, N > 1): see include/edigpu.h ----
-int edigpu_normal_transpose_info(edigpu_handle s, int32_t* halo) {
-  if (!s || !halo) {
-    set_error("edigpu_normal_transpose_info: NULL argument");
-    return 1;
-  }
-  if (!normal_transposable(s)) {
-    set_error("edigpu_normal_transpose_info: needs a whole normal-mode sector built by edigpu_normal_build "
-              "(factored Hnd, no phonons); use the all-gather entry points otherwise");
-    return 1;
-  }
-  *halo = s->col_halo;
-  return 0;
-}
-
-int edigpu_normal_apply_rows_dev(edigpu_handle s, int64_t dw_first, int64_t dw_count, const void* v_rows_dev,
-                                 void* hv_rows_dev, void* stream) {
-  if (!s || !v_rows_dev || !hv_rows_dev) {
-    set_error("edigpu_normal_apply_rows_dev: NULL argument");
-    return 1;
-  }
-  if (!normal_transposable(s)) {
-    set_error("edigpu_normal_apply_rows_dev: not a transposable handle (see edigpu_normal_transpose_info)");
-    return 1;
-  }
-  if (dw_first < 0 || dw_count < 0 || dw_first + dw_count > s->dim_dw) {
-    set_error("edigpu_normal_apply_rows_dev: row range outside [0, DimDw)");
-    return 1;
-  }
-  EDIGPU_HIP(hipSetDevice(s->device));
-  return launch_normal_rows(s, dw_first, dw_count, (const double*)v_rows_dev, (double*)hv_rows_dev,
-                            (hipStream_t)stream);
-}
-
-int edigpu_normal_apply_cols_dev(edigpu_handle s, int64_t col_first, int64_t col_count, int64_t row_stride,
-                                 int32_t halo, const void* w_cols_dev, void* hv_cols_dev, void* stream) {
-  if (!s || !w_cols_dev || !hv_cols_dev) {
-    set_error("edigpu_normal_apply_cols_dev: NULL argument");
-    return 1;
-  }
-  if (!normal_transposable(s)) {
-    set_error("edigpu_normal_apply_cols_dev: not a transposable handle (see edigpu_normal_transpose_info)");
-    return 1;
-  }
-  if (col_first < 0 || col_count < 0 || col_first + col_count > s->dim_up || halo < s->col_halo ||
-      row_stride < col_count + 2 * (int64_t)halo) {
-    set_error("edigpu_normal_apply_cols_dev: column range outside [0, DimUp), halo smaller than the sector needs, "
-              "or row stride < col_count + 2 halo");
-    return 1;
-  }
-  EDIGPU_HIP(hipSetDevice(s->device));
-  return launch_normal_cols(s, col_first, col_count, row_stride, halo, (const double*)w_cols_dev, (double*)hv_cols_dev,
-                            (hipStream_t)stream);
-}
-
-int edigpu_transpose_pack(int64_t dim_up, int64_t nrows, int64_t q, int32_t world, int64_t pcol, int32_t halo,
-                          const void* v_rows_dev, void* send_dev, void* stream) {
-  if (!v_rows_dev || !send_dev || dim_up <= 0 || nrows < 0 || nrows > q || world <= 0 || pcol <= 0 || halo < 0 ||
-      pcol * world < dim_up) {
-    set_error("edigpu_transpose_pack: bad argument");
-    return 1;
-  }
-  if (ensure_device()) return 1;
-  return launch_transpose_pack(dim_up, nrows, q, world, pcol, halo, (const double*)v_rows_dev, (double*)send_dev,
-                               (hipStream_t)stream);
-}
-
-int edigpu_transpose_unpack_add(int64_t dim_up, int64_t nrows, int64_t q, int32_t world, int64_t pcol,
-                                int32_t halo, const void* recv_dev, void* hv_rows_dev, void* stream) {
-  if (!recv_dev || !hv_rows_dev || dim_up <= 0 || nrows < 0 || nrows > q || world <= 0 || pcol <= 0 || halo < 0 ||
-      pcol * world < dim_up) {
-    set_error("edigpu_transpose_unpack_add: bad argument");
-    return 1;
-  }
-  if (ensure_device()) return 1;
-  return launch_transpose_unpack_add(dim_up, nrows, q, world, pcol, halo, (const double*)recv_dev,
-                                     (double*)hv_rows_dev, (hipStream_t)stream);
-}
-
-int edigpu_transpose_rotate_pack(int32_t first, int64_t dim_up, int64_t nrows, int64_t q, int32_t world,
-                                 int64_t pcol, int32_t halo, void* vin_dev, void* vout_dev, const void* ab_dev,
-                                 void* send_dev, void* stream) {
-  if (!vin_dev || !vout_dev || !send_dev || (!first && !ab_dev) || dim_up <= 0 || nrows < 0 || nrows > q ||
-      world <= 0 || pcol <= 0 || halo < 0 || pcol * world < dim_up) {
-    set_error("edigpu_transpose_rotate_pack: bad argument");
-    return 1;
-  }
-  if (ensure_device()) return 1;
-  return vec_rotate_pack(first, dim_up, nrows, q, world, pcol, halo, (double*)vin_dev, (double*)vout_dev,
-                         (const double*)ab_dev, (double*)send_dev, (hipStream_t)stream);
-}
-
-int edigpu_transpose_unpack_add_dot2(int64_t dim_up, int64_t nrows, int64_t q, int32_t world, int64_t pcol,
-                                     int32_t halo, const void* vin_dev, void* vout_dev, const void* tmp_dev,
-                                     const void* back_dev, void* out2_dev, void* work_dev, void* stream) {
-  if (!vin_dev || !vout_dev || !tmp_dev || !back_dev || !out2_dev || !work_dev || dim_up <= 0 || nrows < 0 ||
-      nrows > q || world <= 0 || pcol <= 0 || halo < 0 || pcol * world < dim_up) {
-    set_error("edigpu_transpose_unpack_add_dot2: bad argument");
-    return 1;
-  }
-  if (ensure_device()) return 1;
-  return vec_unpack_add_dot2(dim_up, nrows, q, pcol, halo, (const double*)vin_dev, (double*)vout_dev,
-                             (const double*)tmp_dev, (const double*)back_dev, (double*)out2_dev, (double*)work_dev,
-                             (hipStream_t)stream);
-}
-
-// seed from host or device memory (hipMemcpyDefault); norm2 = <vin|vin> as tridiag_Hv_sector_* returns it
-static int tridiag_impl(edigpu_handle s, const double* vin, int nlanc, double* alanc, double* blanc,
-                        double threshold, int* niter_done, double* norm2) {
-  if (!s || !vin || !alanc || !blanc || nlanc <= 0) {
-    set_error("edigpu_lanczos_tridiag: bad argument");
-    return 1;
-  }
-  if (single_shard(s, "edigpu_lanczos_tridiag")) return 1;
-  // _CMPLX_NORMAL held as one real sector on the doubled up index: complex Lanczos on H = real Lanczos on that sector
-  // with the interleaved vector read as real (alpha = <v|H|v> is real, beta a norm), so the fused real loop does it
-  if (s->kind == 4 && s->sub_d) return tridiag_impl(s->sub_d, vin, nlanc, alanc, blanc, threshold, niter_done, norm2);
-  EDIGPU_HIP(hipSetDevice(s->device));
-  if (ensure_workspace(s)) return 1;
-  hipStream_t st = s->stream;
-  if (lanczos_prepare(s, nlanc, threshold, st)) return 1;
-  if (lanczos_seed(s, vin, 0, st)) return 1;
-  if (lz_norm_begin(s->d_vin, s->lz_len, s->d_partial, s->d_scal, st)) return 1;
-  if (lanczos_run(s, 0, nlanc, nlanc, st)) return 1;
-  std::vector<double> sc((size_t)SC_AB + 2 * (size_t)nlanc);
-  EDIGPU_HIP(hipMemcpyAsync(sc.data(), s->d_scal, sc.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  EDIGPU_HIP(hipStreamSynchronize(st));
-  if (!(sc[SC_NORM] > 0.0)) {  // zero seed: nothing to tridiagonalise (the reference skips such channels)
-    std::fill(alanc, alanc + nlanc, 0.0);
-    std::fill(blanc, blanc + nlanc, 0.0);
-    if (niter_done) *niter_done = 0;
-    if (norm2) *norm2 = 0.0;
-    return 0;
-  }
-  for (int k = 0; k < nlanc; k++) {
-    alanc[k] = sc[SC_AB + k];
-    blanc[k] = sc[SC_AB + nlanc + k];
-  }
-  if (niter_done) *niter_done = (int)sc[SC_NDONE];
-  if (norm2) *norm2 = sc[SC_NORM] * sc[SC_NORM];
-  return 0;
-}
-
-int edigpu_lanczos_tridiag(edigpu_handle s, const double* vin_host, int nlanc, double* alanc,
-                           double* blanc, double threshold, int* niter_done) {
-  return tridiag_impl(s, vin_host, nlanc, alanc, blanc, threshold, niter_done, nullptr);
-}
-
-int edigpu_lanczos_tridiag_dev(edigpu_handle s, const double* vin_dev, int nlanc, double* alanc,
-                               double* blanc, double threshold, int* niter_done, double* norm2) {
-  return tridiag_impl(s, vin_dev, nlanc, alanc, blanc, threshold, niter_done, norm2);
-}
-
-// one term of apply_Cops / apply_op_C / apply_op_CDG on device vectors of two normal-mode sectors:
-// v_dst (=|+=) coef * c^(+)_{iorb,ispin} v_src
-// one operator of apply_Cops on normal-mode sectors: the destination's down rows [fd, fd + cd) (v_dst_dev holds those
-// rows), v_src_dev = the whole source vector
-static int apply_op_normal_term(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev,
-                                int iorb, int ispin, int create, double coef, int accumulate, hipStream_t st,
-                                const char* who, int64_t fd = 0, int64_t cd = -1) {
-  const std::string w(who);
-  if (src->kind != 0 || dst->kind != 0 || !src->from_model() || !dst->from_model() || src->nph > 0 || dst->nph > 0) {
-    set_error(w + ": both handles must be normal-mode sectors built by edigpu_normal_build");
-    return 1;
-  }
-  if (src->nloc != src->dim || dst->nloc != dst->dim) {
-    set_error(w + ": handles must hold whole sectors");
-    return 1;
-  }
-  const int ns = model_ns(src->model);
-  if (iorb < 0 || iorb >= src->model.norb || ispin < 0 || ispin > 1) {
-    set_error(w + ": orbital / spin out of range");
-    return 1;
-  }
-  const int d = create ? 1 : -1;
-  const int nup_s = src->sec_a, ndw_s = src->sec_b;
-  if (dst->sec_a != nup_s + (ispin == 0 ? d : 0) || dst->sec_b != ndw_s + (ispin == 1 ? d : 0) ||
-      model_ns(dst->model) != ns) {
-    set_error(w + ": destination sector is not (source sector +- one particle of that spin)");
-    return 1;
-  }
-  if (cd < 0) cd = dst->dim_dw - fd;
-  if (fd < 0 || fd + cd > dst->dim_dw) {
-    set_error(w + ": row window outside the destination sector");
-    return 1;
-  }
-  EDIGPU_HIP(hipSetDevice(src->device));
-  // signed partial permutation of the changed species: for every destination state its preimage
-  CombBasis bs, bd;
-  bs.init(ns, ispin == 0 ? nup_s : ndw_s);
-  bd.init(ns, ispin == 0 ? dst->sec_a : dst->sec_b);
-  const uint32_t bit = 1u << iorb;
-  std::vector<uint32_t> part((size_t)std::max<int64_t>(bd.size(), 1), 0xFFFFFFFFu);
-  for (int64_t j = 0; j < bd.size(); j++) {
-    const uint32_t t = (uint32_t)bd.states[j];
-    if (create ? !(t & bit) : (t & bit) != 0u) continue;  // c^+ leaves the level occupied, c leaves it empty
-    const uint32_t sst = t ^ bit;                         // source state
-    const uint32_t sg = (__builtin_popcount(sst & (bit - 1u)) & 1) ? 0x80000000u : 0u;
-    part[j] = (uint32_t)bs.rank(sst) | sg;
-  }
-  uint32_t* d_part = nullptr;
-  if (dev_upload(&d_part, part.data(), part.size())) return 1;
-  // up operator: the rows keep their down index (the source's rows fd .. are read); down operator: the partner table is
-  // indexed by the destination's down index
-  const int rc = ispin == 0 ? launch_apply_op_normal(dst->dim_up, cd, src->dim_up, 0, d_part, v_src_dev + fd * src->dim_up,
-                                                     v_dst_dev, st, coef, accumulate)
-                            : launch_apply_op_normal(dst->dim_up, cd, src->dim_up, 1, d_part + fd, v_src_dev, v_dst_dev, st,
-                                                     coef, accumulate);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(d_part);
-  return rc;
-}
-
-// one operator of apply_Cops on superc / nonsu2 sectors (whole sectors or row shards of library-built ones): the
-// destination's rows [fd, fd + cd), v_src_dev = the whole source vector (complex)
-static int apply_op_flat_term(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev, int iorb,
-                              int ispin, int create, double cre, double cim, int accumulate, hipStream_t st, const char* who,
-                              int64_t fd = 0, int64_t cd = -1) {
-  const std::string w(who);
-  if ((src->kind != 1 && src->kind != 2) || (dst->kind != 1 && dst->kind != 2) || !src->built_by_library ||
-      !dst->built_by_library) {
-    set_error(w + ": both handles must be superc / nonsu2 sectors built by edigpu_flat_build or edigpu_direct_build");
-    return 1;
-  }
-  if (src->nph != dst->nph || src->model.nph != dst->model.nph) {
-    set_error(w + ": the two handles have different nph (" + std::to_string(src->nph) + " and " + std::to_string(dst->nph) + ")");
-    return 1;
-  }
-  const int nblk = src->nph + 1;
-  if (nblk > 1 && (src->nloc != src->dim || dst->nloc != dst->dim || fd != 0 || cd >= 0)) {
-    set_error(w + ": phonon sectors are served as whole sectors only (no shards, no row window)");
-    return 1;
-  }
-  const edigpu_model& m = src->model;
-  const int ns = model_ns(m);
-  if (iorb < 0 || iorb >= m.norb || ispin < 0 || ispin > 1 || dst->model.ed_mode != m.ed_mode ||
-      model_ns(dst->model) != ns) {
-    set_error(w + ": orbital / spin out of range or sectors of different models");
-    return 1;
-  }
-  // superc: sector = Sz = Nup - Ndw; nonsu2: sector = Ntot
-  const int d = create ? 1 : -1;
-  const int want = m.ed_mode == 1 ? src->sec_a + (ispin == 0 ? d : -d) : src->sec_a + d;
-  // Jz_basis=T: the operator also moves twoJz by the spin and the Lz of its level (ED_SECTOR.f90:289-350)
-  const int want_jz = src->jz ? src->sec_b + d * twojz_of_level(iorb + ispin * ns, ns, m.norb) : 0;
-  if (dst->sec_a != want || dst->jz != src->jz || (src->jz && dst->sec_b != want_jz)) {
-    set_error(w + ": destination sector is not the one the operator leads to");
-    return 1;
-  }
-  EDIGPU_HIP(hipSetDevice(src->device));
-  HostDirect hs, hd;
-  std::string e = build_direct(src->model, src->sec_a, 0, -1, hs, src->jz, src->sec_b, !src->sw.direct_nosort);
-  if (e.empty()) e = build_direct(dst->model, dst->sec_a, 0, -1, hd, dst->jz, dst->sec_b, !dst->sw.direct_nosort);
-  if (!e.empty()) {
-    set_error(e);
-    return 1;
-  }
-  if (cd < 0) cd = hd.dim - fd;
-  if (fd < 0 || fd + cd > hd.dim) {
-    set_error(w + ": row window outside the destination sector");
-    return 1;
-  }
-  int32_t *d_states = nullptr, *d_off = nullptr, *d_rk = nullptr;
-  int rc = dev_upload(&d_states, hd.states.data(), hd.states.size());
-  rc |= dev_upload(&d_off, hs.off_dw.data(), hs.off_dw.size());
-  rc |= dev_upload(&d_rk, hs.rk_up.data(), hs.rk_up.size());
-  if (!rc)
-    rc = launch_apply_op_flat(cd, ns, 1u << (iorb + ispin * ns), create, d_states + fd, d_off, d_rk, v_src_dev, v_dst_dev, st,
-                              cre, cim, accumulate, nblk, hs.dim);  // phonon sectors: every electronic block, one launch
-  (void)hipStreamSynchronize(st);
-  dev_free(d_states);
-  dev_free(d_off);
-  dev_free(d_rk);
-  return rc;
-}
-
-}  // extern "C"
-namespace edigpu {
-int apply_cops_rows(edigpu_sector* src, edigpu_sector* dst, const double* v_src_full, double* v_dst_rows, int64_t first,
-                    int64_t count, int nops, const double* coef2, const int32_t* create, const int32_t* iorb,
-                    const int32_t* ispin, hipStream_t st, const char* who) {
-  for (int s = 0; s < nops; s++) {
-    if (src->kind == 0) {
-      if (coef2[2 * s + 1] != 0.0) {
-        set_error(std::string(who) + ": complex coefficients belong to the _CMPLX_NORMAL build");
-        return 1;
-      }
-      if (apply_op_normal_term(src, dst, v_src_full, v_dst_rows, iorb[s], ispin[s], create[s] > 0, coef2[2 * s], s > 0, st, who,
-                               first, count))
-        return 1;
-    } else if (apply_op_flat_term(src, dst, v_src_full, v_dst_rows, iorb[s], ispin[s], create[s] > 0, coef2[2 * s],
-                                  coef2[2 * s + 1], s > 0, st, who, first, count)) {
-      return 1;
-    }
-  }
-  return 0;
-}
-}  // namespace edigpu
-extern "C" {
-
-int edigpu_apply_op_normal(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev,
-                           int iorb, int ispin, int create, void* stream) {
-  if (!src || !dst || !v_src_dev || !v_dst_dev) {
-    set_error("edigpu_apply_op_normal: NULL argument");
-    return 1;
-  }
-  if (axisop_route(src, dst)) {  // phonon, complex and ed_total_ud=F sectors: kernels_axisop.hip
-    const int32_t cr = create ? 1 : -1, io = iorb, sp = ispin;
-    const double one = 1.0;
-    return axisop_apply(src, dst, v_src_dev, v_dst_dev, 1, &one, nullptr, &cr, &io, &sp, (hipStream_t)stream,
-                        "edigpu_apply_op_normal");
-  }
-  return apply_op_normal_term(src, dst, v_src_dev, v_dst_dev, iorb, ispin, create, 1.0, 0, (hipStream_t)stream,
-                              "edigpu_apply_op_normal");
-}
-
-int edigpu_apply_cops_normal(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev,
-                             int nops, const double* coef, const int32_t* create, const int32_t* iorb,
-                             const int32_t* ispin, void* stream) {
-  if (!src || !dst || !v_src_dev || !v_dst_dev || nops <= 0 || !coef || !create || !iorb || !ispin) {
-    set_error("edigpu_apply_cops_normal: bad argument");
-    return 1;
-  }
-  if (axisop_route(src, dst))  // phonon, complex and ed_total_ud=F sectors: all operators in one pass (kernels_axisop.hip)
-    return axisop_apply(src, dst, v_src_dev, v_dst_dev, nops, coef, nullptr, create, iorb, ispin, (hipStream_t)stream,
-                        "edigpu_apply_cops_normal");
-  for (int s = 0; s < nops; s++)
-    if (apply_op_normal_term(src, dst, v_src_dev, v_dst_dev, iorb[s], ispin[s], create[s] > 0, coef[s], s > 0,
-                             (hipStream_t)stream, "edigpu_apply_cops_normal"))
-      return 1;
-  return 0;
-}
-
-int edigpu_apply_op_flat(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev,
-                         int iorb, int ispin, int create, void* stream) {
-  if (!src || !dst || !v_src_dev || !v_dst_dev) {
-    set_error("edigpu_apply_op_flat: NULL argument");
-    return 1;
-  }
-  if (src->nloc != src->dim || dst->nloc != dst->dim) {
-    set_error("edigpu_apply_op_flat: handles must hold whole sectors (single shard)");
-    return 1;
-  }
-  return apply_op_flat_term(src, dst, v_src_dev, v_dst_dev, iorb, ispin, create, 1.0, 0.0, 0, (hipStream_t)stream,
-                            "edigpu_apply_op_flat");
-}
-
-int edigpu_apply_cops_flat(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev, int nops,
-                           const double* coef_re_im, const int32_t* create, const int32_t* iorb, const int32_t* ispin,
-                           void* stream) {
-  if (!src || !dst || !v_src_dev || !v_dst_dev || nops <= 0 || !coef_re_im || !create || !iorb || !ispin) {
-    set_error("edigpu_apply_cops_flat: bad argument");
-    return 1;
-  }
-  if (src->nloc != src->dim || dst->nloc != dst->dim) {
-    set_error("edigpu_apply_cops_flat: handles must hold whole sectors (single shard)");
-    return 1;
-  }
-  for (int s = 0; s < nops; s++)
-    if (apply_op_flat_term(src, dst, v_src_dev, v_dst_dev, iorb[s], ispin[s], create[s] > 0, coef_re_im[2 * s],
-                           coef_re_im[2 * s + 1], s > 0, (hipStream_t)stream, "edigpu_apply_cops_flat"))
-      return 1;
-  return 0;
-}
-
-int edigpu_lanczos_eigh(edigpu_handle s, int nitermax, double tol, int check_every,
-                        const double* v0_host, double* eval, double* evec_host, int* niter_done) {
-  if (!s || !eval || nitermax <= 0) {
-    set_error("edigpu_lanczos_eigh: bad argument");
-    return 1;
-  }
-  if (single_shard(s, "edigpu_lanczos_eigh")) return 1;
-  if (s->kind == 4 && s->sub_d)  // see tridiag_impl: the Ritz vector comes back interleaved, i.e. complex
-    return edigpu_lanczos_eigh(s->sub_d, nitermax, tol, check_every, v0_host, eval, evec_host, niter_done);
-  EDIGPU_HIP(hipSetDevice(s->device));
-  if (ensure_workspace(s)) return 1;
-  if (check_every <= 0) check_every = 10;
-  if ((int64_t)nitermax > s->nloc) nitermax = (int)s->nloc;
-  hipStream_t st = s->stream;
-  // breakdown guard: a beta below 1e-12 means the Krylov space is exhausted (tiny sectors with nitermax ~ dim); the
-  // recurrence stops there instead of dividing by it
-  constexpr double kBreakdown = 1e-12;
-  if (lanczos_prepare(s, nitermax, kBreakdown, st)) return 1;
-  const int64_t len = s->lz_len;
-  const size_t vbytes = (size_t)len * sizeof(double);
-  // keep the normalised start vector for the second pass
-  double* d_v0 = nullptr;
-  EDIGPU_HIP(hipMalloc((void**)&d_v0, vbytes));
-  auto fail = [&](void) {
-    (void)hipFree(d_v0);
-    return 1;
-  };
-  if (lanczos_seed(s, v0_host, 0x5eed1234ull, st)) return fail();
-  if (lz_norm_begin(s->d_vin, len, s->d_partial, s->d_scal, st)) return fail();
-  if (hipMemcpyAsync(d_v0, s->d_vin, vbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail();
-
-  std::vector<double> sc((size_t)SC_AB + 2 * (size_t)nitermax), d, e, z;
-  double e_old = 0.0;
-  int ndone = 0;
-  bool have = false, conv = false;
-  // With a vector asked for, the Lanczos vectors are kept as they are produced (blocks of kKeep vectors, allocated
-  // while the device has room: 288 GB hold thousands of config-2 vectors) and the Ritz vector is assembled from them --
-  // one extra copy per step instead of a second pass that regenerates every v_k with as many products again.
-  // LoopSwitches::eigh_twopass, or an allocation that fails, falls back to the second pass.
-  constexpr int kKeep = 16;
-  std::vector<double*> kept;  // block b holds v_(b kKeep) .. v_(b kKeep + kKeep - 1)
-  bool keep = evec_host != nullptr && !s->lz.eigh_twopass;  // (sampled by lanczos_prepare above)
-  auto drop_kept = [&]() {
-    for (double* b : kept) (void)hipFree(b);
-    kept.clear();
-    keep = false;
-  };
-  auto fail_all = [&]() {
-    drop_kept();
-    return fail();
-  };
-  for (int it0 = 0; it0 < nitermax && !conv;) {
-    // the steps up to the next convergence check in one go (replayed from a graph on launch-bound sectors)
-    const int it1 = std::min(nitermax, (it0 / check_every + 1) * check_every);
-    if (keep) {
-      for (int it = it0; it < it1 && keep; it++) {
-        if (it % kKeep == 0) {
-          size_t fr = 0, tot = 0;
-          double* b = nullptr;
-          // leave a quarter of the device free for whatever else lives there
-          if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < tot / 4 + (size_t)kKeep * vbytes ||
-              hipMalloc((void**)&b, (size_t)kKeep * vbytes) != hipSuccess) {
-            (void)hipGetLastError();
-            drop_kept();
-            break;
-          }
-          kept.push_back(b);
-        }
-        if (lanczos_step(s, it, nitermax, st)) return fail_all();
-        if (hipMemcpyAsync(kept[(size_t)(it / kKeep)] + (size_t)(it % kKeep) * (size_t)len, s->d_vin, vbytes,
-                           hipMemcpyDeviceToDevice, st) != hipSuccess)
-          return fail_all();
-        it0 = it + 1;
-      }
-      if (it0 < it1 && lanczos_run(s, it0, it1, nitermax, st)) return fail_all();  // (room ran out part way)
-    } else if (lanczos_run(s, it0, it1, nitermax, st)) {
-      return fail_all();
-    }
-    it0 = it1;
-    {
-      if (hipMemcpyAsync(sc.data(), s->d_scal, sc.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
-        return fail_all();
-      if (hipStreamSynchronize(st) != hipSuccess) return fail_all();
-      ndone = (int)sc[SC_NDONE];
-      if (ndone == 0) break;
-      d.assign(sc.begin() + SC_AB, sc.begin() + SC_AB + ndone);
-      e.assign(sc.begin() + SC_AB + nitermax, sc.begin() + SC_AB + nitermax + ndone);
-      if (tql2(ndone, d, e, z)) {
-        set_error("edigpu_lanczos_eigh: tridiagonal QL did not converge");
-        return fail_all();
-      }
-      const double e_new = *std::min_element(d.begin(), d.end());
-      if (have && fabs(e_new - e_old) < tol) conv = true;
-      if (sc[SC_STOP] != 0.0) conv = true;  // invariant subspace reached
-      e_old = e_new;
-      have = true;
-    }
-  }
-  if (ndone == 0) {
-    set_error("edigpu_lanczos_eigh: zero start vector");
-    return fail_all();
-  }
-  *eval = e_old;
-  if (niter_done) *niter_done = ndone;
-  if (evec_host) {
-    // Ritz vector = sum_k y_k v_k : regenerate the v_k with the same (deterministic) kernels
-    const int kmin = (int)(std::min_element(d.begin(), d.end()) - d.begin());
-    std::vector<double> y(ndone);
-    for (int k = 0; k < ndone; k++) y[k] = z[(size_t)kmin * ndone + k];
-    double* d_acc = nullptr;
-    if (hipMalloc((void**)&d_acc, vbytes) != hipSuccess) {
-      set_error("edigpu_lanczos_eigh: out of device memory");
-      return fail_all();
-    }
-    (void)hipMemsetAsync(d_acc, 0, vbytes, st);
-    int rc = 0;
-    if (keep && (int)kept.size() * kKeep >= ndone) {
-      for (int it = 0; it < ndone && !rc; it++)
-        rc |= lz_axpy_coef(d_acc, kept[(size_t)(it / kKeep)] + (size_t)(it % kKeep) * (size_t)len, len, y[it], s->d_scal, -1, st);
-    } else {
-      (void)hipMemcpyAsync(s->d_vin, d_v0, vbytes, hipMemcpyDeviceToDevice, st);
-      if (lanczos_prepare(s, ndone, kBreakdown, st)) {
-        (void)hipFree(d_acc);
-        return fail_all();
-      }
-      for (int it = 0; it < ndone && !rc; it++) {
-        // same kernels, same order as the first pass => bitwise the same Lanczos vectors
-        rc |= lanczos_step(s, it, ndone, st);
-        rc |= lz_axpy_coef(d_acc, s->d_vin, len, y[it], s->d_scal, -1, st);
-      }
-    }
-    // normalise
-    if (!rc) rc |= lz_norm_begin(d_acc, len, s->d_partial, s->d_scal, st);
-    if (!rc) rc |= lanczos_fetch(s, d_acc, evec_host, st);
-    if (hipStreamSynchronize(st) != hipSuccess) rc = 1;
-    (void)hipFree(d_acc);
-    if (rc) {
-      if (g_err.empty()) set_error("edigpu_lanczos_eigh: second pass failed");
-      return fail_all();
-    }
-  }
-  drop_kept();
-  (void)hipFree(d_v0);
-  return 0;
-}
-
-// cyclic Jacobi for a small dense symmetric matrix (row-major n x n, destroyed); eigenvalues ascending in
-// w, eigenvectors in the COLUMNS of z (row-major n x n)
-static void jacobi_eigh(int n, std::vector<double>& a, std::vector<double>& w, std::vector<double>& z) {
-  z.assign((size_t)n * n, 0.0);
-  for (int i = 0; i < n; i++) z[(size_t)i * n + i] = 1.0;
-  for (int sweep = 0; sweep < 60; sweep++) {
-    double off = 0.0, diag = 0.0;
-    for (int i = 0; i < n; i++) {
-      diag += a[(size_t)i * n + i] * a[(size_t)i * n + i];
-      for (int j = i + 1; j < n; j++) off += a[(size_t)i * n + j] * a[(size_t)i * n + j];
-    }
-    if (off <= 1e-32 * (diag + off) || off == 0.0) break;
-    for (int p = 0; p < n - 1; p++)
-      for (int q = p + 1; q < n; q++) {
-        const double apq = a[(size_t)p * n + q];
-        if (apq == 0.0) continue;
-        const double theta = (a[(size_t)q * n + q] - a[(size_t)p * n + p]) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-        for (int k = 0; k < n; k++) {
-          const double akp = a[(size_t)k * n + p], akq = a[(size_t)k * n + q];
-          a[(size_t)k * n + p] = c * akp - sn * akq;
-          a[(size_t)k * n + q] = sn * akp + c * akq;
-        }
-        for (int k = 0; k < n; k++) {
-          const double apk = a[(size_t)p * n + k], aqk = a[(size_t)q * n + k];
-          a[(size_t)p * n + k] = c * apk - sn * aqk;
-          a[(size_t)q * n + k] = sn * apk + c * aqk;
-        }
-        for (int k = 0; k < n; k++) {
-          const double zkp = z[(size_t)k * n + p], zkq = z[(size_t)k * n + q];
-          z[(size_t)k * n + p] = c * zkp - sn * zkq;
-          z[(size_t)k * n + q] = sn * zkp + c * zkq;
-        }
-      }
-  }
-  std::vector<int> ord(n);
-  for (int i = 0; i < n; i++) ord[i] = i;
-  std::sort(ord.begin(), ord.end(), [&](int i, int j) { return a[(size_t)i * n + i] < a[(size_t)j * n + j]; });
-  w.resize(n);
-  std::vector<double> zs((size_t)n * n);
-  for (int c = 0; c < n; c++) {
-    w[c] = a[(size_t)ord[c] * n + ord[c]];
-    for (int k = 0; k < n; k++) zs[(size_t)k * n + c] = z[(size_t)k * n + ord[c]];
-  }
-  z.swap(zs);
-}
-
-// Thick-restart Lanczos with full re-orthogonalisation: the lowest `neigen` eigenpairs from an
-// ncv-dimensional basis -- the job the reference gives to ARPACK (sp_eigh, ED_NORMAL/ED_DIAG_NORMAL.f90:179-196; with
-// MpiComm, :221-242, to PARPACK).  One routine for whole sectors and for shards: `n` elements (`len` doubles) of every
-// vector live on this rank, ops.apply is the product on them, ops.allreduce sums small device buffers over the ranks
-// (empty: a single rank).  Every decision is taken from all-reduced numbers, so the ranks stay in step.
-}  // extern "C"
-namespace edigpu {
-int trl_solve(int device, hipStream_t st, int cplx, int64_t n, int64_t len, int64_t nglobal, const TrlOps& ops, int neigen, int ncv,
-              double tol, int maxrestart, const double* v0, uint64_t seed_offset, double* evals, double* evecs,
-              int* nconv_out, int* nmatvec_out) {
-  EDIGPU_HIP(hipSetDevice(device));
-  const LoopSwitches lz = LoopSwitches::sample();
-  const bool multi = (bool)ops.allreduce;
-  auto reduce = [&](double* dev, size_t cnt) -> int { return multi ? ops.allreduce(dev, cnt, st) : 0; };
-  if ((int64_t)neigen > nglobal) neigen = (int)nglobal;
-  int m = ncv > 0 ? ncv : std::max(2 * neigen + 10, 20);
-  if (m < neigen + 2) m = neigen + 2;
-  if (m > 128) m = 128;
-  if ((int64_t)m > nglobal) m = (int)nglobal;
-  if (tol <= 0.0) tol = 1e-12;
-  if (maxrestart <= 0) maxrestart = 300;
-  const size_t vbytes = (size_t)len * sizeof(double);
-  struct Bufs {
-    double *Q = nullptr, *Qt = nullptr, *h = nullptr, *part = nullptr, *Y = nullptr;
-    ~Bufs() { (void)hipFree(Q); (void)hipFree(Qt); (void)hipFree(h); (void)hipFree(part); (void)hipFree(Y); }
-  } b;
-  EDIGPU_HIP(hipMalloc((void**)&b.Q, vbytes * (size_t)(m + 1)));
-  EDIGPU_HIP(hipMalloc((void**)&b.h, sizeof(double) * 2 * (size_t)(m + 40)));
-  EDIGPU_HIP(hipMalloc((void**)&b.part, sizeof(double) * (size_t)trl_partial_doubles()));
-  EDIGPU_HIP(hipMalloc((void**)&b.Y, sizeof(double) * (size_t)m * m));
-  auto q = [&](int j) { return b.Q + (size_t)j * len; };
-  std::vector<double> hh(2 * (size_t)(m + 40));
-  auto norm_of = [&](double* w, double& out) -> int {
-    if (trl_norm2(cplx, n, w, b.h, b.part, st) || reduce(b.h, 2)) return 1;
-    EDIGPU_HIP(hipMemcpyAsync(hh.data(), b.h, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-    EDIGPU_HIP(hipStreamSynchronize(st));
-    out = sqrt(std::max(hh[0], 0.0));
-    return 0;
-  };
-  // start vector
-  if (v0) {
-    EDIGPU_HIP(hipMemcpyAsync(q(0), v0, vbytes, hipMemcpyDefault, st));
-  } else if (lz_fill_random(q(0), len, 0x7e57ab1eull + seed_offset, st)) {
-    return 1;
-  }
-  double nrm = 0.0;
-  if (norm_of(q(0), nrm)) return 1;
-  if (nrm == 0.0) {
-    set_error("edigpu_lanczos_eigh_multi: zero start vector");
-    return 1;
-  }
-  if (trl_scale(len, q(0), 1.0 / nrm, st)) return 1;
-
-  std::vector<double> T((size_t)m * m, 0.0), Tw, theta, Y;
-  int k = 0, meff = m, nmv = 0, nconv = 0, stalled = 0;
-  double beta_last = 0.0, best_worst = 1e300;
-  bool invariant = false;
-  // per cycle the Gram-Schmidt coefficients (two passes) and the squared norms stay on the device and are
-  // fetched once: no host synchronisation inside the Lanczos steps
-  const size_t hstride = 2 * (size_t)(m + 40);
-  double *d_coef = nullptr, *d_nrm = nullptr;
-  EDIGPU_HIP(hipMalloc((void**)&d_coef, sizeof(double) * 2 * hstride * (size_t)m));
-  EDIGPU_HIP(hipMalloc((void**)&d_nrm, sizeof(double) * (2 * (size_t)m + 80)));  // the reduction writes 2 * kTrlNC slots
-  struct Free2 {
-    double *&a, *&b;
-    ~Free2() { (void)hipFree(a); (void)hipFree(b); }
-  } free2{d_coef, d_nrm};
-  std::vector<double> hcoef(2 * hstride * (size_t)m), hnrm(2 * (size_t)m + 80);
-  // Classical Gram-Schmidt twice on every step (CGS2).  The variant that skips the second pass when the first one
-  // removed little (LoopSwitches::trl_onepass, criterion |w_new|^2 >= 0.5 |w_old|^2) saves up to half the basis traffic
-  // but was found to let the restart vector drift out of orthogonality (2e-13 after the first cycle with the
-  // earlier 1 % criterion, x1000 per restart: Ritz values below the spectrum after five restarts on a 36-dimensional
-  // sector), so it is not the default.
-  const bool twopass = !lz.trl_onepass;
-  // LoopSwitches::trl_full: full CGS2 on every step (the round-2 solver)
-  const bool selective = !lz.trl_full && !lz.trl_onepass;
-  constexpr double kSelThr = 1e-14;
-  // coefficients below thr_skip * |w_new| are left in w: three orders below the requested residual
-  const double thr_skip = lz.trl_thr.value_or(1e-3 * tol);
-  int* d_skip = nullptr;
-  EDIGPU_HIP(hipMalloc((void**)&d_skip, sizeof(int)));
-  struct Free1 {
-    int*& p;
-    ~Free1() { (void)hipFree(p); }
-  } free1{d_skip};
-  for (int restart = 0; restart <= maxrestart; restart++) {
-    invariant = false;
-    meff = m;
-    EDIGPU_HIP(hipMemsetAsync(d_coef, 0, sizeof(double) * 2 * hstride * (size_t)m, st));
-    for (int j = k; j < m; j++) {
-      double* w = q(j + 1);
-      if (ops.apply(q(j), w, st)) return 1;
-      nmv++;
-      // classical Gram-Schmidt against q_0..q_j, twice; the coefficients are column j of Q^H H Q
-      double* c1 = d_coef + (size_t)(2 * j) * hstride;
-      double* c2 = d_coef + (size_t)(2 * j + 1) * hstride;
-      // second pass only when the first one removed more than 99 % of |w|^2 ("twice is enough" with eta = 0.1:
-      // orthogonality ~10 eps otherwise); decided on the device, c2 stays zero when skipped
-      // coefficients below 1e-11 |w_new| (pure rounding: the three-term recurrence makes them zero) are not
-      // subtracted, their basis vectors not read (trl_decide_kernel)
-      if (selective && j > k) {
-        // Selective re-orthogonalisation (every step but the first after a restart).  Pass A: classical Gram-Schmidt
-        // against the two vectors the three-term recurrence couples to, q_(j-1) and q_j -- the only directions in
-        // which a large component is removed and cancellation can leave an error.  Pass B: the dots against the WHOLE
-        // basis (for those two the second of "twice is enough", for all others a first pass on components that are
-        // small next to |w|: one pass is accurate), and only the coefficients above kSelThr |w| are subtracted: what
-        // is skipped leaves an orthogonality error of that size (1e-14), the basis vectors of zero coefficients are
-        // not read.  ~j + 13 vector passes per step instead of the 4 (j + 1) of the full CGS2 it replaces.
-        const int nl = std::min(2, j + 1), l0 = j + 1 - nl;
-        if (trl_dots(cplx, n, nl, q(l0), len, w, c1 + 2 * l0, b.part, st) || reduce(c1 + 2 * l0, 2 * (size_t)nl) ||
-            trl_subtract(cplx, n, nl, q(l0), len, c1 + 2 * l0, w, st))
-          return 1;
-        if (trl_dots(cplx, n, j + 2, b.Q, len, w, c2, b.part, st) || reduce(c2, 2 * (size_t)(j + 2)) ||
-            trl_filter(c2, j + 1, kSelThr * kSelThr, st) || trl_subtract(cplx, n, j + 1, b.Q, len, c2, w, st))
-          return 1;
-      } else if (twopass || multi) {
-        // (shards: the coefficients Q^H w are summed over the ranks between the dots and the subtraction -- one
-        // all-reduce of j + 1 numbers per pass, the k-element reduce of SciFortran's MPI Lanczos)
-        if (trl_dots(cplx, n, j + 1, b.Q, len, w, c1, b.part, st) || reduce(c1, 2 * (size_t)(j + 1)) ||
-            trl_subtract(cplx, n, j + 1, b.Q, len, c1, w, st))
-          return 1;
-        if (trl_dots(cplx, n, j + 1, b.Q, len, w, c2, b.part, st) || reduce(c2, 2 * (size_t)(j + 1)) ||
-            trl_subtract(cplx, n, j + 1, b.Q, len, c2, w, st))
-          return 1;
-      } else {
-        if (trl_dots(cplx, n, j + 2, b.Q, len, w, c1, b.part, st)) return 1;  // column j+1 is w itself: <w|w>
-        if (trl_decide(c1, j + 1, 0.5, thr_skip * thr_skip, b.h, d_skip, st)) return 1;
-        if (trl_subtract(cplx, n, j + 1, b.Q, len, b.h, w, st)) return 1;
-        if (trl_orthogonalize(cplx, n, j + 1, b.Q, len, w, c2, b.part, st, d_skip)) return 1;
-      }
-      if (trl_norm2(cplx, n, w, d_nrm + 2 * j, b.part, st) || reduce(d_nrm + 2 * j, 2)) return 1;
-      if (vec_scale(len, w, d_nrm + 2 * j, st)) return 1;  // w / sqrt(<w|w>) with the norm read on the device
-    }
-    EDIGPU_HIP(hipMemcpyAsync(hcoef.data(), d_coef, sizeof(double) * hcoef.size(), hipMemcpyDeviceToHost, st));
-    EDIGPU_HIP(hipMemcpyAsync(hnrm.data(), d_nrm, sizeof(double) * hnrm.size(), hipMemcpyDeviceToHost, st));
-    EDIGPU_HIP(hipStreamSynchronize(st));
-    for (int j = k; j < m; j++) {
-      const double* c1 = &hcoef[(size_t)(2 * j) * hstride];
-      const double* c2 = &hcoef[(size_t)(2 * j + 1) * hstride];
-      for (int i = 0; i <= j; i++) {
-        T[(size_t)i * m + j] = c1[2 * i] + c2[2 * i];
-        T[(size_t)j * m + i] = T[(size_t)i * m + j];
-      }
-      const double beta = sqrt(std::max(hnrm[2 * j], 0.0));
-      beta_last = beta;
-      const double scale = fabs(T[(size_t)j * m + j]) + 1.0;
-      if (!(beta > 1e-13 * scale)) {  // invariant subspace: q_0..q_j is closed under H (later steps are discarded)
-        meff = j + 1;
-        invariant = true;
-        break;
-      }
-    }
-    // Rayleigh-Ritz on the meff x meff projection
-    Tw.assign((size_t)meff * meff, 0.0);
-    for (int i = 0; i < meff; i++)
-      for (int j = 0; j < meff; j++) Tw[(size_t)i * meff + j] = T[(size_t)i * m + j];
-    jacobi_eigh(meff, Tw, theta, Y);
-    const int want = std::min(neigen, meff);
-    if (lz.trl_debug) {
-      fprintf(stderr, "trl: restart %d k %d meff %d invariant %d beta_last %.3e theta0 %.6e\n  beta:", restart, k, meff,
-              (int)invariant, beta_last, theta.empty() ? 0.0 : theta[0]);
-      for (int j = k; j < meff; j++) fprintf(stderr, " %.2e", sqrt(std::max(hnrm[2 * j], 0.0)));
-      if (!cplx && n <= 4096) {  // orthonormality of the basis q_0..q_meff
-        std::vector<double> hq((size_t)(meff + 1) * len);
-        EDIGPU_HIP(hipMemcpy(hq.data(), b.Q, hq.size() * sizeof(double), hipMemcpyDeviceToHost));
-        double dev = 0.0;
-        int wi = 0, wj = 0;
-        for (int i = 0; i <= meff; i++)
-          for (int j2 = 0; j2 <= i; j2++) {
-            double d = 0.0;
-            for (int64_t e = 0; e < n; e++) d += hq[(size_t)i * len + e] * hq[(size_t)j2 * len + e];
-            d = fabs(d - (i == j2 ? 1.0 : 0.0));
-            if (d > dev) dev = d, wi = i, wj = j2;
-          }
-        fprintf(stderr, "\n  |Q^T Q - 1| max %.2e at (%d,%d)", dev, wi, wj);
-      }
-      fprintf(stderr, "\n  theta / res:");
-      for (int i = 0; i < std::min(meff, 6); i++)
-        fprintf(stderr, " %.12f / %.1e", theta[i], fabs(beta_last * Y[(size_t)(meff - 1) * meff + i]));
-      fprintf(stderr, "\n");
-    }
-    nconv = 0;
-    bool counting = true;
-    double worst = 0.0;  // largest relative residual among the wanted pairs
-    for (int i = 0; i < want; i++) {
-      const double res = invariant ? 0.0 : fabs(beta_last * Y[(size_t)(meff - 1) * meff + i]);
-      const double rel = res / std::max(fabs(theta[i]), 1.0);
-      worst = std::max(worst, rel);
-      if (counting && rel <= tol) nconv++;
-      else counting = false;
-    }
-    if (nconv >= want || invariant || restart == maxrestart) break;
-    // A tolerance below what rounding allows (the reference's default lanc_tolerance is 1e-18) is never met: the
-    // residuals fall to ~1e-13 |H|, and further restarts only feed rounding noise back into the basis (measured: they
-    // grow by ~3x per restart from there and the Ritz values are lost after ~30).  Stop once the wanted residuals are at
-    // rounding level and two restarts in a row have not improved on the best seen; nconv then reports what meets tol.
-    if (worst < best_worst) {
-      best_worst = worst;
-      stalled = 0;
-    } else if (best_worst <= 1e-8 && ++stalled >= 2) {
-      break;
-    }
-    // thick restart: keep the wanted Ritz vectors plus half of the rest, then the residual vector
-    int kk = want + (meff - want) / 2;
-    if (kk > meff - 1) kk = meff - 1;
-    if (kk < 1) kk = 1;
-    // the rotated Ritz vectors land in the second basis buffer, the residual vector follows them there, and the
-    // two buffers change roles (no copy back)
-    if (!b.Qt) EDIGPU_HIP(hipMalloc((void**)&b.Qt, vbytes * (size_t)(m + 1)));
-    EDIGPU_HIP(hipMemcpyAsync(b.Y, Y.data(), sizeof(double) * (size_t)meff * meff, hipMemcpyHostToDevice, st));
-    if (trl_rotate_basis(len, meff, kk, b.Q, len, b.Y, meff, b.Qt, len, st)) return 1;
-    EDIGPU_HIP(hipMemcpyAsync(b.Qt + (size_t)kk * len, q(meff), vbytes, hipMemcpyDeviceToDevice, st));
-    std::swap(b.Q, b.Qt);
-    std::fill(T.begin(), T.end(), 0.0);
-    for (int i = 0; i < kk; i++) T[(size_t)i * m + i] = theta[i];
-    k = kk;
-  }
-  const int want = std::min(neigen, meff);
-  for (int i = 0; i < neigen; i++) evals[i] = i < want ? theta[i] : 0.0;
-  if (nconv_out) *nconv_out = nconv;
-  if (nmatvec_out) *nmatvec_out = nmv;
-  if (evecs) {
-    if (!b.Qt) EDIGPU_HIP(hipMalloc((void**)&b.Qt, vbytes * (size_t)(m + 1)));
-    EDIGPU_HIP(hipMemcpyAsync(b.Y, Y.data(), sizeof(double) * (size_t)meff * meff, hipMemcpyHostToDevice, st));
-    if (trl_rotate_basis(len, meff, want, b.Q, len, b.Y, meff, b.Qt, len, st)) return 1;
-    EDIGPU_HIP(hipMemcpyAsync(evecs, b.Qt, vbytes * (size_t)want, hipMemcpyDefault, st));
-  }
-  EDIGPU_HIP(hipStreamSynchronize(st));
-  return 0;
-}
-}  // namespace edigpu
-extern "C" {
-
-int edigpu_lanczos_eigh_multi(edigpu_handle s, int neigen, int ncv, double tol, int maxrestart, const double* v0,
-                              double* evals, double* evecs, int* nconv_out, int* nmatvec_out) {
-  if (!s || !evals || neigen <= 0) {
-    set_error("edigpu_lanczos_eigh_multi: bad argument");
-    return 1;
-  }
-  if (single_shard(s, "edigpu_lanczos_eigh_multi")) return 1;
-  EDIGPU_HIP(hipSetDevice(s->device));
-  if (ensure_workspace(s)) return 1;
-  TrlOps ops;
-  ops.apply = [s](const double* in, double* out, hipStream_t st) { return apply_any(s, in, in, out, 3, st); };
-  return trl_solve(s->device, s->stream, s->is_complex, s->nloc, s->ws_len, s->nloc, ops, neigen, ncv, tol, maxrestart, v0, 0, evals,
-                   evecs, nconv_out, nmatvec_out);
-}
-
-int edigpu_vec_work_doubles(void) { return kRedBlocks; }
-
-int edigpu_vec_rotate(int64_t n, double* vin_dev, double* vout_dev, const double* beta2_dev, void* stream) {
-  if (n < 0 || !vin_dev || !vout_dev || !beta2_dev) {
-    set_error("edigpu_vec_rotate: bad argument");
-    return 1;
-  }
-  return vec_rotate(n, vin_dev, vout_dev, beta2_dev, (hipStream_t)stream);
-}
-
-int edigpu_vec_add_dot(int64_t n, const double* vin_dev, double* vout_dev, const double* tmp_dev,
-                       double* out_dev, double* work_dev, void* stream) {
-  if (n < 0 || !vin_dev || !vout_dev || !tmp_dev || !out_dev || !work_dev) {
-    set_error("edigpu_vec_add_dot: bad argument");
-    return 1;
-  }
-  return vec_add_dot(n, vin_dev, vout_dev, tmp_dev, out_dev, work_dev, (hipStream_t)stream);
-}
-
-int edigpu_vec_axpy_nrm2(int64_t n, const double* vin_dev, double* vout_dev, const double* alpha_dev,
-                         double* out_dev, double* work_dev, void* stream) {
-  if (n < 0 || !vin_dev || !vout_dev || !alpha_dev || !out_dev || !work_dev) {
-    set_error("edigpu_vec_axpy_nrm2: bad argument");
-    return 1;
-  }
-  return vec_axpy_nrm2(n, vin_dev, vout_dev, alpha_dev, out_dev, work_dev, (hipStream_t)stream);
-}
-
-int edigpu_vec_rotate_lazy(int64_t n, double* vin_dev, double* vout_dev, const double* ab_dev, void* stream) {
-  if (n < 0 || !vin_dev || !vout_dev || !ab_dev) {
-    set_error("edigpu_vec_rotate_lazy: bad argument");
-    return 1;
-  }
-  return vec_rotate_lazy(n, vin_dev, vout_dev, ab_dev, (hipStream_t)stream);
-}
-
-int edigpu_vec_add_dot2(int64_t n, const double* vin_dev, double* vout_dev, const double* tmp_dev, double* out2_dev,
-                        double* work_dev, void* stream) {
-  if (n < 0 || !vin_dev || !vout_dev || !tmp_dev || !out2_dev || !work_dev) {
-    set_error("edigpu_vec_add_dot2: bad argument");
-    return 1;
-  }
-  return vec_add_dot2(n, vin_dev, vout_dev, tmp_dev, out2_dev, work_dev, (hipStream_t)stream);
-}
-
-int edigpu_vec_scale(int64_t n, double* v_dev, const double* nrm2_dev, void* stream) {
-  if (n < 0 || !v_dev || !nrm2_dev) {
-    set_error("edigpu_vec_scale: bad argument");
-    return 1;
-  }
-  return vec_scale(n, v_dev, nrm2_dev, (hipStream_t)stream);
-}
-
-int edigpu_time_apply(edigpu_handle s, int warmup, int steps, int lanczos, double* ms_per_step) {
-  if (!s || steps <= 0 || !ms_per_step) {
-    set_error("edigpu_time_apply: bad argument");
-    return 1;
-  }
-  if (single_shard(s, "edigpu_time_apply")) return 1;
-  if (s->kind == 4 && s->sub_d && lanczos) return edigpu_time_apply(s->sub_d, warmup, steps, lanczos, ms_per_step);
-  EDIGPU_HIP(hipSetDevice(s->device));
-  if (ensure_workspace(s)) return 1;
-  hipStream_t st = s->stream;
-  const int total = warmup + steps;
-  if (lanczos_prepare(s, std::max(total, 1), 0.0, st)) return 1;
-  if (lanczos) {  // 1: Lanczos steps; 2: the plain product as the loop computes it (panel-major vectors where it uses them)
-    if (lanczos_seed(s, nullptr, 12345ull, st)) return 1;
-    if (lz_norm_begin(s->d_vin, s->lz_len, s->d_partial, s->d_scal, st)) return 1;
-  } else {  // the boundary product (edigpu_apply_dev): vectors in the natural layout
-    if (lz_fill_random(s->d_vin, s->ws_len, 12345ull, st)) return 1;
-    if (lz_norm_begin(s->d_vin, s->ws_len, s->d_partial, s->d_scal, st)) return 1;
-  }
-  hipEvent_t e0, e1;
-  EDIGPU_HIP(hipEventCreate(&e0));
-  EDIGPU_HIP(hipEventCreate(&e1));
-  int rc = 0;
-  for (int it = 0; it < total && !rc; it++) {
-    if (it == warmup) rc |= (hipEventRecord(e0, st) != hipSuccess);
-    if (lanczos == 2) {
-      rc |= s->lz_blocked ? launch_normal_blocked(s, s->d_vin, s->d_tmp, st) : apply_any(s, s->d_vin, s->d_vin, s->d_tmp, 3, st);
-    } else if (lanczos) {
-      rc |= lanczos_step(s, it, total, st);
-    } else {
-      // fixed source vector -> fixed destination: the plain SpMV measurement
-      rc |= apply_any(s, s->d_vin, s->d_vin, s->d_tmp, 3, st);
-    }
-  }
-  if (!rc) rc |= (hipEventRecord(e1, st) != hipSuccess);
-  if (!rc) rc |= (hipEventSynchronize(e1) != hipSuccess);
-  float ms = 0.f;
-  if (!rc) rc |= (hipEventElapsedTime(&ms, e0, e1) != hipSuccess);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (rc) {
-    if (g_err.empty()) set_error("edigpu_time_apply: HIP failure");
-    return 1;
-  }
-  *ms_per_step = (double)ms / (double)steps;
-  return 0;
-}
-
-int edigpu_apply_loop_d(edigpu_handle s, int64_t nloc, const double* v_host, double* hv_host) {
-  if (!s || !v_host || !hv_host) {
-    set_error("edigpu_apply_loop_d: NULL argument");
-    return 1;
-  }
-  if (single_shard(s, "edigpu_apply_loop_d")) return 1;
-  if (s->is_complex || s->kind == 4 || nloc != s->nloc) {
-    set_error("edigpu_apply_loop_d: needs a real handle and a vector of its local rows");
-    return 1;
-  }
-  EDIGPU_HIP(hipSetDevice(s->device));
-  if (ensure_workspace(s)) return 1;
-  hipStream_t st = s->stream;
-  if (lanczos_prepare(s, 1, 0.0, st)) return 1;  // chooses the layout
-  if (lanczos_seed(s, v_host, 0, st)) return 1;
-  // (the result goes to d_vout: d_tmp is what lanczos_fetch converts through)
-  if (s->lz_blocked ? launch_normal_blocked(s, s->d_vin, s->d_vout, st) : apply_any(s, s->d_vin, s->d_vin, s->d_vout, 3, st))
-    return 1;
-  if (lanczos_fetch(s, s->d_vout, hv_host, st)) return 1;
-  EDIGPU_HIP(hipStreamSynchronize(st));
-  return 0;
-}
-
-int edigpu_tile_task_map(int32_t npanels, int32_t blocks_per_panel, int32_t balanced, int32_t* grid, int32_t* np,
-                         int32_t* panel, int32_t* chunk, int32_t* pos) {
-  if (npanels < 1 || blocks_per_panel < 1 || !grid || !np ||
-      ((int64_t)npanels + 7) / 8 * 8 * (int64_t)blocks_per_panel > INT32_MAX) {
-    set_error("edigpu_tile_task_map: bad argument");
-    return 1;
-  }
-  const TileMap m = plan_tile_map(npanels, blocks_per_panel, balanced != 0);
-  *grid = m.grid;
-  *np = m.np;
-  for (int wg = 0; wg < m.grid; wg++) {
-    int pn, ch, ps;
-    if (!tile_task_of(m, npanels, blocks_per_panel, wg, pn, ch, ps)) pn = -1;
-    if (panel) panel[wg] = pn;
-    if (chunk) chunk[wg] = ch;
-    if (pos) pos[wg] = ps;
-  }
-  return 0;
-}
-
-int edigpu_ell16_images(int64_t nrow, const int64_t* rowptr, const int32_t* col, const double* val, int64_t* info,
-                        uint32_t* pk16, uint32_t* pk16o, int64_t* owned_col) {
-  if (nrow < 1 || !rowptr || !info || (rowptr[nrow] > 0 && (!col || !val))) {
-    set_error("edigpu_ell16_images: bad argument");
-    return 1;
-  }
-  HostCsr a;
-  a.nrow = a.ncol = nrow;
-  a.rowptr.assign(rowptr, rowptr + nrow + 1);
-  a.col.assign(col, col + rowptr[nrow]);
-  a.val.assign(val, val + rowptr[nrow]);
-  const HostEll h = encode_ell(a, true, true, true);
-  info[0] = h.width;
-  info[1] = h.pitch;
-  info[2] = h.pitch16o;
-  info[3] = (int64_t)h.pk16.size();
-  info[4] = (int64_t)h.pk16o.size();
-  if (pk16) std::copy(h.pk16.begin(), h.pk16.end(), pk16);
-  if (pk16o) std::copy(h.pk16o.begin(), h.pk16o.end(), pk16o);
-  if (owned_col)
-    for (int64_t pos = 0; pos < h.pitch16o; pos++) owned_col[pos] = ell16_owned_col(pos);
-  return 0;
-}
-
-int edigpu_finalize_ab(int32_t np, const double* partial, int64_t n, const double* P, const double* Q, int32_t nscal,
-                       double* scal, int32_t iter, int32_t nlanc) {
-  if (np < 1 || np > kMaxPartials || !partial || n < 1 || !P || !Q || !scal || nlanc < 1 || iter >= nlanc ||
-      nscal < SC_AB + 2 * nlanc) {
-    set_error("edigpu_finalize_ab: bad argument");
-    return 1;
-  }
-  if (ensure_device()) return 1;
-  EDIGPU_HIP(hipSetDevice(g_device));
-  double *d_part = nullptr, *d_p = nullptr, *d_q = nullptr, *d_scal = nullptr;
-  int rc = dev_upload(&d_part, partial, (size_t)3 * np) || dev_upload(&d_p, P, (size_t)n) ||
-           dev_upload(&d_q, Q, (size_t)n) || dev_upload(&d_scal, scal, (size_t)nscal);
-  if (!rc) rc = lz_finalize_alpha_beta(d_p, d_q, n, d_part, np, d_scal, iter, nlanc, nullptr);
-  if (!rc && hipDeviceSynchronize() != hipSuccess) {
-    set_error("edigpu_finalize_ab: the kernel failed");
-    rc = 1;
-  }
-  if (!rc && hipMemcpy(scal, d_scal, (size_t)nscal * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
-    set_error("edigpu_finalize_ab: download failed");
-    rc = 1;
-  }
-  dev_free(d_part);
-  dev_free(d_p);
-  dev_free(d_q);
-  dev_free(d_scal);
-  return rc;
 }
 
 int edigpu_dev_alloc(int64_t bytes, void** dev_ptr) {
@@ -3226,70 +286,6 @@ int edigpu_dev_download(void* dst_host, const void* src_dev, int64_t bytes) {
   return 0;
 }
 
-int edigpu_membw(int64_t bytes, double* gbs3) {
-  if (!gbs3 || bytes < (1 << 20)) {
-    set_error("edigpu_membw: bad argument");
-    return 1;
-  }
-  if (ensure_device()) return 1;
-  EDIGPU_HIP(hipSetDevice(g_device));
-  return measure_membw(bytes, gbs3);
-}
-
-int edigpu_lanczos_bench(edigpu_handle s, int warmup, int steps, double* ms_wall_per_step,
-                         double* ms_hv_per_launch) {
-  if (!s || steps <= 0 || warmup < 0 || !ms_wall_per_step || !ms_hv_per_launch) {
-    set_error("edigpu_lanczos_bench: bad argument");
-    return 1;
-  }
-  if (single_shard(s, "edigpu_lanczos_bench")) return 1;
-  if (s->kind == 4 && s->sub_d) return edigpu_lanczos_bench(s->sub_d, warmup, steps, ms_wall_per_step, ms_hv_per_launch);
-  EDIGPU_HIP(hipSetDevice(s->device));
-  if (ensure_workspace(s)) return 1;
-  hipStream_t st = s->stream;
-  const int total = warmup + steps;
-  if (lanczos_prepare(s, total, 0.0, st)) return 1;
-  if (lanczos_seed(s, nullptr, 12345ull, st)) return 1;
-  if (lz_norm_begin(s->d_vin, s->lz_len, s->d_partial, s->d_scal, st)) return 1;
-  int rc = 0;
-  // the product as the loop computes it: on the panel-major vectors when the recurrence runs on them
-  auto hv_probe = [&]() -> int {
-    if (s->lz_blocked) return launch_normal_blocked(s, s->d_vin, s->d_tmp, st);
-    return apply_any(s, s->d_vin, s->d_vin, s->d_tmp, 3, st);
-  };
-  // (a launch-bound sector replays its steps from a captured graph, as edigpu_lanczos_tridiag does: lanczos_run)
-  rc |= lanczos_run(s, 0, warmup, total, st);
-  if (!rc) rc |= (hipStreamSynchronize(st) != hipSuccess);
-  const auto t0 = std::chrono::steady_clock::now();
-  if (!rc) rc |= lanczos_run(s, warmup, total, total, st);
-  if (!rc) rc |= (hipStreamSynchronize(st) != hipSuccess);
-  const auto t1 = std::chrono::steady_clock::now();
-  // H*v launches alone (the Lanczos vector of the last step as input), HIP events around each
-  std::vector<hipEvent_t> ev(2 * (size_t)steps);
-  for (auto& e : ev) EDIGPU_HIP(hipEventCreate(&e));
-  for (int k = 0; k < 3 && !rc; k++) rc |= hv_probe();
-  for (int k = 0; k < steps && !rc; k++) {
-    rc |= (hipEventRecord(ev[2 * k], st) != hipSuccess);
-    rc |= hv_probe();
-    rc |= (hipEventRecord(ev[2 * k + 1], st) != hipSuccess);
-  }
-  if (!rc) rc |= (hipStreamSynchronize(st) != hipSuccess);
-  double hv = 0.0;
-  for (int k = 0; k < steps && !rc; k++) {
-    float ms = 0.f;
-    rc |= (hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]) != hipSuccess);
-    hv += ms;
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  if (rc) {
-    if (g_err.empty()) set_error("edigpu_lanczos_bench: HIP failure");
-    return 1;
-  }
-  *ms_wall_per_step = std::chrono::duration<double, std::milli>(t1 - t0).count() / steps;
-  *ms_hv_per_launch = hv / steps;
-  return 0;
-}
-
 int edigpu_destroy(edigpu_handle s) {
   if (!s) return 0;
   (void)hipSetDevice(s->device);
@@ -3300,62 +296,31 @@ int edigpu_destroy(edigpu_handle s) {
   if (s->sub_s) edigpu_destroy(s->sub_s);
   if (s->sub_a) edigpu_destroy(s->sub_a);
   if (s->sub_d) edigpu_destroy(s->sub_d);
-  dev_free(s->d_cz);
-  dev_free(s->d_hd);
-  dev_free(s->d_gu);
-  dev_free(s->d_gd);
-  dev_free(s->d_mx_rowptr);
-  dev_free(s->d_tile_chunks);
-  dev_free(s->d_tile_lbeg);
+  dev_free_all(s->d_cz, s->d_hd, s->d_gu, s->d_gd, s->d_mx_rowptr, s->d_tile_chunks, s->d_tile_lbeg);
   if (s->lz_graph) (void)hipGraphExecDestroy(s->lz_graph);
-  dev_free(s->d_lzcnt);
-  dev_free(s->d_bl_meta);
-  dev_free(s->d_bl_lend);
-  dev_free(s->d_bl_ent);
-  dev_free(s->d_bl_wtab);
+  dev_free_all(s->d_lzcnt, s->d_bl_meta, s->d_bl_lend, s->d_bl_ent, s->d_bl_wtab);
   if (s->ib) {
     free_ib(s->ib);
     delete s->ib;
     s->ib = nullptr;
   }
-  dev_free(s->d_tl_meta);
-  dev_free(s->d_tl_col);
-  dev_free(s->d_tl_val);
-  dev_free(s->d_mx_col);
-  dev_free(s->d_mx_val);
-  dev_free(s->d_eux);
-  dev_free(s->d_ed);
-  dev_free(s->d_impd);
-  dev_free(s->d_ndcoef);
-  dev_free(s->d_jup);
-  dev_free(s->d_jdw);
+  dev_free_all(s->d_tl_meta, s->d_tl_col, s->d_tl_val, s->d_mx_col, s->d_mx_val);
+  dev_free_all(s->d_eux, s->d_ed, s->d_impd, s->d_ndcoef, s->d_jup, s->d_jdw);
   free_ell(s->up_ell);
   free_csr(s->dw);
   free_csr(s->nd);
   free_csr(s->loc);
   free_csr(s->nonloc);
-  for (const void* q : {(const void*)s->orbs.ell_col, (const void*)s->orbs.ell_val, (const void*)s->orbs.hd,
-                        (const void*)s->orbs.eax, (const void*)s->orbs.impbit, (const void*)s->orbs.xtab})
-    if (q) (void)hipFree(const_cast<void*>(q));
+  dev_free_all(s->orbs.ell_col, s->orbs.ell_val, s->orbs.hd, s->orbs.eax, s->orbs.impbit, s->orbs.xtab);
   s->orbs = OrbsArgs();
-  dev_free(s->d_dir_states);
-  dev_free(s->d_dir_offdw);
-  dev_free(s->d_dir_rkup);
-  dev_free(s->d_dir_terms);
-  dev_free(s->d_dir_tests);
-  dev_free(s->d_dir_dtab);
-  dev_free(s->d_dir_xtab);
+  dev_free_all(s->d_dir_states, s->d_dir_offdw, s->d_dir_rkup, s->d_dir_terms, s->d_dir_tests, s->d_dir_dtab, s->d_dir_xtab);
   free_occ(s);
   free_rdm(s);
   free_rdm_flat(s);
   free_ph(s);
   free_axisop(s);
   free_batch(s);
-  dev_free(s->d_vin);
-  dev_free(s->d_vout);
-  dev_free(s->d_tmp);
-  dev_free(s->d_partial);
-  dev_free(s->d_scal);
+  dev_free_all(s->d_vin, s->d_vout, s->d_tmp, s->d_partial, s->d_scal);
   delete s;
   return 0;
 }

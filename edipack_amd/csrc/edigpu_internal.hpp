@@ -4,6 +4,8 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -13,7 +15,18 @@
 
 namespace edigpu {
 
+// What a handle is (the values are part of the ABI: edigpu_info hands them out): normal mode (Kronecker), superc / nonsu2
+// stored as flat CSR / SELL, the same on the fly, ed_total_ud = F, _CMPLX_NORMAL (H = S + iA over real sub-handles).
+enum SectorKind : int { kNormal = 0, kFlat = 1, kDirect = 2, kOrbs = 3, kCmplxNormal = 4 };
+
+// the calling thread's error string (edigpu_last_error) and current device (edigpu_init): edigpu_capi.hip
 void set_error(const std::string& msg);
+#pragma GCC visibility push(hidden)
+bool have_error();
+int current_device();
+// 0 when a HIP device is usable, else 1 with the message set
+int ensure_device(int* count_out = nullptr);
+#pragma GCC visibility pop
 
 #define EDIGPU_HIP(call)                                                                     \
   do {                                                                                       \
@@ -206,8 +219,8 @@ void free_ph(edigpu_sector* s);
 struct AxisDev;
 void free_axisop(edigpu_sector* s);
 // true: this pair of handles is not the real, phonon-free, library-built normal-mode pair that apply_op_normal_kernel
-// serves; axisop_apply then makes every check and serves phonon, complex (kind 4) and ed_total_ud=F (kind 3) pairs.
-// cim = null: real coefficients; else complex ones on kind-4 handles (edigpu_apply_cops_normal_z).  Returns after the
+// serves; axisop_apply then makes every check and serves phonon, complex (kCmplxNormal) and ed_total_ud=F (kOrbs) pairs.
+// cim = null: real coefficients; else complex ones on kCmplxNormal handles (edigpu_apply_cops_normal_z).  Returns after the
 // stream has finished.
 bool axisop_route(const edigpu_sector* src, const edigpu_sector* dst);
 int axisop_apply(edigpu_sector* src, edigpu_sector* dst, const double* v_src, double* v_dst, int nops, const double* cre,
@@ -227,16 +240,12 @@ struct BatchDev {
   size_t scal_cap = 0;       // in doubles
 };
 void free_batch(edigpu_sector* s);
-// a flat or on-the-fly sector held whole on this GPU, without phonons, whose product has the fused Lanczos epilogue
-// (edigpu_capi.hip: the sectors whose single-seed step is rotate -> product with partials -> finalize)
-bool flat_lanczos_fusable(const edigpu_sector* s);
-
 }  // namespace edigpu
 
 struct edigpu_sector {
   explicit edigpu_sector(const edigpu::Switches& at_creation) : sw(at_creation) {}
   const edigpu::Switches sw;  // the environment the creating C-ABI call saw (switches.hpp): every set-up and launch choice reads it
-  int kind = 0;        // 0 normal (Kronecker), 1 flat CSR, 2 direct (on-the-fly superc/nonsu2), 3 orbs (ed_total_ud=F)
+  edigpu::SectorKind kind = edigpu::kNormal;
   int is_complex = 0;
   int device = 0;
   hipStream_t stream = nullptr;
@@ -259,10 +268,10 @@ struct edigpu_sector {
   uint8_t* d_impd = nullptr;    // dim_dw
   double* d_ndcoef = nullptr;   // nterms
   uint32_t* d_jup = nullptr;    // nterms * dim_up
-  // kind 4 (_CMPLX_NORMAL): H = S + iA as two real normal-mode handles + planar work vectors (6 * dim doubles)
+  // kCmplxNormal: H = S + iA as two real normal-mode handles + planar work vectors (6 * dim doubles)
   edigpu_sector* sub_s = nullptr;
   edigpu_sector* sub_a = nullptr;
-  // kind 4, preferred: the same operator as ONE real sector on the doubled up index 2 iup + (re | im)
+  // kCmplxNormal, preferred: the same operator as ONE real sector on the doubled up index 2 iup + (re | im)
   // (host_build.cpp: build_normal_doubled); the interleaved complex vectors are its real vectors
   edigpu_sector* sub_d = nullptr;
   double* d_cz = nullptr;
@@ -312,6 +321,10 @@ struct edigpu_sector {
   bool jz = false;                 // nonsu2 sector of Jz_basis=T: (Ntot, twoJz) = (sec_a, sec_b)
   bool built_by_library = false;   // made by edigpu_*_build: model, sec_a, sec_b are valid
   bool from_model() const { return built_by_library; }
+  bool is_normal_family() const { return kind == edigpu::kNormal || kind == edigpu::kCmplxNormal; }
+  bool is_flat_family() const { return kind == edigpu::kFlat || kind == edigpu::kDirect; }  // superc / nonsu2
+  bool has_phonons() const { return nph > 0; }
+  bool is_whole() const { return nloc == dim; }  // not a row shard
   // ---- flat ----
   edigpu::DevCsr loc, nonloc; // local rows; loc columns are shard-relative, nonloc global
   // ---- orbs (ed_total_ud = F) ----
@@ -358,3 +371,59 @@ struct edigpu_sector {
   unsigned int* d_lzcnt = nullptr;  // arrival counter of the in-kernel finalize (lz_finalize.hpp)
   int64_t ws_len = 0;           // in doubles per vector
 };
+
+namespace edigpu {
+
+// a handle under construction: edigpu_destroy (device memory, sub-handles with their parent) on every early return
+struct SectorDeleter {
+  void operator()(edigpu_sector* s) const { edigpu_destroy(s); }
+};
+using SectorPtr = std::unique_ptr<edigpu_sector, SectorDeleter>;
+
+// ---- what the files of the C-ABI layer share (Source layout) ----
+// (these were file-local while the layer was one file: they stay out of the library's dynamic symbols)
+#pragma GCC visibility push(hidden)
+// edigpu_setup.hip: the device images of a handle
+int finish_handle(edigpu_sector* s);
+void free_ell(DevEll& e);
+void free_csr(DevCsr& d);
+void free_ib(IbDev* p);
+int setup_normal(edigpu_sector* s, int64_t dim_up, int64_t dim_dw, int64_t dw_first, int64_t dw_count, const double* hd,
+                 const HostCsr& up, const HostCsr& dw, const int64_t* nd_rowptr, const int32_t* nd_col, const double* nd_val,
+                 HostNormal* built = nullptr);
+int setup_flat(edigpu_sector* s, int64_t nrow_local, int64_t ncol_global, int64_t row_first, const int64_t* rowptr,
+               const int32_t* col, const double* val, int cplx);
+int setup_orbs(edigpu_sector* s, const HostOrbs& ho, const double* hd);
+int build_flat_on_device(edigpu_sector* s, const HostDirect& hd);
+// edigpu_apply.hip: the product of any handle on stream st (phase: kernels.hpp, launch_normal)
+int ensure_workspace(edigpu_sector* s);
+int apply_any(edigpu_sector* s, const double* v_local, const double* v_full, double* hv, int phase, hipStream_t st);
+int single_shard(const edigpu_sector* s, const char* who);
+// edigpu_lanczos.hip: the recurrence on the handle's workspace
+int lanczos_step(edigpu_sector* s, int iter, int nlanc, hipStream_t st);
+int lanczos_prepare(edigpu_sector* s, int nlanc, double threshold, hipStream_t st);
+int lanczos_seed(edigpu_sector* s, const double* src, uint64_t seed, hipStream_t st);
+int lanczos_run(edigpu_sector* s, int from, int to, int nlanc, hipStream_t st);
+int lanczos_fetch(edigpu_sector* s, const double* v, double* dst, hipStream_t st);
+#pragma GCC visibility pop
+// edigpu_apply.hip: one electronic block of a superc / nonsu2 phonon handle, phase 1 (own rows) / 2 (gathered block)
+int apply_flat_block(edigpu_sector* s, const double* v_local, const double* v_full, double* hv, int phase, hipStream_t st);
+// edigpu_lanczos.hip: a flat or on-the-fly sector held whole on this GPU, without phonons, whose product has the fused
+// Lanczos epilogue (the sectors whose single-seed step is rotate -> product with partials -> finalize)
+bool flat_lanczos_fusable(const edigpu_sector* s);
+// edigpu_trl.hip: the thick-restart Lanczos driver, shared by edigpu_lanczos_eigh_multi and its sharded twin
+struct TrlOps {
+  std::function<int(const double* in, double* out, hipStream_t st)> apply;  // out = H in on this rank's elements
+  std::function<int(double* dev, size_t n, hipStream_t st)> allreduce;     // sum over the ranks, in place; empty: one rank
+};
+int trl_solve(int device, hipStream_t st, int cplx, int64_t n, int64_t len, int64_t nglobal, const TrlOps& ops, int neigen, int ncv,
+              double tol, int maxrestart, const double* v0, uint64_t seed_offset, double* evals, double* evecs,
+              int* nconv_out, int* nmatvec_out);
+// edigpu_ops.hip: apply_Cops on a window of destination units: v_dst_rows = sum_s coef_s O_s v_src for the
+// destination's down rows (normal mode) / rows (superc, nonsu2) [first, first + count); v_src_full holds the WHOLE source
+// vector in the reference's layout; coef2 = (re, im) per operator (normal mode: real).  Returns after the stream finished.
+int apply_cops_rows(edigpu_sector* src, edigpu_sector* dst, const double* v_src_full, double* v_dst_rows, int64_t first,
+                    int64_t count, int nops, const double* coef2, const int32_t* create, const int32_t* iorb,
+                    const int32_t* ispin, hipStream_t st, const char* who);
+
+}  // namespace edigpu

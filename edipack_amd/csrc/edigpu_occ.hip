@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "host_occ.hpp"
 #include "kernels.hpp"
 
@@ -12,26 +13,25 @@ namespace edigpu {
 void free_occ(edigpu_sector* s) {
   if (!s || !s->occ) return;
   OccDev* o = s->occ;
-  for (void* q : {(void*)o->pu, (void*)o->pd, (void*)o->order, (void*)o->partial, (void*)o->sums})
-    if (q) (void)hipFree(q);
+  dev_free_all(o->pu, o->pd, o->order, o->partial, o->sums);
   delete o;
   s->occ = nullptr;
 }
 
 static bool occ_served(const edigpu_sector* s) {
-  return s && s->built_by_library && s->kind != 3 && s->nloc == s->dim;
+  return s && s->built_by_library && s->kind != kOrbs && s->is_whole();
 }
 
 int64_t occ_table_bytes(const edigpu_sector* s) {
   if (!occ_served(s)) return 0;
   const int64_t workspace = (int64_t)(4096 + 1) * kOccSums * 8;  // one vector's partial sums on a 256-CU device
-  if (s->kind == 1 || s->kind == 2) return 2 * (s->nph > 0 ? s->dim_el : s->dim) + workspace;
-  const edigpu_sector* base = s->kind == 4 ? s->sub_s : s;
+  if (s->is_flat_family()) return 2 * (s->has_phonons() ? s->dim_el : s->dim) + workspace;
+  const edigpu_sector* base = s->kind == kCmplxNormal ? s->sub_s : s;
   return 2 * s->dim_up + ((base && base->d_impd) ? 0 : s->dim_dw) + 4 * s->dim_dw * (s->nph + 1) + workspace;
 }
 
 int occ_refuse(const edigpu_sector* s, const std::string& who) {
-  if (s->kind == 3) {
+  if (s->kind == kOrbs) {
     set_error(who + ": ed_total_ud=F sectors are not supported");
     return 1;
   }
@@ -40,19 +40,10 @@ int occ_refuse(const edigpu_sector* s, const std::string& who) {
               "edigpu_direct_build[_jz]); a hand-over handle has no sector map");
     return 1;
   }
-  if (s->nloc != s->dim) {
+  if (!s->is_whole()) {
     set_error(who + ": the handle must hold the whole sector (shards are not supported)");
     return 1;
   }
-  return 0;
-}
-
-template <class T>
-static int occ_upload(T** d, const std::vector<T>& h) {
-  *d = nullptr;
-  if (h.empty()) return 0;
-  EDIGPU_HIP(hipMalloc((void**)d, h.size() * sizeof(T)));
-  EDIGPU_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -74,9 +65,9 @@ static int occ_build(edigpu_sector* s, const std::string& who) {
     free_occ(s);
     return 1;
   };
-  if (s->kind == 1 || s->kind == 2) {
+  if (s->is_flat_family()) {
     o->flat = 1;
-    o->dim_up = s->nph > 0 ? s->dim_el : s->dim;
+    o->dim_up = s->has_phonons() ? s->dim_el : s->dim;
     o->dim_dw = 1;
     std::vector<int32_t> map((size_t)o->dim_up);
     int64_t n = o->dim_up;
@@ -89,7 +80,7 @@ static int occ_build(edigpu_sector* s, const std::string& who) {
     if (n != o->dim_up) return fail("the sector map does not have the handle's dimension");
     std::vector<uint16_t> pu(map.size());
     occ_patterns_state(map.data(), n, m.norb, model_ns(m), pu.data());
-    if (occ_upload(&o->pu, pu)) return fail(edigpu_last_error());
+    if (dev_upload(&o->pu, pu)) return fail(edigpu_last_error());
     return 0;
   }
   o->dim_up = s->dim_up;
@@ -108,9 +99,9 @@ static int occ_build(edigpu_sector* s, const std::string& who) {
   std::vector<int32_t> order;
   occ_sort_rows(pd.data(), s->dim_dw, o->nblk, order, o->run);
   // the factored sectors already keep the down patterns on the device (edigpu_sector::d_impd)
-  const edigpu_sector* base = s->kind == 4 ? s->sub_s : s;
+  const edigpu_sector* base = s->kind == kCmplxNormal ? s->sub_s : s;
   const bool have_pd = base && base->factored && base->d_impd;
-  if (occ_upload(&o->pu, pu) || occ_upload(&o->order, order) || (!have_pd && occ_upload(&o->pd, pd)))
+  if (dev_upload(&o->pu, pu) || dev_upload(&o->order, order) || (!have_pd && dev_upload(&o->pd, pd)))
     return fail(edigpu_last_error());
   return 0;
 }
@@ -125,7 +116,7 @@ static OccTables occ_args(const edigpu_sector* s) {
   t.dim_up = o->dim_up;
   t.dim_dw = o->dim_dw;
   t.pu = o->pu;
-  t.pd = o->pd ? o->pd : (s->kind == 4 ? s->sub_s->d_impd : s->d_impd);
+  t.pd = o->pd ? o->pd : (s->kind == kCmplxNormal ? s->sub_s->d_impd : s->d_impd);
   t.order = o->order;
   return t;
 }
@@ -136,20 +127,7 @@ static int occ_moments_enqueue(edigpu_sector* s, const double* v_dev, int nvec) 
   const OccTables t = occ_args(s);
   const int nwaves = occ_moment_waves(t, o->ncu);
   const int64_t need_partial = (int64_t)nvec * nwaves * kOccSums, need_sums = (int64_t)nvec * kOccSums;
-  if (o->partial_cap < need_partial) {
-    if (o->partial) (void)hipFree(o->partial);
-    o->partial = nullptr;
-    o->partial_cap = 0;
-    EDIGPU_HIP(hipMalloc((void**)&o->partial, (size_t)need_partial * sizeof(double)));
-    o->partial_cap = need_partial;
-  }
-  if (o->sums_cap < need_sums) {
-    if (o->sums) (void)hipFree(o->sums);
-    o->sums = nullptr;
-    o->sums_cap = 0;
-    EDIGPU_HIP(hipMalloc((void**)&o->sums, (size_t)need_sums * sizeof(double)));
-    o->sums_cap = need_sums;
-  }
+  if (dev_grow(&o->partial, &o->partial_cap, need_partial) || dev_grow(&o->sums, &o->sums_cap, need_sums)) return 1;
   OccSlots sl;
   sl.nslots = occ_sum_slots(o->norb, sl.need_up, sl.need_dw);
   OccRuns rn;

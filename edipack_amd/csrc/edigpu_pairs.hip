@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "host_pairs.hpp"
 #include "kernels.hpp"
 
@@ -21,23 +22,23 @@ std::vector<PairsTerm> pairs_terms(int nterms, const double* coef, const int32_t
 // one refusal per kind of handle the products do not serve
 int pairs_refuse(const edigpu_sector* s, const std::string& who, const char* which) {
   const std::string w = who + ": the " + which + " handle ";
-  if (s->kind == 4 || (s->kind == 0 && s->is_complex)) {
+  if (s->kind == kCmplxNormal || (s->kind == kNormal && s->is_complex)) {
     set_error(w + "is a complex normal-mode sector (edigpu_normal_build_z): only real vectors are supported");
     return 1;
   }
-  if (s->kind == 1 || s->kind == 2) {
+  if (s->is_flat_family()) {
     set_error(w + "is a superc / nonsu2 sector: only ed_mode=normal sectors are supported");
     return 1;
   }
-  if (s->kind == 3) {
+  if (s->kind == kOrbs) {
     set_error(w + "is an ed_total_ud=F sector: ed_total_ud=F sectors are not supported");
     return 1;
   }
-  if (s->kind != 0 || !s->built_by_library) {
+  if (s->kind != kNormal || !s->built_by_library) {
     set_error(w + "must be built from a model (edigpu_normal_build); a hand-over handle has no sector labels");
     return 1;
   }
-  if (s->nloc != s->dim) {
+  if (!s->is_whole()) {
     set_error(w + "must hold the whole sector (shards are not supported)");
     return 1;
   }
@@ -89,9 +90,7 @@ int pairs_prepare(const edigpu_sector* src, const edigpu_sector* dst, const doub
 // device copy of the tables of one call: one allocation, up tables first
 struct PairsDevTables {
   uint32_t* d = nullptr;
-  ~PairsDevTables() {
-    if (d) (void)hipFree(d);
-  }
+  ~PairsDevTables() { dev_free(d); }
 };
 
 int pairs_upload(const PairsTables& tab, int nblk, PairsDevTables& dev, PairsArgs& a, hipStream_t st) {

@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "host_occ.hpp"
 #include "host_ph.hpp"
 #include "kernels.hpp"
@@ -23,25 +24,14 @@ struct PhDev {
 void free_ph(edigpu_sector* s) {
   if (!s || !s->ph) return;
   PhDev* p = s->ph;
-  for (void* q : {(void*)p->sq, (void*)p->rorder, (void*)p->corder, (void*)p->ubeg, (void*)p->units, (void*)p->partial,
-                  (void*)p->sums})
-    if (q) (void)hipFree(q);
+  dev_free_all(p->sq, p->rorder, p->corder, p->ubeg, p->units, p->partial, p->sums);
   delete p;
   s->ph = nullptr;
 }
 
-template <class T>
-static int ph_upload(T** d, const std::vector<T>& h) {
-  *d = nullptr;
-  if (h.empty()) return 0;
-  EDIGPU_HIP(hipMalloc((void**)d, h.size() * sizeof(T)));
-  EDIGPU_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
-
 static int ph_refuse(const edigpu_sector* s, const std::string& who) {
   if (occ_refuse(s, who)) return 1;
-  if (s->nph <= 0) {
+  if (!s->has_phonons()) {
     set_error(who + ": the handle has no phonons (nph = 0)");
     return 1;
   }
@@ -71,7 +61,7 @@ static int ph_build(edigpu_sector* s, const std::string& who, bool plan) {
     if (p->dim_el <= 0 || p->dim_el * p->dimph != s->dim) return fail("the handle's phonon blocks do not add up to its dimension");
     std::vector<double> sq((size_t)p->dimph + 1);
     ph_sqrt_table(p->dimph, sq.data());
-    if (ph_upload(&p->sq, sq)) return fail(edigpu_last_error());
+    if (dev_upload(&p->sq, sq)) return fail(edigpu_last_error());
   }
   PhDev* p = s->ph;
   if (!plan || p->planned) return 0;
@@ -80,7 +70,7 @@ static int ph_build(edigpu_sector* s, const std::string& who, bool plan) {
   // about eight units per compute unit on large sectors, and units long enough to pay for the reduction at their end
   const int64_t target = std::max<int64_t>(2048, p->dim_el / (std::max(ncu, 1) * 8));
   PhPlan pl;
-  if (s->kind == 1 || s->kind == 2) {
+  if (s->is_flat_family()) {
     std::vector<int32_t> map((size_t)p->dim_el);
     int64_t n = p->dim_el;
     if (s->jz ? edigpu_sector_map_jz(&m, s->sec_a, s->sec_b, map.data(), &n) : edigpu_sector_map(&m, s->sec_a, 0, 0, map.data(), &n))
@@ -103,8 +93,8 @@ static int ph_build(edigpu_sector* s, const std::string& who, bool plan) {
   p->dim_cols = pl.dim_cols;
   p->nunits = (int)pl.units.size();
   const size_t nslot = (size_t)ph_slots(p->dimph) * (p->cplx ? 2 : 1);
-  if (ph_upload(&p->rorder, pl.rorder) || ph_upload(&p->corder, pl.corder) || ph_upload(&p->ubeg, pl.ubeg) ||
-      ph_upload(&p->units, pl.units))
+  if (dev_upload(&p->rorder, pl.rorder) || dev_upload(&p->corder, pl.corder) || dev_upload(&p->ubeg, pl.ubeg) ||
+      dev_upload(&p->units, pl.units))
     return fail(edigpu_last_error());
   if (hipMalloc((void**)&p->partial, std::max<size_t>(1, (size_t)p->nunits) * nslot * sizeof(double)) != hipSuccess ||
       hipMalloc((void**)&p->sums, (size_t)p->ncls * nslot * sizeof(double)) != hipSuccess)

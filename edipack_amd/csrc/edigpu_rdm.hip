@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "host_rdm.hpp"
 #include "kernels.hpp"
 
@@ -27,14 +28,13 @@ struct RdmDev {
 void free_rdm(edigpu_sector* s) {
   if (!s || !s->rdm) return;
   RdmDev* r = s->rdm;
-  for (void* q : {(void*)r->rows, (void*)r->rel, (void*)r->ent, (void*)r->work, (void*)r->partial, (void*)r->out})
-    if (q) (void)hipFree(q);
+  dev_free_all(r->rows, r->rel, r->ent, r->work, r->partial, r->out);
   delete r;
   s->rdm = nullptr;
 }
 
 static bool rdm_served(const edigpu_sector* s) {
-  return s && s->built_by_library && (s->kind == 0 || s->kind == 4) && s->nloc == s->dim;
+  return s && s->built_by_library && (s->is_normal_family()) && s->is_whole();
 }
 
 int64_t rdm_table_bytes(const edigpu_sector* s) {
@@ -49,18 +49,9 @@ int64_t rdm_table_bytes(const edigpu_sector* s) {
   return tables + (nel / 8 + 2 * l.ntri) * cw * 8;
 }
 
-template <class T>
-static int rdm_upload(T** d, const std::vector<T>& h) {
-  *d = nullptr;
-  if (h.empty()) return 0;
-  EDIGPU_HIP(hipMalloc((void**)d, h.size() * sizeof(T)));
-  EDIGPU_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
-
 static int rdm_refuse(const edigpu_sector* s, const std::string& who) {
   if (occ_refuse(s, who)) return 1;
-  if (s->kind != 0 && s->kind != 4) {
+  if (!s->is_normal_family()) {
     set_error(who + ": only ed_mode=normal sectors are supported");
     return 1;
   }
@@ -108,7 +99,7 @@ static int rdm_build(edigpu_sector* s, const std::string& who) {
   r->args.dim_up = s->dim_up;
   r->args.dim_dw = s->dim_dw;
   if (rdm_lds_bytes(r->args) > (size_t)(160 << 10)) return fail("the work list does not fit the LDS");
-  if (rdm_upload(&r->rows, p.rows) || rdm_upload(&r->rel, p.rel) || rdm_upload(&r->ent, p.ent) || rdm_upload(&r->work, p.work))
+  if (dev_upload(&r->rows, p.rows) || dev_upload(&r->rel, p.rel) || dev_upload(&r->ent, p.ent) || dev_upload(&r->work, p.work))
     return fail(edigpu_last_error());
   r->args.rows = r->rows;
   r->args.rel = r->rel;
@@ -125,16 +116,7 @@ static int rdm_enqueue(edigpu_sector* s, const double* v_dev, int nvec) {
   RdmDev* r = s->rdm;
   const int cw = r->args.cw;
   const int64_t pstride = std::max<int64_t>(r->partial_entries, 1) * cw, ostride = r->layout.ntri * cw;
-  auto grow = [](double** d, int64_t* cap, int64_t need) {
-    if (*cap >= need) return 0;
-    if (*d) (void)hipFree(*d);
-    *d = nullptr;
-    *cap = 0;
-    EDIGPU_HIP(hipMalloc((void**)d, (size_t)need * sizeof(double)));
-    *cap = need;
-    return 0;
-  };
-  if (grow(&r->partial, &r->partial_cap, pstride * nvec) || grow(&r->out, &r->out_cap, ostride * nvec)) return 1;
+  if (dev_grow(&r->partial, &r->partial_cap, pstride * nvec) || dev_grow(&r->out, &r->out_cap, ostride * nvec)) return 1;
   const int64_t vstride = s->dim_up * s->dim_dw * (s->nph + 1) * cw;
   return launch_imp_rdm(r->args, r->nwork, r->groups.data(), (int)r->groups.size(), v_dev, vstride, nvec, r->partial, pstride,
                         r->out, ostride, s->stream);

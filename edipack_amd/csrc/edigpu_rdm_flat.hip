@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "host_rdm_flat.hpp"
 #include "kernels.hpp"
 
@@ -29,29 +30,18 @@ struct RdmFlatDev {
 void free_rdm_flat(edigpu_sector* s) {
   if (!s || !s->rdm_flat) return;
   RdmFlatDev* r = s->rdm_flat;
-  for (void* q : {(void*)r->rowstart, (void*)r->bdw, (void*)r->rel, (void*)r->ent, (void*)r->panels, (void*)r->work,
-                  (void*)r->partial, (void*)r->out})
-    if (q) (void)hipFree(q);
+  dev_free_all(r->rowstart, r->bdw, r->rel, r->ent, r->panels, r->work, r->partial, r->out);
   delete r;
   s->rdm_flat = nullptr;
 }
 
-template <class T>
-static int rdm_flat_upload(T** d, const std::vector<T>& h) {
-  *d = nullptr;
-  if (h.empty()) return 0;
-  EDIGPU_HIP(hipMalloc((void**)d, h.size() * sizeof(T)));
-  EDIGPU_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
-
 static int rdm_flat_refuse(const edigpu_sector* s, const std::string& who) {
   if (occ_refuse(s, who)) return 1;
-  if (s->kind == 0 || s->kind == 4) {
+  if (s->is_normal_family()) {
     set_error(who + ": normal-mode sectors are not served here, use edigpu_imp_rdm");
     return 1;
   }
-  if (s->kind != 1 && s->kind != 2) {
+  if (!s->is_flat_family()) {
     set_error(who + ": only superc and nonsu2 sectors are supported");
     return 1;
   }
@@ -79,7 +69,7 @@ static int rdm_flat_build(edigpu_sector* s, const std::string& who) {
   };
   int ncu = 0;
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || ncu < 1) ncu = 256;
-  const int64_t dim_el = s->nph > 0 ? s->dim_el : s->dim;
+  const int64_t dim_el = s->has_phonons() ? s->dim_el : s->dim;
   std::vector<int32_t> map((size_t)dim_el);
   int64_t n = dim_el;
   if (edigpu_sector_map(&m, s->sec_a, 0, 0, map.data(), &n)) {
@@ -99,8 +89,8 @@ static int rdm_flat_build(edigpu_sector* s, const std::string& who) {
   r->args.rel_max = p.rel_max;
   r->args.dim_el = dim_el;
   if (p.stage_max > kRdmFlatStageElems || rdm_flat_lds_bytes(r->args) > (size_t)(160 << 10)) return fail("the work list does not fit the LDS");
-  if (rdm_flat_upload(&r->rowstart, p.rowstart) || rdm_flat_upload(&r->bdw, p.bdw) || rdm_flat_upload(&r->rel, p.rel) ||
-      rdm_flat_upload(&r->ent, p.ent) || rdm_flat_upload(&r->panels, p.panels) || rdm_flat_upload(&r->work, p.work))
+  if (dev_upload(&r->rowstart, p.rowstart) || dev_upload(&r->bdw, p.bdw) || dev_upload(&r->rel, p.rel) ||
+      dev_upload(&r->ent, p.ent) || dev_upload(&r->panels, p.panels) || dev_upload(&r->work, p.work))
     return fail(edigpu_last_error());
   r->args.rowstart = r->rowstart;
   r->args.bdw = r->bdw;
@@ -119,16 +109,7 @@ static int rdm_flat_enqueue(edigpu_sector* s, const double* v_dev, int nvec) {
   RdmFlatDev* r = s->rdm_flat;
   const int cw = r->args.cw;
   const int64_t pstride = std::max<int64_t>(r->partial_entries, 1) * cw, ostride = r->tables.ntri * cw;
-  auto grow = [](double** d, int64_t* cap, int64_t need) {
-    if (*cap >= need) return 0;
-    if (*d) (void)hipFree(*d);
-    *d = nullptr;
-    *cap = 0;
-    EDIGPU_HIP(hipMalloc((void**)d, (size_t)need * sizeof(double)));
-    *cap = need;
-    return 0;
-  };
-  if (grow(&r->partial, &r->partial_cap, pstride * nvec) || grow(&r->out, &r->out_cap, ostride * nvec)) return 1;
+  if (dev_grow(&r->partial, &r->partial_cap, pstride * nvec) || dev_grow(&r->out, &r->out_cap, ostride * nvec)) return 1;
   const int64_t vstride = r->args.dim_el * (s->nph + 1) * cw;
   return launch_imp_rdm_flat(r->args, r->nwork, r->groups.data(), (int)r->groups.size(), v_dev, vstride, nvec, r->partial,
                              pstride, r->out, ostride, s->stream);

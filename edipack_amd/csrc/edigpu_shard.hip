@@ -33,6 +33,7 @@
 
 #include <rccl/rccl.h>
 
+#include "dev_mem.hpp"
 #include "exchange_index.hpp"
 #include "kernels.hpp"
 #include "sb_core.hpp"
@@ -123,7 +124,8 @@ struct ShmHeader {
 struct edigpu_comm_s {
   const edigpu::CommSwitches sw = edigpu::CommSwitches::sample();  // the environment edigpu_comm_create* saw (switches.hpp)
   int rank = 0, world = 1;
-  int kind = 0;  // 0 RCCL, 1 host-staged through shared memory
+  enum Transport : int { kRccl = 0, kHostStaged = 1 };  // (the values: edigpu_comm_info)
+  Transport kind = kRccl;
   int device = 0;
   ncclComm_t nccl = nullptr;
   hipStream_t side = nullptr;  // exchange stream: the all-to-all / all-gather of a product runs beside its local part
@@ -151,7 +153,7 @@ struct edigpu_comm_s {
 namespace edigpu {
 
 // a world of one still issues its collectives through RCCL (one-GPU rehearsal of the calls)
-static bool force_collectives(const edigpu_comm_s* c) { return c->sw.force_collectives && c->kind == 0 && c->nccl != nullptr; }
+static bool force_collectives(const edigpu_comm_s* c) { return c->sw.force_collectives && c->kind == edigpu_comm_s::kRccl && c->nccl != nullptr; }
 
 static int shm_barrier(edigpu_comm_s* c) {
   ShmHeader* h = c->hdr;
@@ -215,7 +217,7 @@ static int comm_all_to_all(edigpu_comm_s* c, const double* send, double* recv, s
     hipStream_t s;
     ~End() { (void)side_end(c, s); }
   } end_{c, st == c->side ? caller : st};
-  if (c->kind == 0) {
+  if (c->kind == edigpu_comm_s::kRccl) {
     RcclApi* r = rccl();
     EDIGPU_RCCL(r->GroupStart());
     for (int p = 0; p < c->world; p++) {
@@ -251,7 +253,7 @@ static int comm_all_gather(edigpu_comm_s* c, const double* send, double* recv, s
     hipStream_t s;
     ~End() { (void)side_end(c, s); }
   } end_{c, st == c->side ? caller : st};
-  if (c->kind == 0) {
+  if (c->kind == edigpu_comm_s::kRccl) {
     EDIGPU_RCCL(rccl()->AllGather(send, recv, n, RCCL_FLOAT64, c->nccl, st));
     return 0;
   }
@@ -277,7 +279,7 @@ static int comm_all_reduce(edigpu_comm_s* c, double* buf, size_t n, hipStream_t 
     hipStream_t s;
     ~End() { (void)side_end(c, s); }
   } end_{c, st == c->side ? caller : st};
-  if (c->kind == 0) {
+  if (c->kind == edigpu_comm_s::kRccl) {
     EDIGPU_RCCL(rccl()->AllReduce(buf, buf, n, RCCL_FLOAT64, RCCL_SUM, c->nccl, st));
     return 0;
   }
@@ -481,9 +483,9 @@ struct ShardGeom {
 static int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g) {
   g.loop = LoopSwitches::sample();
   g.w = s->is_complex ? 2 : 1;
-  g.transposed = s->kind == 0 && s->nloc == s->dim && normal_transposable_el(s);
-  g.nblk = s->nph > 0 ? s->nph + 1 : 1;
-  if (s->kind == 0) {
+  g.transposed = s->kind == kNormal && s->is_whole() && normal_transposable_el(s);
+  g.nblk = s->has_phonons() ? s->nph + 1 : 1;
+  if (s->kind == kNormal) {
     g.units = s->dim_dw;
     g.unit_len = s->dim_up;
   } else {
@@ -511,7 +513,7 @@ static int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardG
     g.npmax = sb_shard_panels(s, c->world);
     g.bplen = sb::shard_slot(c->world, g.npmax, g.q);
   }
-  if (g.nblk > 1 && (s->sub_a || (s->kind == 0 && !g.transposed))) {
+  if (g.nblk > 1 && (s->sub_a || (s->kind == kNormal && !g.transposed))) {
     // like spMatVec_mpi_normal_main (ED_HAMILTONIAN_NORMAL_STORED_HxV.f90:841-904) and spMatVec_mpi_superc_main /
     // _nonsu2_main: every phonon block is exchanged on its own and the phonon / electron-phonon pass is local, which
     // holds for density couplings only
@@ -527,7 +529,7 @@ static int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardG
                 "edigpu_shard_plan, or -- normal mode -- build the whole sector for the transposed exchange)");
       return 1;
     }
-    if (s->kind == 4) {
+    if (s->kind == kCmplxNormal) {
       set_error("sharded call: four-product complex sectors are single-shard");
       return 1;
     }
@@ -537,8 +539,7 @@ static int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardG
 
 template <class T>
 static int regrow(T*& p, size_t n) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
+  dev_free(p);
   EDIGPU_HIP(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)));
   EDIGPU_HIP(hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)));
   // the memset runs on the null stream, which the handles' non-blocking streams do not wait for
@@ -911,7 +912,7 @@ int edigpu_comm_create(edigpu_comm* out, int32_t rank, int32_t world, const void
   auto* c = new edigpu_comm_s();
   c->rank = rank;
   c->world = world;
-  c->kind = 0;
+  c->kind = edigpu_comm_s::kRccl;
   if (comm_common(c)) {
     delete c;
     return 1;
@@ -950,7 +951,7 @@ int edigpu_comm_create_shm(edigpu_comm* out, int32_t rank, int32_t world, const 
   auto* c = new edigpu_comm_s();
   c->rank = rank;
   c->world = world;
-  c->kind = 1;
+  c->kind = edigpu_comm_s::kHostStaged;
   c->shm_name = name[0] == '/' ? name : std::string("/") + name;
   slot_bytes = (slot_bytes + 63) / 64 * 64;
   c->shm_bytes = 4096 + (size_t)world * (size_t)slot_bytes;
@@ -1053,9 +1054,8 @@ int edigpu_comm_info(edigpu_comm c, int32_t* rank, int32_t* world, int32_t* kind
 int edigpu_comm_destroy(edigpu_comm c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
-  for (double** p : {&c->vin, &c->vout, &c->tmp, &c->vfull, &c->send, &c->recv, &c->hvc, &c->back, &c->hist, &c->work, &c->scr,
-                     &c->bp[0], &c->bp[1], &c->bp[2], &c->bp[3], &c->bp[4]})
-    if (*p) (void)hipFree(*p);
+  dev_free_all(c->vin, c->vout, c->tmp, c->vfull, c->send, c->recv, c->hvc, c->back, c->hist, c->work, c->scr, c->bp[0], c->bp[1],
+               c->bp[2], c->bp[3], c->bp[4]);
   if (c->nccl && rccl()) (void)rccl()->CommDestroy(c->nccl);
   if (c->side) (void)hipStreamDestroy(c->side);
   if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
@@ -1082,7 +1082,7 @@ static int apply_sharded(edigpu_handle s, edigpu_comm c, int64_t nloc, const dou
   }
   // _CMPLX_NORMAL held as one real sector on the doubled up index: its down rows shard like any real sector's (each row
   // 2 DimUp doubles = DimUp complex elements), so the transposed exchange serves complex sectors as well
-  if (s->kind == 4 && s->sub_d) return apply_sharded(s->sub_d, c, 2 * nloc, v, hv, 0);
+  if (s->kind == kCmplxNormal && s->sub_d) return apply_sharded(s->sub_d, c, 2 * nloc, v, hv, 0);
   ShardGeom g;
   if (shard_geometry(s, c, g)) return 1;
   if (nloc != g.nloc) {
@@ -1121,15 +1121,15 @@ int edigpu_lanczos_tridiag_sharded(edigpu_handle h, edigpu_comm c, const double*
   }
   // a world of one rank holding the whole sector: the fused single-GPU recurrence (half the vector traffic of the
   // exchange form: no send / receive buffers); CommSwitches::force_collectives keeps the N > 1 code path (tests)
-  if (h->kind == 4 && h->sub_d) h = h->sub_d;  // complex normal sector = its doubled real sector (see apply_sharded)
-  if (c->world == 1 && h->nloc == h->dim && !c->sw.force_collectives && vin_shard)
+  if (h->kind == kCmplxNormal && h->sub_d) h = h->sub_d;  // complex normal sector = its doubled real sector (see apply_sharded)
+  if (c->world == 1 && h->is_whole() && !c->sw.force_collectives && vin_shard)
     return edigpu_lanczos_tridiag_dev(h, vin_shard, nlanc, alanc, blanc, threshold, niter_done, norm2);
   return sharded_tridiag(h, c, vin_shard, nlanc, alanc, blanc, threshold, niter_done, norm2);
 }
 
 // sp_eigh(MpiComm, spHtimesV_p, eval, evec, ...) / sp_lanc_eigh(MpiComm, ...) with every vector a device-resident shard
 // (ED_NORMAL/ED_DIAG_NORMAL.f90:179-214 and the superc / nonsu2 twins): the thick-restart driver of the single-GPU
-// solver (trl_solve, edigpu_capi.hip) on this rank's elements, the product through the sharded exchange, the Gram-
+// solver (trl_solve, edigpu_trl.hip) on this rank's elements, the product through the sharded exchange, the Gram-
 // Schmidt coefficients and norms through small all-reduces.  Nothing of vector length crosses PCIe.
 int edigpu_lanczos_eigh_multi_sharded(edigpu_handle h, edigpu_comm c, int neigen, int ncv, double tol, int maxrestart,
                                       const double* v0_shard, double* evals, double* evecs_shard, int* nconv, int* nmatvec) {
@@ -1138,12 +1138,12 @@ int edigpu_lanczos_eigh_multi_sharded(edigpu_handle h, edigpu_comm c, int neigen
     return 1;
   }
   bool realified = false;
-  if (h->kind == 4 && h->sub_d) {  // complex normal sector: the products run on its doubled real sector, whose real
+  if (h->kind == kCmplxNormal && h->sub_d) {  // complex normal sector: the products run on its doubled real sector, whose real
     h = h->sub_d;                  // vectors ARE the interleaved complex ones -- the solver keeps the complex algebra
     realified = true;
   }
   // a world of one rank holding the whole sector: the single-GPU solver (no exchange buffers)
-  if (c->world == 1 && h->nloc == h->dim && !c->sw.force_collectives && !realified)
+  if (c->world == 1 && h->is_whole() && !c->sw.force_collectives && !realified)
     return edigpu_lanczos_eigh_multi(h, neigen, ncv, tol, maxrestart, v0_shard, evals, evecs_shard, nconv, nmatvec);
   ShardGeom g;
   if (shard_geometry(h, c, g)) return 1;
@@ -1200,7 +1200,7 @@ int edigpu_apply_cops_sharded(edigpu_handle src, edigpu_handle dst, edigpu_comm 
     set_error("edigpu_apply_cops_sharded: bad argument");
     return 1;
   }
-  if (src->kind == 4 || dst->kind == 4 || src->nph > 0 || dst->nph > 0) {
+  if (src->kind == kCmplxNormal || dst->kind == kCmplxNormal || src->has_phonons() || dst->has_phonons()) {
     set_error("edigpu_apply_cops_sharded: complex normal-mode and phonon sectors are not supported");
     return 1;
   }
@@ -1242,10 +1242,10 @@ int edigpu_exchange_bench(edigpu_handle s, edigpu_comm c, int steps, int32_t* rc
     set_error("edigpu_exchange_bench: bad argument");
     return 1;
   }
-  if (s->kind == 4 && s->sub_d) s = s->sub_d;
+  if (s->kind == kCmplxNormal && s->sub_d) s = s->sub_d;
   if (rccl_ranks) {
     *rccl_ranks = 0;
-    if (c->kind == 0) {
+    if (c->kind == edigpu_comm_s::kRccl) {
       int n = -1;
       if (c->nccl && rccl() && rccl()->CommCount && rccl()->CommCount(c->nccl, &n) != ncclSuccess) n = -1;
       *rccl_ranks = c->nccl ? n : 1;  // (a world of one makes no RCCL communicator)
@@ -1295,7 +1295,7 @@ int edigpu_lanczos_bench_sharded(edigpu_handle s, edigpu_comm c, int warmup, int
     set_error("edigpu_lanczos_bench_sharded: bad argument");
     return 1;
   }
-  if (s->kind == 4 && s->sub_d) s = s->sub_d;
+  if (s->kind == kCmplxNormal && s->sub_d) s = s->sub_d;
   ShardGeom g;
   if (shard_geometry(s, c, g)) return 1;
   EDIGPU_HIP(hipSetDevice(s->device));
@@ -1335,7 +1335,7 @@ int edigpu_shard_info(edigpu_handle s, edigpu_comm c, int32_t info[4]) {
     set_error("edigpu_shard_info: bad argument");
     return 1;
   }
-  if (s->kind == 4 && s->sub_d) s = s->sub_d;
+  if (s->kind == kCmplxNormal && s->sub_d) s = s->sub_d;
   ShardGeom g;
   if (shard_geometry(s, c, g)) return 1;
   info[0] = g.block ? 2 : g.transposed ? 1 : 0;

@@ -1,9 +1,10 @@
 // trl_hooks.hip -- test hooks of the thick-restart eigensolver's multi-vector kernels (kernels_trl.hip).
 //
 // Each hook takes host buffers given as pointer + length in doubles, uploads every buffer WHOLE, calls one launcher of
-// kernels.hpp as the solver does (trl_solve, edigpu_capi.hip) on the calling thread's current device, and downloads every
+// kernels.hpp as the solver does (trl_solve, edigpu_trl.hip) on the calling thread's current device, and downloads every
 // buffer the launcher may write, whole again: a test that surrounds its payload with sentinels sees every write.
 // No kernel lives here; the arguments are checked before the device is touched.
+#include "../dev_mem.hpp"
 #include "../kernels.hpp"
 
 namespace edigpu {
@@ -14,9 +15,7 @@ constexpr int kGroup = 16;  // kTrlNC (kernels_trl.hip): basis vectors per launc
 struct DevBuf {
   double* p = nullptr;
   size_t n = 0;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
+  ~DevBuf() { dev_free(p); }
   int up(const double* h, int64_t len) {
     n = (size_t)len;
     EDIGPU_HIP(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(double)));
@@ -35,9 +34,7 @@ struct DevBuf {
 
 struct DevInt {
   int* p = nullptr;
-  ~DevInt() {
-    if (p) (void)hipFree(p);
-  }
+  ~DevInt() { dev_free(p); }
   int up(int v) {
     EDIGPU_HIP(hipMalloc((void**)&p, sizeof(int)));
     EDIGPU_HIP(hipMemcpy(p, &v, sizeof(int), hipMemcpyHostToDevice));

@@ -1,7 +1,5 @@
 // kernels.hpp -- launch wrappers of the gfx950 kernels (definitions in kernels_*.hip).
 #pragma once
-#include <functional>
-
 #include "edigpu_internal.hpp"
 #include "host_rdm.hpp"
 #include "host_rdm_flat.hpp"
@@ -162,15 +160,6 @@ int vec_unpack_add_dot2(int64_t dim_up, int64_t nrows, int64_t q, int64_t pcol, 
                         double* vout, const double* tmp, const double* back, double* out2, double* work,
                         hipStream_t st);
 
-// ---- thick-restart Lanczos driver (edigpu_capi.hip), shared by edigpu_lanczos_eigh_multi and its sharded twin ----
-struct TrlOps {
-  std::function<int(const double* in, double* out, hipStream_t st)> apply;  // out = H in on this rank's elements
-  std::function<int(double* dev, size_t n, hipStream_t st)> allreduce;     // sum over the ranks, in place; empty: one rank
-};
-int trl_solve(int device, hipStream_t st, int cplx, int64_t n, int64_t len, int64_t nglobal, const TrlOps& ops, int neigen, int ncv,
-              double tol, int maxrestart, const double* v0, uint64_t seed_offset, double* evals, double* evecs,
-              int* nconv_out, int* nmatvec_out);
-
 // ---- thick-restart Lanczos multi-vector kernels (kernels_trl.hip) ----
 // h_dev (2 doubles per basis vector: re, im) = Q^H w, then w -= Q h; n counts complex or real elements
 int trl_orthogonalize(int cplx, int64_t n, int nvec, const double* Q, int64_t ldq, double* w, double* h_dev,
@@ -195,8 +184,6 @@ int launch_apply_op_normal(int64_t dst_dimup, int64_t dst_dimdw, int64_t src_dim
                            const uint32_t* part, const double* src, double* dst, hipStream_t st, double coef = 1.0,
                            int accumulate = 0);
 
-// one electronic block of a superc / nonsu2 phonon handle, phase 1 (own rows) / 2 (gathered block)  (edigpu_capi.hip)
-int apply_flat_block(edigpu_sector* s, const double* v_local, const double* v_full, double* hv, int phase, hipStream_t st);
 int launch_phonon(const edigpu_sector* s, const double* v, double* hv, hipStream_t st);
 // the same pass on a shard of down rows [dw_first, dw_first + dw_count) of a normal-mode sector: (Nph + 1) blocks of
 // dw_count * DimUp elements (the layout of spMatVec_mpi_normal_main); density couplings only
@@ -206,12 +193,6 @@ int launch_apply_op_flat(int64_t ndst, int ns, uint32_t bit, int create, const i
                          const int32_t* src_offdw, const int32_t* src_rkup, const double* src, double* dst,
                          hipStream_t st, double cre = 1.0, double cim = 0.0, int accumulate = 0, int nblk = 1,
                          int64_t nsrc = 0);  // nblk > 1: phonon blocks of ndst (destination) / nsrc (source) elements
-// apply_Cops on a window of destination units (edigpu_capi.hip): v_dst_rows = sum_s coef_s O_s v_src for the
-// destination's down rows (normal mode) / rows (superc, nonsu2) [first, first + count); v_src_full holds the WHOLE source
-// vector in the reference's layout; coef2 = (re, im) per operator (normal mode: real).  Returns after the stream finished.
-int apply_cops_rows(edigpu_sector* src, edigpu_sector* dst, const double* v_src_full, double* v_dst_rows, int64_t first,
-                    int64_t count, int nops, const double* coef2, const int32_t* create, const int32_t* iorb,
-                    const int32_t* ispin, hipStream_t st, const char* who);
 
 // ---- ed_total_ud = F sectors (kernels_orbs.hip) ----
 int launch_orbs(const edigpu_sector* s, const double* v, double* hv, hipStream_t st);

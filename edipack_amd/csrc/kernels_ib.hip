@@ -331,7 +331,7 @@ __global__ void __launch_bounds__(kColsNT, 4) ib_cols_kernel(IbArgs a, const dou
   // A panel's tasks are consecutive: the slots of an XCD sweep one or two panels at a time, whose V segments (1.6 MB per
   // panel at Ns = 16) the chunks gather their partners from.  With two panels in flight the L2 is over-subscribed
   // (measured: 4.4 GB fetched per product for 2.7 GB of V + result); nsub > 1 workgroups per chunk (each stages the
-  // chunk and takes a part of its blocks) keep a single panel in flight, and measured slower (edigpu_capi.hip).
+  // chunk and takes a part of its blocks) keep a single panel in flight, and measured slower (edigpu_setup.hip: setup_ib).
   for (int tt = slot; tt < panels_x * tpp; tt += nslots) {
     const int pi = tt / tpp, panel = pi * 8 + x;
     const int tc = tt - pi * tpp, sub = tc % nsub;

@@ -498,7 +498,7 @@ static int direct_multi_t(const edigpu_sector* s, const double* Xi, double* Yi, 
 // as launch_csr_multi, on a whole on-the-fly sector without phonons
 int launch_direct_multi(const edigpu_sector* s, int W, const double* Xi, double* Yi, bool lz, double* partial, int64_t cap,
                         int* np, const double* scal, int64_t sstride, hipStream_t st) {
-  if (!mu_width_ok(W) || s->kind != 2 || s->nph > 0 || s->nloc != s->dim || s->nloc <= 0) {
+  if (!mu_width_ok(W) || s->kind != kDirect || s->nph > 0 || s->nloc != s->dim || s->nloc <= 0) {
     set_error("launch_direct_multi: needs a whole on-the-fly sector without phonons and a width of 2, 4 or 8");
     return 1;
   }

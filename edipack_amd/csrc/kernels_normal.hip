@@ -758,7 +758,7 @@ int launch_normal_rows_pos(const edigpu_sector* s, const double* P, double* Q, d
 //         with halo columns on both sides (launch_dw_panel_cols)
 // the electronic part of the handle can run as a row half + a column half (phonon blocks: one exchange per block)
 bool normal_transposable_el(const edigpu_sector* s) {
-  if (s->kind != 0 || s->nloc != s->dim || s->dw_count == 0) return false;
+  if (s->kind != kNormal || s->nloc != s->dim || s->dw_count == 0) return false;
   if (!s->factored && s->has_nd) return false;  // explicit spH0nd couples arbitrary columns: all-gather form only
   if (s->factored && s->fac_nterms > 0 && s->d_mx_rowptr == nullptr) return false;
   return true;
@@ -789,7 +789,7 @@ int launch_normal_cols(const edigpu_sector* s, int64_t col_first, int64_t ncol, 
 //   panel sweep: Q += (Hdw + Hnd) v ; per-workgroup partials of alpha = <v|Q>
 // Returns the number of partials written.  The caller finalises alpha and runs the beta kernel.
 bool normal_lanczos_fusable(const edigpu_sector* s) {
-  if (s->kind != 0 || s->nloc != s->dim || s->dw_count == 0 || s->nph > 0) return false;
+  if (s->kind != kNormal || s->nloc != s->dim || s->dw_count == 0 || s->nph > 0) return false;
   if (s->rows_per_block == 0) return false;               // needs the LDS row kernel
   if (!s->factored && s->has_nd && !s->nd.sell) return false;  // CSR Hnd inside the row kernel needs the complete new vector
   if (s->sw.lanczos_unfused) return false;

@@ -221,7 +221,7 @@ __global__ void __launch_bounds__(256) k_shard_from_panels_add(const double* __r
   }
 }
 
-bool sb_shardable(const edigpu_sector* s) { return s->kind == 0 && s->ib && s->ib->sb && s->ib->nhalf == 1; }
+bool sb_shardable(const edigpu_sector* s) { return s->kind == kNormal && s->ib && s->ib->sb && s->ib->nhalf == 1; }
 
 int sb_shard_panels(const edigpu_sector* s, int world) { return (s->ib->npanels + world - 1) / world; }
 
