@@ -1,4 +1,4 @@
-// dev_mem.hpp -- the device-memory helpers of the C-ABI layer: upload, free, grow.  Every one returns 0, or 1 with the
+// dev_mem.hpp -- the device-memory helpers of the C-ABI layer: upload, allocate, free, grow.  Every one returns 0, or 1 with the
 // message set (EDIGPU_HIP).
 #pragma once
 #include <vector>
@@ -44,5 +44,27 @@ int dev_grow(T** d, N* cap, N need) {
   *cap = need;
   return 0;
 }
+
+#pragma GCC visibility push(hidden)
+// *d = a fresh buffer of n elements (of one when n == 0), contents undefined
+template <class T>
+int dev_alloc(T** d, size_t n) {
+  *d = nullptr;
+  EDIGPU_HIP(hipMalloc((void**)d, (n > 0 ? n : 1) * sizeof(T)));
+  return 0;
+}
+
+// p = a fresh buffer of n elements (of one when n == 0) that holds zeros once this returns: the old one is freed, the new
+// one is zeroed on the null stream and the DEVICE is synchronised, since the handles' non-blocking streams do not wait
+// for the null stream
+template <class T>
+int dev_realloc_zeroed_sync(T*& p, size_t n) {
+  dev_free(p);
+  if (dev_alloc(&p, n)) return 1;
+  EDIGPU_HIP(hipMemset(p, 0, (n > 0 ? n : 1) * sizeof(T)));
+  EDIGPU_HIP(hipDeviceSynchronize());
+  return 0;
+}
+#pragma GCC visibility pop
 
 }  // namespace edigpu

@@ -6,7 +6,7 @@
 // [c pcol - halo, (c + 1) pcol + halo).  send[c][i][j] is laid out so that one equal-split all-to-all delivers
 // recv[r][i][j] = rows r q + i in order, i.e. the column shard with row stride pw = pcol + 2 halo and no unpacking.
 //
-// Plain C++ shared by every kernel that packs or unpacks (kernels_ops.hip, kernels_lanczos.hip, edigpu_shard.hip) and by
+// Plain C++ shared by every kernel that packs or unpacks (kernels_ops.hip, kernels_lanczos.hip, kernels_shard.hip) and by
 // the host-only entry points edigpu_exchange_send_map / edigpu_exchange_back_map, through which the CPU suite drives
 // the product's own index arithmetic between gloo ranks (tests/test_sharding_gloo.py).
 #pragma once

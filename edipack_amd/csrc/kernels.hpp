@@ -160,6 +160,22 @@ int vec_unpack_add_dot2(int64_t dim_up, int64_t nrows, int64_t q, int64_t pcol, 
                         double* vout, const double* tmp, const double* back, double* out2, double* work,
                         hipStream_t st);
 
+// ---- one-reduction recurrence on shards (kernels_shard.hip); t / tprev: the reduced sums of the two previous steps ----
+// (null where there is none), work: 3 * kRedBlocks doubles, sums: where this rank's three sums of the step land
+#pragma GCC visibility push(hidden)
+// (v, w) <- ((w - alpha v) / beta, -beta v), nothing on the first step; send != null: the new v also goes into the
+// all-to-all send buffer of the column-block exchange.  n counts doubles
+int shard_rotate3(bool first, int64_t n, int64_t dim_up, int64_t q, int world, int64_t pcol, int halo, double* vin, double* vout,
+                  const double* t, const double* tprev, double* send, hipStream_t st);
+// w += tmp (+ back through the exchange's index map when back != null), then the three sums
+int shard_add_dot3(int64_t n, int64_t dim_up, int64_t q, int64_t pcol, int halo, const double* vin, double* vout,
+                   const double* tmp, const double* back, const double* tprev, double* work, double* sums, hipStream_t st);
+// the same two on vectors that share the padded panel layout element by element; n2 counts pairs of doubles
+int shard_panel_rotate(int64_t n2, double* x, const double* v, const double* t, const double* tprev, hipStream_t st);
+int shard_panel_add_dot(int64_t n2, const double* x, double* vdst, const double* rowhalf, const double* colhalf,
+                        const double* t, const double* tprev, double* work, double* sums, hipStream_t st);
+#pragma GCC visibility pop
+
 // ---- thick-restart Lanczos multi-vector kernels (kernels_trl.hip) ----
 // h_dev (2 doubles per basis vector: re, im) = Q^H w, then w -= Q h; n counts complex or real elements
 int trl_orthogonalize(int cplx, int64_t n, int nvec, const double* Q, int64_t ldq, double* w, double* h_dev,

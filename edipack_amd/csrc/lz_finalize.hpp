@@ -7,13 +7,14 @@
 #include <cstdint>
 
 #include "kernels.hpp"
+#include "lanczos_sums.hpp"
 
 namespace edigpu {
 
 // Called by ALL threads of one workgroup of blockDim.x = NT threads (a power of two <= 1024); sh: 3 * NT doubles of LDS.
 // partial = [np] <P|Q> | [np] sum (Q - sg P)^2 | [np] <P|P> with sg = scal[SC_ALPHA] (the previous alpha).
-// beta^2 = |Q - alpha P|^2 = qq - 2 d (alpha - sg vv) + d^2 vv, d = alpha - sg -- exact for any sg, so a spectrum far
-// from zero does not cancel; when the difference still loses more than ~3 digits (near-invariant subspace, rare) the
+// beta^2 = |Q - alpha P|^2 = qq - 2 d (alpha - sg vv) + d^2 vv, d = alpha - sg (lanczos_sums.hpp) -- exact for any sg, so
+// a spectrum far from zero does not cancel; when the difference still loses more than ~3 digits (near-invariant subspace, rare) the
 // workgroup recomputes |Q - alpha P|^2 by sweeping the two vectors.  iter < 0: the step index is scal[SC_NDONE].
 // COHERENT: the partials were written by other workgroups of the SAME launch with device-scope stores; read them with
 // device-scope loads (they bypass whatever this XCD's L2 still holds of the previous step's partials)
@@ -50,8 +51,7 @@ __device__ inline void lz_finalize_ab_device(const double* partial, int np, cons
     __syncthreads();
   }
   const double alpha = sa[0], qq = sq[0], vv = sn[0], sg = scal[SC_ALPHA];
-  const double d = alpha - sg;
-  double b2 = qq - 2.0 * d * (alpha - sg * vv) + d * d * vv;
+  double b2 = beta2_from_sums(alpha, qq, vv, sg);
   const bool exact = b2 < 1e-3 * qq;  // the same value in every thread
   __syncthreads();
   if (exact) {
@@ -74,7 +74,7 @@ __device__ inline void lz_finalize_ab_device(const double* partial, int np, cons
     scal[SC_AB + iter] = alpha;
     scal[SC_NDONE] = (double)(iter + 1);
     scal[SC_EXACT] = 0.0;
-    const double b = sqrt(b2 > 0.0 ? b2 : 0.0);
+    const double b = beta_from_beta2(b2);
     scal[SC_BETA] = b;
     // breakdown: |beta| below the threshold, or an exact zero / NaN whatever the threshold is
     if (!(fabs(b) > 0.0) || fabs(b) < scal[SC_THR])

@@ -1,5 +1,6 @@
 """Row shards of one sector state vector over the GPUs of a node: the shard plan and the ctypes front-end of the
-library's communicator (csrc/edigpu_shard.hip), which owns the exchange and the whole sharded recurrence.
+library's communicator (csrc/edigpu_comm.hip) and sharded calls (csrc/edigpu_shard.hip), which own the exchange and the
+whole sharded recurrence.
 
 One process per GPU.  Replaces the reference's MPI data flow:
 

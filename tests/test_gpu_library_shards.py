@@ -1,4 +1,4 @@
-"""The N > 1 path inside libedigpu.so (csrc/edigpu_shard.hip), called through the C ABI: communicator, the
+"""The N > 1 path inside libedigpu.so (csrc/edigpu_comm.hip, csrc/edigpu_shard.hip), called through the C ABI: communicator, the
 (Nloc, v, Hv) product on shards (spMatVec_mpi_*) and the sharded tridiagonalisation (sp_lanc_tridiag with MpiComm),
 against the CPU oracle.
 

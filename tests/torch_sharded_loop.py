@@ -1,7 +1,7 @@
 """Test infrastructure: the sharded Lanczos loops of rounds 1-2 written on torch ops and torch.distributed, driving the
 library's building-block entry points (edigpu_apply_local_dev / _remote_dev, edigpu_normal_apply_rows_dev / _cols_dev,
 the fused vector kernels) from Python.  The product path is the in-library loop behind ``LibraryComm``
-(edipack_amd/sharding.py, csrc/edigpu_shard.hip); these classes stay as an independent second implementation that the
+(edipack_amd/sharding.py, csrc/edigpu_comm.hip, csrc/edigpu_shard.hip); these classes stay as an independent second implementation that the
 parity tests compare it with, and as the host of the world-2/3 gloo tests."""
 from __future__ import annotations
 
@@ -501,5 +501,5 @@ def gpu_sharded_hamiltonian(model, workload_sector, world: int, rank: int, direc
 
 
 # -----------------------------------------------------------------------------------------------
-# the N > 1 path inside libedigpu.so (csrc/edigpu_shard.hip): communicator + sharded recurrence in C
+# the N > 1 path inside libedigpu.so (csrc/edigpu_comm.hip, csrc/edigpu_shard.hip): communicator + sharded recurrence in C
 # -----------------------------------------------------------------------------------------------
