@@ -183,6 +183,10 @@ SIGNATURES = {
     "edigpu_lanczos_eigh_sharded": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, _pd, _vp, _pint]),
     "edigpu_exchange_bench": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int32), _pd]),
     "edigpu_apply_cops_sharded": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _pd, _vp, _vp, _vp]),
+    "edigpu_occ_moments_sharded": (C.c_int, [_vp, _vp, _vp, C.c_int, _pd, _pd]),
+    "edigpu_apply_occ_sharded": (C.c_int, [_vp, _vp, _vp, _vp, _pd, _pd]),
+    "edigpu_apply_xph_sharded": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "edigpu_ph_rdm_sharded": (C.c_int, [_vp, _vp, _vp, C.c_int, _pd, _pd]),
     "edigpu_apply_cops_flat": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _pd, _vp, _vp, _vp, _vp]),
     "edigpu_lanczos_bench_sharded": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _pd, _pi64]),
     "edigpu_destroy": (C.c_int, [_vp]),

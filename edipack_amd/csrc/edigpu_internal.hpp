@@ -185,6 +185,7 @@ struct IbDev {
 struct OccDev {
   int norb = 0, flat = 0, nblk = 1, ncu = 0;
   int64_t dim_up = 0, dim_dw = 1;
+  int64_t first = 0, count = 0;  // shard view (edigpu_sector::occ_shard): the rows it was built for
   uint16_t* pu = nullptr;
   uint8_t* pd = nullptr;
   int32_t* order = nullptr;
@@ -193,10 +194,21 @@ struct OccDev {
   int64_t partial_cap = 0, sums_cap = 0;       // in doubles
 };
 void free_occ(edigpu_sector* s);
+// The shard view of the same tables (edigpu_sector::occ_shard; host_occ.hpp occ_shard_view): the rows [first, first +
+// count) of the sector -- down rows of normal mode, rows of superc / nonsu2 -- with their own down patterns (never
+// edigpu_sector::d_impd) and row order, indices local to the shard.  Built by the first sharded call, rebuilt when the
+// range changes.  occ_shard_moments leaves the nvec x kOccSums sums of this rank's rows in *sums_dev on the handle's
+// stream; occ_shard_apply enqueues the product there.  Neither launches anything for count == 0 (*sums_dev = null).
+int occ_shard_moments(edigpu_sector* s, int64_t first, int64_t count, const double* v_dev, int nvec, const double** sums_dev,
+                      const std::string& who);
+int occ_shard_apply(edigpu_sector* s, int64_t first, int64_t count, const double* src_dev, double* dst_dev, const double* w_up,
+                    const double* w_dw, const std::string& who);
 // device bytes of the tables above (made lazily, so the sector cache adds them to what it measured at build time)
 int64_t occ_table_bytes(const edigpu_sector* s);
 // the three refusals the occupation entry points share (ed_total_ud=F, hand-over handle, shard): 1 with the message set
 int occ_refuse(const edigpu_sector* s, const std::string& who);
+// the first two of them: what the sharded twins refuse as well
+int occ_refuse_kind(const edigpu_sector* s, const std::string& who);
 
 // Tables and workspace of edigpu_imp_rdm on a library-built whole normal-mode sector (host_rdm.hpp; kernels_rdm.hip),
 // made and uploaded by the first call on the handle and kept until edigpu_destroy.
@@ -213,6 +225,14 @@ void free_rdm_flat(edigpu_sector* s);
 // kernels_ph.hip), made and uploaded by the first call on the handle and kept until edigpu_destroy.
 struct PhDev;
 void free_ph(edigpu_sector* s);
+// The same on the rows [first, first + count) of the sector (edigpu_sector::ph_shard; host_ph.hpp ph_shard_plan_*), kept
+// like the occupation tables' shard view.  ph_shard_rdm leaves the nvec x ncls x ph_slots x cw sums of this rank's rows in
+// *sums_dev (null for count == 0); *ncls, *dimph, *cw describe them.
+// occ_refuse_kind, then nph = 0 and -- rdm -- DimPh > kPhMaxDim: the refusals of the phonon entry points but the shard one
+int ph_refuse_kind(const edigpu_sector* s, const std::string& who, bool rdm);
+int ph_shard_apply(edigpu_sector* s, int64_t first, int64_t count, const double* src_dev, double* dst_dev, const std::string& who);
+int ph_shard_rdm(edigpu_sector* s, int64_t first, int64_t count, const double* v_dev, int nvec, const double** sums_dev,
+                 const std::string& who);
 
 // Scratch buffer of the partner tables of the one-axis c / c^+ route (edigpu_axisop.hip; host_axisop.hpp,
 // kernels_axisop.hip), kept by the DESTINATION handle of a call and grown on demand, until edigpu_destroy.
@@ -343,11 +363,13 @@ struct edigpu_sector {
   double* d_dir_xtab = nullptr;
   // ---- occupation operators (lazily built) ----
   edigpu::OccDev* occ = nullptr;
+  edigpu::OccDev* occ_shard = nullptr;  // the view of a rank's rows (edigpu_*_sharded)
   // ---- impurity reduced density matrix (lazily built) ----
   edigpu::RdmDev* rdm = nullptr;
   edigpu::RdmFlatDev* rdm_flat = nullptr;
   // ---- phonon displacement seed and phonon density matrix (lazily built) ----
   edigpu::PhDev* ph = nullptr;
+  edigpu::PhDev* ph_shard = nullptr;    // the view of a rank's rows
   // ---- c / c^+ along one axis: table scratch of calls with this handle as destination (lazily built) ----
   edigpu::AxisDev* axis = nullptr;
   // ---- interleaved vectors of the batched product and recurrence (lazily built) ----

@@ -10,12 +10,17 @@
 
 namespace edigpu {
 
-void free_occ(edigpu_sector* s) {
-  if (!s || !s->occ) return;
-  OccDev* o = s->occ;
+static void free_occ_view(OccDev*& o) {
+  if (!o) return;
   dev_free_all(o->pu, o->pd, o->order, o->partial, o->sums);
   delete o;
-  s->occ = nullptr;
+  o = nullptr;
+}
+
+void free_occ(edigpu_sector* s) {
+  if (!s) return;
+  free_occ_view(s->occ);
+  free_occ_view(s->occ_shard);
 }
 
 static bool occ_served(const edigpu_sector* s) {
@@ -30,7 +35,7 @@ int64_t occ_table_bytes(const edigpu_sector* s) {
   return 2 * s->dim_up + ((base && base->d_impd) ? 0 : s->dim_dw) + 4 * s->dim_dw * (s->nph + 1) + workspace;
 }
 
-int occ_refuse(const edigpu_sector* s, const std::string& who) {
+int occ_refuse_kind(const edigpu_sector* s, const std::string& who) {
   if (s->kind == kOrbs) {
     set_error(who + ": ed_total_ud=F sectors are not supported");
     return 1;
@@ -40,6 +45,11 @@ int occ_refuse(const edigpu_sector* s, const std::string& who) {
               "edigpu_direct_build[_jz]); a hand-over handle has no sector map");
     return 1;
   }
+  return 0;
+}
+
+int occ_refuse(const edigpu_sector* s, const std::string& who) {
+  if (occ_refuse_kind(s, who)) return 1;
   if (!s->is_whole()) {
     set_error(who + ": the handle must hold the whole sector (shards are not supported)");
     return 1;
@@ -62,7 +72,7 @@ static int occ_build(edigpu_sector* s, const std::string& who) {
   EDIGPU_HIP(hipDeviceGetAttribute(&o->ncu, hipDeviceAttributeMultiprocessorCount, s->device));
   auto fail = [&](const std::string& why) {
     set_error(who + ": " + why);
-    free_occ(s);
+    free_occ_view(s->occ);
     return 1;
   };
   if (s->is_flat_family()) {
@@ -74,7 +84,7 @@ static int occ_build(edigpu_sector* s, const std::string& who) {
     const int rc = s->jz ? edigpu_sector_map_jz(&m, s->sec_a, s->sec_b, map.data(), &n)
                          : edigpu_sector_map(&m, s->sec_a, 0, 0, map.data(), &n);
     if (rc) {
-      free_occ(s);
+      free_occ_view(s->occ);
       return 1;  // the map's message stands
     }
     if (n != o->dim_up) return fail("the sector map does not have the handle's dimension");
@@ -88,7 +98,7 @@ static int occ_build(edigpu_sector* s, const std::string& who) {
   std::vector<int32_t> mu((size_t)s->dim_up), md((size_t)s->dim_dw);
   int64_t nu = s->dim_up, nd = s->dim_dw;
   if (edigpu_sector_map(&m, s->sec_a, s->sec_b, 0, mu.data(), &nu) || edigpu_sector_map(&m, s->sec_a, s->sec_b, 1, md.data(), &nd)) {
-    free_occ(s);
+    free_occ_view(s->occ);
     return 1;
   }
   if (nu != s->dim_up || nd != s->dim_dw) return fail("the sector maps do not have the handle's dimensions");
@@ -106,8 +116,64 @@ static int occ_build(edigpu_sector* s, const std::string& who) {
   return 0;
 }
 
-static OccTables occ_args(const edigpu_sector* s) {
-  const OccDev* o = s->occ;
+// the view of the rows [first, first + count), (re)built when the range is not the one it holds
+static int occ_shard_build(edigpu_sector* s, int64_t first, int64_t count, const std::string& who) {
+  if (s->occ_shard && s->occ_shard->first == first && s->occ_shard->count == count) return 0;
+  free_occ_view(s->occ_shard);
+  const edigpu_model& m = s->model;
+  if (m.norb < 1 || m.norb > kOccMaxOrb) {
+    set_error(who + ": norb out of range");
+    return 1;
+  }
+  auto fail = [&](const std::string& why) {
+    if (!why.empty()) set_error(who + ": " + why);  // (else the map's message stands)
+    free_occ_view(s->occ_shard);
+    return 1;
+  };
+  OccDev* o = new OccDev();
+  s->occ_shard = o;
+  o->norb = m.norb;
+  o->nblk = s->nph + 1;
+  EDIGPU_HIP(hipDeviceGetAttribute(&o->ncu, hipDeviceAttributeMultiprocessorCount, s->device));
+  OccShardView view;
+  if (s->is_flat_family()) {
+    int64_t n = s->dim / o->nblk;  // the electronic rows of the WHOLE sector (dim_el of a phonon shard is the shard's)
+    std::vector<int32_t> map((size_t)n);
+    const int64_t want = n;
+    if (s->jz ? edigpu_sector_map_jz(&m, s->sec_a, s->sec_b, map.data(), &n) : edigpu_sector_map(&m, s->sec_a, 0, 0, map.data(), &n))
+      return fail("");
+    if (n != want) return fail("the sector map does not have the handle's dimension");
+    std::vector<uint16_t> pat(map.size());
+    occ_patterns_state(map.data(), n, m.norb, model_ns(m), pat.data());
+    occ_shard_view(pat.data(), n, true, o->nblk, first, count, view);
+    if (view.first != first || view.count != count) return fail("the rows are not inside the sector");
+    o->flat = 1;
+    o->dim_up = count;
+    o->dim_dw = 1;
+    if (dev_upload(&o->pu, view.pu)) return fail(edigpu_last_error());
+  } else {
+    std::vector<int32_t> mu((size_t)s->dim_up), md((size_t)s->dim_dw);
+    int64_t nu = s->dim_up, nd = s->dim_dw;
+    if (edigpu_sector_map(&m, s->sec_a, s->sec_b, 0, mu.data(), &nu) || edigpu_sector_map(&m, s->sec_a, s->sec_b, 1, md.data(), &nd))
+      return fail("");
+    if (nu != s->dim_up || nd != s->dim_dw) return fail("the sector maps do not have the handle's dimensions");
+    std::vector<uint16_t> pu(mu.size()), pdw(md.size());
+    occ_patterns_word(mu.data(), nu, m.norb, pu.data());
+    occ_patterns_word(md.data(), nd, m.norb, pdw.data());
+    occ_shard_view(pdw.data(), nd, false, o->nblk, first, count, view);
+    if (view.first != first || view.count != count) return fail("the rows are not inside the sector");
+    o->dim_up = s->dim_up;
+    o->dim_dw = count;
+    std::copy(view.run, view.run + kOccMaxPat + 1, o->run);
+    // the shard's own copy of its down patterns: edigpu_sector::d_impd starts at row 0 of the sector
+    if (dev_upload(&o->pu, pu) || dev_upload(&o->order, view.order) || dev_upload(&o->pd, view.pd)) return fail(edigpu_last_error());
+  }
+  o->first = first;
+  o->count = count;
+  return 0;
+}
+
+static OccTables occ_args(const edigpu_sector* s, const OccDev* o) {
   OccTables t;
   t.norb = o->norb;
   t.flat = o->flat;
@@ -122,9 +188,8 @@ static OccTables occ_args(const edigpu_sector* s) {
 }
 
 // sums of nvec vectors into o->sums on the handle's stream (workspace grown on demand)
-static int occ_moments_enqueue(edigpu_sector* s, const double* v_dev, int nvec) {
-  OccDev* o = s->occ;
-  const OccTables t = occ_args(s);
+static int occ_moments_enqueue(edigpu_sector* s, OccDev* o, const double* v_dev, int nvec) {
+  const OccTables t = occ_args(s, o);
   const int nwaves = occ_moment_waves(t, o->ncu);
   const int64_t need_partial = (int64_t)nvec * nwaves * kOccSums, need_sums = (int64_t)nvec * kOccSums;
   if (dev_grow(&o->partial, &o->partial_cap, need_partial) || dev_grow(&o->sums, &o->sums_cap, need_sums)) return 1;
@@ -133,6 +198,25 @@ static int occ_moments_enqueue(edigpu_sector* s, const double* v_dev, int nvec) 
   OccRuns rn;
   std::copy(o->run, o->run + 33, rn.run);
   return launch_occ_moments(t, sl, rn, v_dev, nvec, nwaves, o->partial, o->sums, s->stream);
+}
+
+int occ_shard_moments(edigpu_sector* s, int64_t first, int64_t count, const double* v_dev, int nvec, const double** sums_dev,
+                      const std::string& who) {
+  *sums_dev = nullptr;
+  if (count <= 0) return 0;
+  if (occ_shard_build(s, first, count, who) || occ_moments_enqueue(s, s->occ_shard, v_dev, nvec)) return 1;
+  *sums_dev = s->occ_shard->sums;
+  return 0;
+}
+
+int occ_shard_apply(edigpu_sector* s, int64_t first, int64_t count, const double* src_dev, double* dst_dev, const double* w_up,
+                    const double* w_dw, const std::string& who) {
+  if (count <= 0) return 0;
+  if (occ_shard_build(s, first, count, who)) return 1;
+  OccWeights w;
+  occ_weight_table(w_up, s->occ_shard->norb, w.wu);
+  occ_weight_table(w_dw, s->occ_shard->norb, w.wd);
+  return launch_apply_occ(occ_args(s, s->occ_shard), w, src_dev, dst_dev, s->stream);
 }
 
 }  // namespace edigpu
@@ -154,7 +238,7 @@ int edigpu_apply_occ(edigpu_handle s, const double* v_src_dev, double* v_dst_dev
   OccWeights w;
   occ_weight_table(w_up, s->occ->norb, w.wu);
   occ_weight_table(w_dw, s->occ->norb, w.wd);
-  return launch_apply_occ(occ_args(s), w, v_src_dev, v_dst_dev, (hipStream_t)stream);
+  return launch_apply_occ(occ_args(s, s->occ), w, v_src_dev, v_dst_dev, (hipStream_t)stream);
 }
 
 int edigpu_occ_moments(edigpu_handle s, const double* v_dev, int nvec, double* moments_host, double* norm2_host) {
@@ -165,7 +249,7 @@ int edigpu_occ_moments(edigpu_handle s, const double* v_dev, int nvec, double* m
   }
   if (occ_refuse(s, who)) return 1;
   EDIGPU_HIP(hipSetDevice(s->device));
-  if (occ_build(s, who) || occ_moments_enqueue(s, v_dev, nvec)) return 1;
+  if (occ_build(s, who) || occ_moments_enqueue(s, s->occ, v_dev, nvec)) return 1;
   const OccDev* o = s->occ;
   std::vector<double> sums((size_t)nvec * kOccSums);
   EDIGPU_HIP(hipMemcpyAsync(sums.data(), o->sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -191,7 +275,7 @@ int edigpu_time_occ(edigpu_handle s, double* v_dev, int warmup, int steps, doubl
   std::fill(one, one + kOccMaxOrb, 1.0);  // weights 0, 1, 2: the values of v stay finite over any number of passes
   occ_weight_table(one, s->occ->norb, w.wu);
   occ_weight_table(one, s->occ->norb, w.wd);
-  const OccTables t = occ_args(s);
+  const OccTables t = occ_args(s, s->occ);
   hipEvent_t e0, e1;
   EDIGPU_HIP(hipEventCreate(&e0));
   EDIGPU_HIP(hipEventCreate(&e1));
@@ -200,7 +284,7 @@ int edigpu_time_occ(edigpu_handle s, double* v_dev, int warmup, int steps, doubl
     std::vector<float> ms((size_t)steps, 0.f);
     for (int k = 0; k < warmup + steps && !rc; k++) {
       rc |= hipEventRecord(e0, s->stream) != hipSuccess;
-      rc |= which == 0 ? occ_moments_enqueue(s, v_dev, 1) : launch_apply_occ(t, w, v_dev, v_dev, s->stream);
+      rc |= which == 0 ? occ_moments_enqueue(s, s->occ, v_dev, 1) : launch_apply_occ(t, w, v_dev, v_dev, s->stream);
       rc |= hipEventRecord(e1, s->stream) != hipSuccess;
       rc |= hipEventSynchronize(e1) != hipSuccess;
       if (!rc && k >= warmup) rc |= hipEventElapsedTime(&ms[(size_t)(k - warmup)], e0, e1) != hipSuccess;

@@ -27,25 +27,7 @@
 
 namespace edigpu {
 
-struct ShardGeom {
-  bool transposed = false;  // normal mode, whole-sector handle: two all-to-alls per product
-  int w = 1;                // doubles per element
-  int64_t units = 0, unit_len = 1, q = 0, first = 0, count = 0;
-  int64_t nloc = 0, chunk = 0;  // elements of this rank's shard / of the padded chunk
-  int nblk = 1;                 // phonon blocks per vector (Nph + 1): the local vector is nblk blocks of blk elements
-  int64_t blk = 0;
-  // transposed exchange
-  int halo = 0;
-  int64_t pcol = 0, col_first = 0, col_count = 0, pw = 0, xlen = 0;
-  // the same exchange on the padded panel layout of the local-block kernels (kernels_sb.hip, "row shards"): no packing,
-  // no halo -- the partner columns of an Hnd term sit in the same panel
-  bool block = false;
-  int npmax = 0;      // panels per rank
-  int64_t bplen = 0;  // doubles of a vector in the shard form: world * npmax * q * 16
-  LoopSwitches loop = {};  // the environment shard_geometry saw: held for the product, recurrence or solve that g serves
-};
-
-static int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g) {
+int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g) {
   g.loop = LoopSwitches::sample();
   g.w = s->is_complex ? 2 : 1;
   g.transposed = s->kind == kNormal && s->is_whole() && normal_transposable_el(s);

@@ -1,0 +1,205 @@
+// edigpu_shard_obs.hip -- occupation and phonon observables on sharded vectors (include/edigpu.h:
+// edigpu_occ_moments_sharded, edigpu_apply_occ_sharded, edigpu_apply_xph_sharded, edigpu_ph_rdm_sharded).
+//
+// The four operators are local to a row and to the row's phonon blocks, and a rank holds all phonon blocks of its rows:
+// the kernels of kernels_occ.hip / kernels_ph.hip run unchanged on tables made for the rank's rows (the shard views of
+// edigpu_occ.hip / edigpu_ph.hip; host_occ.hpp occ_shard_view, host_ph.hpp ph_shard_plan_*).  The per-rank sums leave
+// the fixed-order final kernels, one all-reduce adds the packed sums of the ranks (in rank order on every rank), and the
+// host expansions of the single-GPU entries follow: no floating-point atomics, the same bits on every rank and call.
+// Takes the place of gathering every state on one rank (es_return_dvector_mpi, ED_EIGENSPACE.f90:723-793).
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "host_occ.hpp"
+#include "host_ph.hpp"
+#include "kernels.hpp"
+#include "shard_comm.hpp"
+
+namespace edigpu {
+namespace {
+
+// this rank's rows of handle s (down rows of normal mode, rows of superc / nonsu2) and the size of its shard
+struct ObsGeom {
+  int64_t first = 0, count = 0;
+  int64_t len = 0;  // doubles of one vector's shard
+};
+
+// the refusals the four entries share, then the geometry of the sharded product (its messages stand)
+int obs_geometry(edigpu_sector* s, edigpu_comm_s* c, const std::string& who, bool phonon, bool rdm, ObsGeom& og) {
+  if (phonon ? ph_refuse_kind(s, who, rdm) : occ_refuse_kind(s, who)) return 1;
+  if (s->model.norb < 1 || s->model.norb > kOccMaxOrb) {
+    set_error(who + ": norb out of range");
+    return 1;
+  }
+  ShardGeom g;
+  if (shard_geometry(real_image(s), c, g)) return 1;
+  og.first = g.first;
+  og.count = g.count;
+  og.len = g.count * (s->is_normal_family() ? s->dim_up : 1) * (s->nph + 1) * (s->is_complex ? 2 : 1);
+  return 0;
+}
+
+bool on_device(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // (a plain host pointer, on runtimes that do not know "unregistered")
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
+// the vector the kernels read: v itself when it lives on the device, else its copy in the communicator's buffer at
+// `offset` doubles (the buffer holds at least `cap` doubles after this)
+int stage_in(edigpu_comm_s* c, const double* v, int64_t n, int64_t offset, int64_t cap, hipStream_t st, const double** out) {
+  if (on_device(v)) {
+    *out = v;
+    return 0;
+  }
+  if (dev_grow(&c->ws.obs, &c->ws.obs_cap, cap)) return 1;
+  EDIGPU_HIP(hipMemcpyAsync(c->ws.obs + offset, v, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+  *out = c->ws.obs + offset;
+  return 0;
+}
+
+// red[0:n) <- the sum over the ranks of `mine` (null: this rank owns no row and adds zeros), then to the host
+int reduce_to_host(edigpu_comm_s* c, const double* mine, size_t n, hipStream_t st, std::vector<double>& host) {
+  if (dev_grow(&c->ws.red, &c->ws.red_cap, (int64_t)n)) return 1;
+  if (mine) EDIGPU_HIP(hipMemcpyAsync(c->ws.red, mine, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  else EDIGPU_HIP(hipMemsetAsync(c->ws.red, 0, n * sizeof(double), st));
+  if (comm_all_reduce(c, c->ws.red, n, st)) return 1;
+  host.resize(n);
+  EDIGPU_HIP(hipMemcpyAsync(host.data(), c->ws.red, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  EDIGPU_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+// dst <- op(src) on this rank's shard, host or device vectors; op(src_dev, dst_dev) enqueues on st.  Host vectors go
+// through the communicator's buffer: the source at its start, a host destination in place of it (inplace) or behind it
+template <class Op>
+int apply_on_shard(edigpu_comm_s* c, const ObsGeom& og, const double* src, double* dst, bool inplace, hipStream_t st, Op op) {
+  const int64_t half = (og.len + 1) / 2 * 2;  // (the second vector starts on 16 bytes as well)
+  const double* sd = nullptr;
+  if (stage_in(c, src, og.len, 0, 2 * half, st, &sd)) return 1;
+  double* dd = dst;
+  if (!on_device(dst)) {
+    if (dev_grow(&c->ws.obs, &c->ws.obs_cap, 2 * half)) return 1;  // (kept when stage_in made it)
+    dd = c->ws.obs + (inplace && sd == c->ws.obs ? 0 : half);
+  }
+  if (op(sd, dd)) return 1;
+  if (dd != dst) EDIGPU_HIP(hipMemcpyAsync(dst, dd, (size_t)og.len * sizeof(double), hipMemcpyDeviceToHost, st));
+  EDIGPU_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+}  // namespace
+}  // namespace edigpu
+
+using namespace edigpu;
+
+extern "C" {
+
+int edigpu_occ_moments_sharded(edigpu_handle s, edigpu_comm c, const double* v_shard, int nvec, double* moments_host,
+                               double* norm2_host) {
+  const std::string who = "edigpu_occ_moments_sharded";
+  if (!s || !c || !moments_host || nvec <= 0) {
+    set_error(who + (!s || !c || !moments_host ? ": NULL argument" : ": nvec must be positive"));
+    return 1;
+  }
+  ObsGeom og;
+  if (obs_geometry(s, c, who, false, false, og)) return 1;
+  if (og.count > 0 && !v_shard) {
+    set_error(who + ": NULL argument");
+    return 1;
+  }
+  EDIGPU_HIP(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  const double *vd = nullptr, *mine = nullptr;
+  if (og.count > 0 && (stage_in(c, v_shard, og.len * nvec, 0, og.len * nvec, st, &vd) ||
+                       occ_shard_moments(s, og.first, og.count, vd, nvec, &mine, who)))
+    return 1;
+  std::vector<double> sums;
+  if (reduce_to_host(c, mine, (size_t)nvec * kOccSums, st, sums)) return 1;
+  const int norb = s->model.norb, n2 = 2 * norb;
+  for (int k = 0; k < nvec; k++)
+    occ_expand_sums(sums.data() + (size_t)k * kOccSums, norb, moments_host + (size_t)k * n2 * n2, norm2_host ? norm2_host + k : nullptr);
+  return 0;
+}
+
+int edigpu_apply_occ_sharded(edigpu_handle s, edigpu_comm c, const double* v_src_shard, double* v_dst_shard, const double* w_up,
+                             const double* w_dw) {
+  const std::string who = "edigpu_apply_occ_sharded";
+  if (!s || !c || !w_up || !w_dw) {
+    set_error(who + ": NULL argument");
+    return 1;
+  }
+  ObsGeom og;
+  if (obs_geometry(s, c, who, false, false, og)) return 1;
+  if (og.count <= 0) return 0;
+  if (!v_src_shard || !v_dst_shard) {
+    set_error(who + ": NULL argument");
+    return 1;
+  }
+  EDIGPU_HIP(hipSetDevice(s->device));
+  return apply_on_shard(c, og, v_src_shard, v_dst_shard, true, s->stream, [&](const double* src, double* dst) {
+    return occ_shard_apply(s, og.first, og.count, src, dst, w_up, w_dw, who);
+  });
+}
+
+int edigpu_apply_xph_sharded(edigpu_handle s, edigpu_comm c, const double* v_src_shard, double* v_dst_shard) {
+  const std::string who = "edigpu_apply_xph_sharded";
+  if (!s || !c) {
+    set_error(who + ": NULL argument");
+    return 1;
+  }
+  ObsGeom og;
+  if (obs_geometry(s, c, who, true, false, og)) return 1;
+  if (og.count <= 0) return 0;
+  if (!v_src_shard || !v_dst_shard) {
+    set_error(who + ": NULL argument");
+    return 1;
+  }
+  const uintptr_t a = reinterpret_cast<uintptr_t>(v_src_shard), b = reinterpret_cast<uintptr_t>(v_dst_shard);
+  const uintptr_t bytes = (uintptr_t)og.len * sizeof(double);
+  if (a < b + bytes && b < a + bytes) {
+    set_error(who + ": the destination must not overlap the source (an output block reads its two neighbours)");
+    return 1;
+  }
+  EDIGPU_HIP(hipSetDevice(s->device));
+  return apply_on_shard(c, og, v_src_shard, v_dst_shard, false, s->stream, [&](const double* src, double* dst) {
+    return ph_shard_apply(s, og.first, og.count, src, dst, who);
+  });
+}
+
+int edigpu_ph_rdm_sharded(edigpu_handle s, edigpu_comm c, const double* v_shard, int nvec, double* rho_host, double* norm2_host) {
+  const std::string who = "edigpu_ph_rdm_sharded";
+  if (!s || !c || !rho_host || nvec <= 0) {
+    set_error(who + (!s || !c || !rho_host ? ": NULL argument" : ": nvec must be positive"));
+    return 1;
+  }
+  ObsGeom og;
+  if (obs_geometry(s, c, who, true, true, og)) return 1;
+  if (og.count > 0 && !v_shard) {
+    set_error(who + ": NULL argument");
+    return 1;
+  }
+  EDIGPU_HIP(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  const double *vd = nullptr, *mine = nullptr;
+  if (og.count > 0 && (stage_in(c, v_shard, og.len * nvec, 0, og.len * nvec, st, &vd) ||
+                       ph_shard_rdm(s, og.first, og.count, vd, nvec, &mine, who)))
+    return 1;
+  const int dimph = s->nph + 1, cw = s->is_complex ? 2 : 1, ncls = ph_num_classes(s->model.norb);
+  const size_t nslot = (size_t)ph_slots(dimph) * cw, nmat = (size_t)dimph * dimph * cw;
+  std::vector<double> sums;
+  if (reduce_to_host(c, mine, (size_t)nvec * ncls * nslot, st, sums)) return 1;
+  for (int k = 0; k < nvec; k++) {
+    double tr = 0.0;
+    for (int cl = 0; cl < ncls; cl++)
+      tr += ph_expand_slots(sums.data() + ((size_t)k * ncls + cl) * nslot, dimph, cw, rho_host + ((size_t)k * ncls + cl) * nmat);
+    if (norm2_host) norm2_host[k] = tr;
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -37,6 +37,21 @@ void occ_sort_rows(const uint8_t* pd, int64_t dim_dw, int nblk, std::vector<int3
   for (int64_t r = 0; r < nrows; r++) order[(size_t)next[pd[r % dim_dw]]++] = (int32_t)r;
 }
 
+void occ_shard_view(const uint16_t* pat, int64_t n, bool flat, int nblk, int64_t first, int64_t count, OccShardView& view) {
+  view = OccShardView();
+  const int64_t lo = first < 0 ? 0 : (first > n ? n : first);
+  const int64_t want = count < 0 ? 0 : count;
+  const int64_t hi = want > n - lo ? n : lo + want;
+  view.first = lo;
+  view.count = hi - lo;
+  if (flat) {
+    view.pu.assign(pat + lo, pat + hi);
+    return;
+  }
+  view.pd.assign(pat + lo, pat + hi);
+  occ_sort_rows(view.pd.data(), view.count, nblk, view.order, view.run);
+}
+
 int occ_sum_slots(int norb, uint8_t* need_up, uint8_t* need_dw) {
   for (int t = 0; t < kOccSums; t++) need_up[t] = need_dw[t] = 0xFF;
   need_up[0] = need_dw[0] = 0;

@@ -26,6 +26,19 @@ void occ_weight_table(const double* w, int norb, double* tab);
 // entries).  The moments kernel walks a run with one down pattern for every lane.
 void occ_sort_rows(const uint8_t* pd, int64_t dim_dw, int nblk, std::vector<int32_t>& order, int32_t* run);
 
+// The tables of a rank's rows [first, first + count) of a sector (edigpu_*_sharded of the occupation operators): the
+// range is cut to the sector, a rank past the last row gets empty tables.  Normal mode (flat = false): pat = the down
+// patterns pd[n], the view's pd = that slice and order / run = occ_sort_rows of it over nblk blocks of `count` local
+// rows -- the up patterns are the sector's own.  Flat: pat = the state patterns, pu = their slice.
+struct OccShardView {
+  int64_t first = 0, count = 0;  // after the cut
+  std::vector<uint16_t> pu;      // flat only
+  std::vector<uint8_t> pd;       // normal only
+  std::vector<int32_t> order;
+  int32_t run[kOccMaxPat + 1] = {0};
+};
+void occ_shard_view(const uint16_t* pat, int64_t n, bool flat, int nblk, int64_t first, int64_t count, OccShardView& view);
+
 // The sums a vector is reduced to: slot 0 = <v|v>, then the upper triangle (x <= y, row-major) of the 2 norb x 2 norb
 // moment matrix, x = a for (a, up) and norb + a for (a, down).  Per slot the up bits and the down bits an element's
 // patterns must hold to count (need_up / need_dw, kOccSums entries each; unused slots hold 0xFF).  Returns the slots used.

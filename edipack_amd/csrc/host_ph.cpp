@@ -98,6 +98,25 @@ void ph_plan_flat(const uint16_t* pat, int64_t dim_el, int norb, int64_t target,
   finish_plan(plan);
 }
 
+namespace {
+void cut_range(int64_t n, int64_t& first, int64_t& count) {
+  first = std::max<int64_t>(0, std::min(first, n));
+  count = std::max<int64_t>(0, std::min(count, n - first));
+}
+}  // namespace
+
+void ph_shard_plan_normal(const uint16_t* pu, int64_t dim_up, const uint16_t* pd, int64_t dim_dw, int64_t first, int64_t count,
+                          int norb, int64_t target, PhPlan& plan) {
+  cut_range(dim_dw, first, count);
+  ph_plan_normal(pu, dim_up, pd + first, count, norb, target, plan);
+}
+
+void ph_shard_plan_flat(const uint16_t* pat, int64_t dim_el, int64_t first, int64_t count, int norb, int64_t target,
+                        PhPlan& plan) {
+  cut_range(dim_el, first, count);
+  ph_plan_flat(pat + first, count, norb, target, plan);
+}
+
 double ph_expand_slots(const double* slots, int dimph, int cw, double* rho) {
   double tr = 0.0;
   for (int n = 0; n < dimph; n++)

@@ -45,6 +45,15 @@ void ph_plan_normal(const uint16_t* pu, int64_t dim_up, const uint16_t* pd, int6
 // superc / nonsu2: pat[dim_el] (occ_patterns_state)
 void ph_plan_flat(const uint16_t* pat, int64_t dim_el, int norb, int64_t target, PhPlan& plan);
 
+// The plan of a rank's rows [first, first + count) of a sector (edigpu_ph_rdm_sharded), the range cut to the sector: the
+// down rows pd[first ..] of normal mode (dim_rows = the rows left, the columns are the sector's own), the states
+// pat[first ..] of a superc / nonsu2 sector (dim_cols = the states left).  Indices are local to the shard; a rank past the
+// last row gets a plan without units.
+void ph_shard_plan_normal(const uint16_t* pu, int64_t dim_up, const uint16_t* pd, int64_t dim_dw, int64_t first, int64_t count,
+                          int norb, int64_t target, PhPlan& plan);
+void ph_shard_plan_flat(const uint16_t* pat, int64_t dim_el, int64_t first, int64_t count, int norb, int64_t target,
+                        PhPlan& plan);
+
 // slots of the upper triangle n <= m of a DimPh x DimPh matrix, row-major
 inline int ph_slots(int dimph) { return dimph * (dimph + 1) / 2; }
 inline int ph_slot(int dimph, int n, int m) { return n * dimph - n * (n - 1) / 2 + (m - n); }

@@ -1,5 +1,6 @@
 // shard_comm.hpp -- what the communicator (edigpu_comm.hip) and the sharded product and recurrence (edigpu_shard.hip)
-// share: the communicator's state, its three collectives and two predicates.  Not part of the ABI.
+// share with the observables on shards (edigpu_shard_obs.hip): the communicator's state, its three collectives and two
+// predicates, the geometry of a shard.  Not part of the ABI.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -23,8 +24,11 @@ struct ShardWorkspace {
   double* bp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   double *hist = nullptr, *work = nullptr, *scr = nullptr;
   int64_t hist_cap = 0;
+  // observables on shards (edigpu_shard_obs.hip): host vectors staged for the kernels, the packed sums of a reduction
+  double *obs = nullptr, *red = nullptr;
+  int64_t obs_cap = 0, red_cap = 0;
   void release() {  // (with the communicator's device current)
-    dev_free_all(vin, vout, tmp, vfull, send, recv, hvc, back, hist, work, scr, bp[0], bp[1], bp[2], bp[3], bp[4]);
+    dev_free_all(vin, vout, tmp, vfull, send, recv, hvc, back, hist, work, scr, bp[0], bp[1], bp[2], bp[3], bp[4], obs, red);
   }
   ~ShardWorkspace() { release(); }
 };
@@ -64,6 +68,29 @@ inline bool alone(const edigpu_comm_s* c) { return c->world == 1 && !force_colle
 // _CMPLX_NORMAL held as one real sector on the doubled up index: its down rows shard like any real sector's (each row
 // 2 DimUp doubles = DimUp complex elements), so every sharded call on a complex sector runs on that image
 inline edigpu_sector* real_image(edigpu_sector* s) { return s->kind == kCmplxNormal && s->sub_d ? s->sub_d : s; }
+
+// How a sector's vector is cut over the ranks of a communicator (edigpu_shard.hip shard_geometry)
+struct ShardGeom {
+  bool transposed = false;  // normal mode, whole-sector handle: two all-to-alls per product
+  int w = 1;                // doubles per element
+  int64_t units = 0, unit_len = 1, q = 0, first = 0, count = 0;
+  int64_t nloc = 0, chunk = 0;  // elements of this rank's shard / of the padded chunk
+  int nblk = 1;                 // phonon blocks per vector (Nph + 1): the local vector is nblk blocks of blk elements
+  int64_t blk = 0;
+  // transposed exchange
+  int halo = 0;
+  int64_t pcol = 0, col_first = 0, col_count = 0, pw = 0, xlen = 0;
+  // the same exchange on the padded panel layout of the local-block kernels (kernels_sb.hip, "row shards"): no packing,
+  // no halo -- the partner columns of an Hnd term sit in the same panel
+  bool block = false;
+  int npmax = 0;      // panels per rank
+  int64_t bplen = 0;  // doubles of a vector in the shard form: world * npmax * q * 16
+  LoopSwitches loop = {};  // the environment shard_geometry saw: held for the product, recurrence or solve that g serves
+};
+
+// g <- the geometry of handle s on communicator c, 0; or 1 with the message set: the handle is not this rank's shard, a
+// phonon sector with a general g_ph(a,b), a four-product complex sector.  Complex normal-mode handles: pass real_image(s).
+int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g);
 
 // The collectives (edigpu_comm.hip), each enqueued: on the communicator's own stream, bracketed by events so that it
 // runs after what `caller` holds so far and `caller` goes on after it; a caller that passes c->side places its own events.

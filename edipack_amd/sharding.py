@@ -176,6 +176,86 @@ class LibraryComm:
             out.ctypes.data_as(C.c_void_p) if out.size else None, n, a, cr, io, sp), "edigpu_apply_cops_sharded")
         return out
 
+    # ---- occupation and phonon observables on shards (csrc/edigpu_shard_obs.hip) -------------------------------
+    # A shard is a numpy array of this rank's elements (several vectors: [nvec, nloc]) or an int, the address of
+    # the same on the device -- e.g. the evecs of eigh_multi uploaded, or a torch tensor's data_ptr().  The library
+    # knows the shard's length from the handle and the communicator; a rank that owns no row passes an empty array.
+    @staticmethod
+    def _shard_ptr(h, v):
+        """(pointer or None, the array that must stay alive)"""
+        import ctypes as C
+        import numpy as np
+        if isinstance(v, (int, np.integer)):
+            return (C.c_void_p(int(v)) if v else None), None
+        a = np.ascontiguousarray(v, dtype=h.dtype)
+        return (a.ctypes.data_as(C.c_void_p) if a.size else None), a
+
+    def occ_moments(self, h, v_shard, nvec: int = 1):
+        """SectorHamiltonian.occ_moments of nvec vectors held as shards: (M[nvec, 2 norb, 2 norb], norm2[nvec]), the sums
+        over all ranks, the same bits on every rank.  Collective."""
+        import numpy as np
+        n2 = 2 * (h.norb or self._capi.MAXORB)
+        m, nrm = np.zeros((nvec, n2, n2)), np.zeros(nvec)
+        p, _keep = self._shard_ptr(h, v_shard)
+        self._capi.check(self._capi.lib().edigpu_occ_moments_sharded(h._h, self._c, p, nvec, self._capi.pd(m),
+                                                                     self._capi.pd(nrm)), "edigpu_occ_moments_sharded")
+        return m, nrm
+
+    def apply_occ(self, h, v_shard, w_up, w_dw, out=None):
+        """sum_a (w_up[a] n_{a,up} + w_dw[a] n_{a,dw}) on this rank's shard; no exchange, a rank may call it alone.
+        A numpy shard returns the product as a new array; a device pointer is overwritten in place, or `out` (a device
+        pointer) receives the product, and None is returned.  Returns after the device has finished."""
+        import numpy as np
+        wu = np.ascontiguousarray(w_up, dtype=np.float64)
+        wd = np.ascontiguousarray(w_dw, dtype=np.float64)
+        if h.norb and (wu.size != h.norb or wd.size != h.norb):
+            raise ValueError("apply_occ: w_up and w_dw need norb entries each")
+        src, keep = self._shard_ptr(h, v_shard)
+        res = None if keep is None else np.empty_like(keep)
+        dst = src if keep is None and out is None else self._shard_ptr(h, out if keep is None else res)[0]
+        self._capi.check(self._capi.lib().edigpu_apply_occ_sharded(h._h, self._c, src, dst, self._capi.pd(wu),
+                                                                   self._capi.pd(wd)), "edigpu_apply_occ_sharded")
+        return res
+
+    def apply_n(self, h, v_shard, iorb: int, out=None):
+        """apply_op_N on this rank's shard: (n_{iorb,up} + n_{iorb,dw}) |v>."""
+        import numpy as np
+        w = np.zeros(max(h.norb, iorb + 1))
+        w[iorb] = 1.0
+        return self.apply_occ(h, v_shard, w, w, out)
+
+    def apply_sz(self, h, v_shard, iorb: int, out=None):
+        """apply_op_Sz on this rank's shard: (n_{iorb,up} - n_{iorb,dw}) / 2 |v>."""
+        import numpy as np
+        w = np.zeros(max(h.norb, iorb + 1))
+        w[iorb] = 0.5
+        return self.apply_occ(h, v_shard, w, -w, out)
+
+    def apply_xph(self, h, v_shard, out=None):
+        """(b + b^dagger) |v> on this rank's shard of a phonon sector; no exchange.  A numpy shard returns the seed as a
+        new array; a device pointer needs `out`, a device pointer that does not overlap it."""
+        import numpy as np
+        src, keep = self._shard_ptr(h, v_shard)
+        if keep is None and out is None:
+            raise ValueError("apply_xph: a device shard needs `out` (the seed cannot overwrite its source)")
+        res = None if keep is None else np.empty_like(keep)
+        dst = self._shard_ptr(h, out if keep is None else res)[0]
+        self._capi.check(self._capi.lib().edigpu_apply_xph_sharded(h._h, self._c, src, dst), "edigpu_apply_xph_sharded")
+        return res
+
+    def ph_rdm(self, h, v_shard, nvec: int = 1):
+        """SectorHamiltonian.ph_rdm of nvec vectors held as shards: (rho[nvec, 3^norb, DimPh, DimPh], norm2[nvec]), the
+        sums over all ranks, the same bits on every rank.  Collective."""
+        import ctypes as C
+        import numpy as np
+        ncls, dimph = 3 ** (h.norb or self._capi.MAXORB), h.nph + 1
+        rho = np.zeros((nvec, ncls, dimph, dimph), dtype=np.complex128 if h.is_complex else np.float64)
+        nrm = np.zeros(nvec)
+        p, _keep = self._shard_ptr(h, v_shard)
+        self._capi.check(self._capi.lib().edigpu_ph_rdm_sharded(h._h, self._c, p, nvec, rho.ctypes.data_as(C.POINTER(C.c_double)),
+                                                                self._capi.pd(nrm)), "edigpu_ph_rdm_sharded")
+        return rho, nrm
+
     def bench(self, h, warmup: int, steps: int):
         """(ms per sharded Lanczos step, bytes this rank sends per product)."""
         import ctypes as C

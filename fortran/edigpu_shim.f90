@@ -436,6 +436,32 @@ module EDIGPU_SHIM
        integer(c_int32_t), intent(in) :: create(*), iorb(*), ispin(*)
        integer(c_int) :: ierr
      end function edigpu_apply_cops_sharded
+     function edigpu_occ_moments_sharded(h, c, v_shard, nvec, moments, norm2) &
+          bind(C, name="edigpu_occ_moments_sharded") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, c, v_shard
+       integer(c_int), value :: nvec
+       real(c_double), intent(inout) :: moments(*), norm2(*)
+       integer(c_int) :: ierr
+     end function edigpu_occ_moments_sharded
+     function edigpu_apply_occ_sharded(h, c, v_src, v_dst, w_up, w_dw) bind(C, name="edigpu_apply_occ_sharded") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, c, v_src, v_dst
+       real(c_double), intent(in) :: w_up(*), w_dw(*)
+       integer(c_int) :: ierr
+     end function edigpu_apply_occ_sharded
+     function edigpu_apply_xph_sharded(h, c, v_src, v_dst) bind(C, name="edigpu_apply_xph_sharded") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h, c, v_src, v_dst
+       integer(c_int) :: ierr
+     end function edigpu_apply_xph_sharded
+     function edigpu_ph_rdm_sharded(h, c, v_shard, nvec, rho, norm2) bind(C, name="edigpu_ph_rdm_sharded") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, c, v_shard
+       integer(c_int), value :: nvec
+       real(c_double), intent(inout) :: rho(*), norm2(*)
+       integer(c_int) :: ierr
+     end function edigpu_ph_rdm_sharded
      function edigpu_destroy(h) bind(C, name="edigpu_destroy") result(ierr)
        import :: c_ptr, c_int
        type(c_ptr), value :: h
@@ -468,6 +494,8 @@ module EDIGPU_SHIM
   public :: gpu_comm_unique_id, gpu_comm_create, gpu_comm_create_shm, gpu_comm_destroy, gpu_shard_plan
   public :: spMatVec_mpi_gpu_d, spMatVec_mpi_gpu_c, gpu_lanc_tridiag_mpi_d, gpu_lanc_tridiag_mpi_c
   public :: gpu_sp_eigh_mpi_d, gpu_sp_eigh_mpi_c, gpu_apply_op_mpi_d
+  ! observables and the chi_spin / chi_dens / phonon seeds on the shards the MPI solve leaves
+  public :: gpu_occ_moments_mpi, gpu_apply_op_N_mpi, gpu_apply_op_Sz_mpi, gpu_apply_xph_mpi, gpu_ph_rdm_mpi
 
 contains
 
@@ -1201,6 +1229,65 @@ contains
     p2 = c_null_ptr; if (size(vv_shard) > 0) p2 = c_loc(vv_shard)
     call gpu_check(edigpu_apply_cops_sharded(hsrc, hdst, gpu_comm, p1, p2, 1_c_int, coef2, cr, io, sp), "gpu_apply_op_mpi_d")
   end subroutine gpu_apply_op_mpi_d
+
+  !> gpu_occ_moments on shards, on the module's communicator: v_shard = this rank's shard(s) of size(norm2) vectors of
+  !! sector h, consecutive with stride Nloc as gpu_sp_eigh_mpi_* leaves eig_basis (c_loc of it, or a device vector;
+  !! c_null_ptr on a rank without rows).  moments and norm2 hold the sums over all ranks, the same bits on every rank:
+  !! what the loop of ED_OBSERVABLES_NORMAL.f90:120-185 accumulates, without es_return_dvector_mpi's gather.  Collective.
+  subroutine gpu_occ_moments_mpi(h, v_shard, moments, norm2)
+    type(c_ptr), intent(in) :: h, v_shard
+    real(8), intent(inout) :: moments(:, :, :), norm2(:)
+    if (.not. c_associated(gpu_comm)) stop "gpu_occ_moments_mpi: no communicator"
+    if (size(moments, 3) /= size(norm2) .or. size(moments, 1) /= size(moments, 2)) stop "gpu_occ_moments_mpi: shapes"
+    call gpu_check(edigpu_occ_moments_sharded(h, gpu_comm, v_shard, int(size(norm2), c_int), moments, norm2), &
+         "gpu_occ_moments_mpi")
+  end subroutine gpu_occ_moments_mpi
+
+  !> gpu_apply_op_N on this rank's shard (the seed of ED_CHI_DENS.f90:118 without the master rank): host or device
+  !! vectors, v_dst may be v_src; nothing is exchanged.  Returns after the device has finished.
+  subroutine gpu_apply_op_N_mpi(h, v_src_shard, v_dst_shard, iorb)
+    type(c_ptr), intent(in) :: h, v_src_shard, v_dst_shard
+    integer, intent(in) :: iorb
+    real(c_double) :: w(EDIGPU_MAXORB)
+    if (.not. c_associated(gpu_comm)) stop "gpu_apply_op_N_mpi: no communicator"
+    if (iorb < 1 .or. iorb > EDIGPU_MAXORB) stop "gpu_apply_op_N_mpi: orbital out of range"
+    w = 0d0; w(iorb) = 1d0
+    call gpu_check(edigpu_apply_occ_sharded(h, gpu_comm, v_src_shard, v_dst_shard, w, w), "gpu_apply_op_N_mpi")
+  end subroutine gpu_apply_op_N_mpi
+
+  !> gpu_apply_op_Sz on this rank's shard (the seed of ED_CHI_SPIN.f90:121), as gpu_apply_op_N_mpi
+  subroutine gpu_apply_op_Sz_mpi(h, v_src_shard, v_dst_shard, iorb)
+    type(c_ptr), intent(in) :: h, v_src_shard, v_dst_shard
+    integer, intent(in) :: iorb
+    real(c_double) :: wu(EDIGPU_MAXORB), wd(EDIGPU_MAXORB)
+    if (.not. c_associated(gpu_comm)) stop "gpu_apply_op_Sz_mpi: no communicator"
+    if (iorb < 1 .or. iorb > EDIGPU_MAXORB) stop "gpu_apply_op_Sz_mpi: orbital out of range"
+    wu = 0d0; wu(iorb) = 0.5d0
+    wd = -wu
+    call gpu_check(edigpu_apply_occ_sharded(h, gpu_comm, v_src_shard, v_dst_shard, wu, wd), "gpu_apply_op_Sz_mpi")
+  end subroutine gpu_apply_op_Sz_mpi
+
+  !> vvinit = (b + b^+) v_state on this rank's shard of a phonon sector (lanc_build_gf_phonon_main,
+  !! ED_NORMAL/ED_GF_NORMAL.f90:318-333): a rank holds every phonon block of its rows, so nothing is exchanged.
+  !! v_dst_shard must not overlap v_src_shard.
+  subroutine gpu_apply_xph_mpi(h, v_src_shard, v_dst_shard)
+    type(c_ptr), intent(in) :: h, v_src_shard, v_dst_shard
+    if (.not. c_associated(gpu_comm)) stop "gpu_apply_xph_mpi: no communicator"
+    call gpu_check(edigpu_apply_xph_sharded(h, gpu_comm, v_src_shard, v_dst_shard), "gpu_apply_xph_mpi")
+  end subroutine gpu_apply_xph_mpi
+
+  !> The phonon reduced density matrix per impurity occupation class of size(norm2) REAL vectors held as shards (what
+  !! prob_ph, dens_ph, X_ph, X2_ph and prob_distr_ph, ED_OBSERVABLES_NORMAL.f90:182-214, 1235-1298, are linear in):
+  !! rho(n, m, class, k), symmetric
+  !! in n, m, DimPh = Nph + 1 <= 32, classes 1 .. 3**Norb; sums over all ranks, the same bits on every rank.  Complex
+  !! handles return interleaved (re, im): call edigpu_ph_rdm_sharded.  Collective.
+  subroutine gpu_ph_rdm_mpi(h, v_shard, rho, norm2)
+    type(c_ptr), intent(in) :: h, v_shard
+    real(8), intent(inout) :: rho(:, :, :, :), norm2(:)
+    if (.not. c_associated(gpu_comm)) stop "gpu_ph_rdm_mpi: no communicator"
+    if (size(rho, 4) /= size(norm2) .or. size(rho, 1) /= size(rho, 2)) stop "gpu_ph_rdm_mpi: shapes"
+    call gpu_check(edigpu_ph_rdm_sharded(h, gpu_comm, v_shard, int(size(norm2), c_int), rho, norm2), "gpu_ph_rdm_mpi")
+  end subroutine gpu_ph_rdm_mpi
 
   !> delete_Hv_sector_* counterpart (ED_NORMAL/ED_HAMILTONIAN_NORMAL.f90:212-279)
   subroutine gpu_delete_sector()

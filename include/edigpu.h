@@ -824,6 +824,27 @@ int edigpu_lanczos_eigh_sharded(edigpu_handle h, edigpu_comm c, int nitermax, do
 int edigpu_apply_cops_sharded(edigpu_handle src, edigpu_handle dst, edigpu_comm c, const double *v_src_shard,
                               double *v_dst_shard, int nops, const double *coef_re_im, const int32_t *create,
                               const int32_t *iorb, const int32_t *ispin);
+/*
+ * Occupation and phonon observables on shards: edigpu_occ_moments, edigpu_apply_occ, edigpu_apply_xph and edigpu_ph_rdm
+ * on this rank's shard of a vector, without gathering it (the -D_MPI host otherwise collects every state on one rank:
+ * es_return_dvector_mpi, ED_EIGENSPACE.f90:723-793).  All four operators are local to a row and to its phonon blocks.
+ * Handles as for edigpu_apply_sharded_* (normal mode: the whole sector or the rank's down-row shard, _CMPLX_NORMAL its
+ * whole handle; superc / nonsu2: the rank's row shard, stored or on the fly).  v_*_shard: this rank's nloc elements in
+ * the layout of the sharded product (phonon sectors: block after block of the rank's rows), interleaved (re, im) on
+ * complex handles; nvec > 1: consecutive shards with stride nloc, as edigpu_lanczos_eigh_multi_sharded writes them.  Host
+ * or device memory; a device pointer is read and written in place.  A rank that owns no row may pass NULL vectors.
+ * occ_moments / ph_rdm are collective: the results have the shapes of the single-GPU entries, hold the sums over all
+ * ranks and are bit-identical on every rank and from call to call.  apply_occ (v_dst may be v_src) and apply_xph (no
+ * overlap) exchange nothing: `c` only gives the geometry.  All four return after the device has finished.  The
+ * impurity density matrix is not among them: a bath word's run of down rows can straddle two ranks.
+ */
+int edigpu_occ_moments_sharded(edigpu_handle h, edigpu_comm c, const double *v_shard, int nvec, double *moments_host,
+                               double *norm2_host);
+int edigpu_apply_occ_sharded(edigpu_handle h, edigpu_comm c, const double *v_src_shard, double *v_dst_shard,
+                             const double *w_up, const double *w_dw);
+int edigpu_apply_xph_sharded(edigpu_handle h, edigpu_comm c, const double *v_src_shard, double *v_dst_shard);
+int edigpu_ph_rdm_sharded(edigpu_handle h, edigpu_comm c, const double *v_shard, int nvec, double *rho_host,
+                          double *norm2_host);
 /* bench.py --gpus N: `warmup` + `steps` sharded Lanczos steps on a seeded random vector; wall time per step between
  * two collectives that act as barriers, and the bytes this rank sends per product */
 int edigpu_lanczos_bench_sharded(edigpu_handle h, edigpu_comm c, int warmup, int steps, double *ms_per_step,
