@@ -9,21 +9,39 @@ from oracle import oracle as O
 
 
 def make_models(ed_mode: str, bath_type: str, norb: int, nbath: int, seed: int = 0, jxp: float = 0.25,
-                reference_bath: bool = False, **over):
+                reference_bath: bool = False, spin_split: bool = False, zero_dw=None, **over):
     """Structure-preserving synthetic impurity problem: seeded bath levels
     e~U(-2,2), hybridisations v~U(0.1,0.6), Uloc=2, Ust=1.5, Jh=Jx=Jp=0.25, pair amplitudes
-    d~U(-0.1,0.1) (superc), spin-flip u~U(0,0.3) + Hermitian impHloc (nonsu2), xmu=0, hfmode=T."""
+    d~U(-0.1,0.1) (superc), spin-flip u~U(0,0.3) + Hermitian impHloc (nonsu2), xmu=0, hfmode=T.
+
+    spin_split=True makes the one-body data of the down species its own draw (Nspin=2): e[1], v[1], the
+    spin-diagonal hloc[1,1] (normal mode; no spin mixing, ED_NORMAL/stored/H_local.f90:14) and hb[1,1] /
+    the general bath's v[1].  Those numbers come from a second generator, so the arrays of the default call
+    keep their values.  zero_dw=(a, k) then sets v[1, a, k] = 0: the down species loses one hop."""
+    if spin_split and ed_mode == "superc":
+        raise ValueError("superc refuses Nspin > 1 (ED_SETUP.f90:49)")
+    if zero_dw is not None and not spin_split:
+        raise ValueError("zero_dw needs spin_split=True")
     rng = np.random.default_rng(20260630 + seed)
-    nspin = 2 if ed_mode == "nonsu2" else 1
+    rng2 = np.random.default_rng([20260630 + seed, 2]) if spin_split else None
+    nspin = 2 if ed_mode == "nonsu2" or spin_split else 1
     nfoo = 1 if bath_type == "hybrid" else norb
-    be = rng.uniform(-2, 2, (nspin, nfoo, nbath))
-    bv = rng.uniform(0.1, 0.6, (nspin, norb, nbath))
-    bd = rng.uniform(-0.1, 0.1, (nspin, nfoo, nbath)) if ed_mode == "superc" else None
-    bu = rng.uniform(0.0, 0.3, (nspin, norb, nbath)) if ed_mode == "nonsu2" else None
+    ndraw = 2 if ed_mode == "nonsu2" else 1      # species that rng draws: species 0 keeps the default call's values
+    be = rng.uniform(-2, 2, (ndraw, nfoo, nbath))
+    bv = rng.uniform(0.1, 0.6, (ndraw, norb, nbath))
+    bd = rng.uniform(-0.1, 0.1, (ndraw, nfoo, nbath)) if ed_mode == "superc" else None
+    bu = rng.uniform(0.0, 0.3, (ndraw, norb, nbath)) if ed_mode == "nonsu2" else None
+    if nspin > ndraw:
+        be, bv = np.repeat(be, 2, axis=0), np.repeat(bv, 2, axis=0)
     if nspin == 2:
         # keep the two spin species of e and v equal (SU(2)-symmetric bath), break it only via u
         be[1] = be[0]
         bv[1] = bv[0]
+    if spin_split:
+        be[1] = rng2.uniform(-2, 2, (nfoo, nbath))
+        bv[1] = rng2.uniform(0.1, 0.6, (norb, nbath))
+        if zero_dw is not None:
+            bv[1, zero_dw[0], zero_dw[1]] = 0.0
     hl = np.zeros((nspin, nspin, norb, norb), complex)
     if ed_mode == "nonsu2":
         a = rng.standard_normal((2 * norb, 2 * norb)) + 1j * rng.standard_normal((2 * norb, 2 * norb))
@@ -35,8 +53,11 @@ def make_models(ed_mode: str, bath_type: str, norb: int, nbath: int, seed: int =
         a = rng.standard_normal((norb, norb))
         a = 0.3 * (a + a.T)
         hl[0, 0] = a
+        if spin_split:
+            a = rng2.standard_normal((norb, norb))
+            hl[1, 1] = 0.3 * (a + a.T)
     if bath_type in ("replica", "general"):
-        return _make_replica_models(rng, ed_mode, bath_type, norb, nbath, nspin, hl, jxp, over)
+        return _make_replica_models(rng, ed_mode, bath_type, norb, nbath, nspin, hl, jxp, over, rng2, zero_dw)
     par = dict(ed_mode=ed_mode, bath_type=bath_type, norb=norb, nbath=nbath, nspin=nspin, hfmode=True, xmu=0.0,
                uloc=tuple([2.0] * norb), ust=1.5 if norb > 1 else 0.0, jh=0.25 if norb > 1 else 0.0,
                jx=jxp if norb > 1 else 0.0, jp=jxp if norb > 1 else 0.0)
@@ -61,10 +82,11 @@ def _replica_pair(ed_mode, bath_type, norb, nbath, nspin, hl, hb, v, par):
     return om, pm
 
 
-def _make_replica_models(rng, ed_mode, bath_type, norb, nbath, nspin, hl, jxp, over):
+def _make_replica_models(rng, ed_mode, bath_type, norb, nbath, nspin, hl, jxp, over, rng2=None, zero_dw=None):
     """Seeded replica/general bath: Hermitian per-replica matrices with inter-orbital (and, nonsu2,
-    spin-flip; superc, anomalous) blocks -- the structure build_Hreplica produces from a symmetric basis."""
-    n1 = 2 if ed_mode in ("superc", "nonsu2") else 1
+    spin-flip; superc, anomalous) blocks -- the structure build_Hreplica produces from a symmetric basis.
+    rng2 (spin_split): normal mode gets its own hb[1,1] and, general bath, v[1]; nonsu2 draws both already."""
+    n1 = 2 if ed_mode in ("superc", "nonsu2") or rng2 is not None else 1
     hb = np.zeros((n1, n1, norb, norb, nbath), complex)
     for k in range(nbath):
         a = rng.uniform(-0.4, 0.4, (norb, norb))
@@ -85,12 +107,22 @@ def _make_replica_models(rng, ed_mode, bath_type, norb, nbath, nspin, hl, jxp, o
             hb[1, 1, :, :, k] = b
             hb[0, 1, :, :, k] = f
             hb[1, 0, :, :, k] = f.conj().T
+    if rng2 is not None and ed_mode == "normal":
+        for k in range(nbath):
+            a = rng2.uniform(-0.4, 0.4, (norb, norb))
+            hb[1, 1, :, :, k] = 0.5 * (a + a.T) + np.diag(rng2.uniform(-2, 2, norb))
     if bath_type == "replica":
         v = np.broadcast_to(rng.uniform(0.1, 0.6, nbath), (nspin, norb, nbath)).copy()
+    elif rng2 is not None and ed_mode == "normal":
+        v = np.repeat(rng.uniform(0.1, 0.6, (1, norb, nbath)), 2, axis=0)
     else:
         v = rng.uniform(0.1, 0.6, (nspin, norb, nbath))
         if nspin == 2 and ed_mode != "nonsu2":
             v[1] = v[0]
+    if rng2 is not None and ed_mode == "normal" and bath_type == "general":
+        v[1] = rng2.uniform(0.1, 0.6, (norb, nbath))
+        if zero_dw is not None:
+            v[1, zero_dw[0], zero_dw[1]] = 0.0
     par = dict(ed_mode=ed_mode, bath_type=bath_type, norb=norb, nbath=nbath, nspin=nspin, hfmode=True, xmu=0.0,
                uloc=tuple([2.0] * norb), ust=1.5 if norb > 1 else 0.0, jh=0.25 if norb > 1 else 0.0,
                jx=jxp if norb > 1 else 0.0, jp=jxp if norb > 1 else 0.0)
@@ -140,6 +172,28 @@ def replica_golden_models(inp):
     par = dict(ed_mode=mode, bath_type=bath, norb=norb, nbath=nb, nspin=nspin, hfmode=True, xmu=0.0,
                uloc=tuple(inp["ULOC"]), ust=inp["UST"], jh=inp["JH"], jx=inp["JX"], jp=inp["JP"])
     return _replica_pair(mode, bath, norb, nb, nspin, hl, hb, v, par)
+
+
+def afm_site_models(inp, site):
+    """Site `site` (0, 1) of test/src/INEQ_NORMAL_NORMAL, the antiferromagnet of two inequivalent one-orbital sites with
+    Nspin = 2, as a single-site problem: Hloc = kron(sigma_z, tau_0) over (site, spin) = +1 on both spins of site 1, -1
+    on site 2 (ed_normal_normal_afm2.f90:69-70), the init_dmft_bath start bath with the up levels raised and the down
+    levels lowered by SB_FIELD on site 1, the other way round on site 2 (ed_break_symmetry_bath with sign (-1)^(ip+1),
+    ED_BATH_USER.f90:155-171)."""
+    norb, nbath, sgn = int(inp["NORB"]), int(inp["NBATH"]), (1.0 if site == 0 else -1.0)
+    hl = np.zeros((2, 2, norb, norb), complex)
+    for s in range(2):
+        hl[s, s] = sgn * np.eye(norb)
+    par = dict(ed_mode=inp["ED_MODE"], bath_type=inp["BATH_TYPE"], norb=norb, nbath=nbath, nspin=int(inp["NSPIN"]),
+               hfmode=inp["HFMODE"], xmu=inp["XMU"], uloc=tuple(inp["ULOC"]), ust=inp["UST"], jh=inp["JH"],
+               jx=inp["JX"], jp=inp["JP"])
+    om = O.Model(hloc=hl, ed_hw_bath=inp["ED_HW_BATH"], **par)
+    O.init_dmft_bath(om)
+    om.be[0] += sgn * inp["SB_FIELD"]
+    om.be[1] -= sgn * inp["SB_FIELD"]
+    pm = ImpurityModel(hloc=hl, be=om.be.copy(), bv=om.bv.copy(),
+                       **{k: (np.asarray(v) if k == "uloc" else v) for k, v in par.items()})
+    return om, pm
 
 
 def rel_err(a, b):

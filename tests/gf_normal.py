@@ -42,17 +42,36 @@ def apply_c_up(h_from, h_to, vec, iorb, create):
     return out
 
 
-def sigma_momenta_normal(om, tridiag, beta=1000.0, lmats=4096, ngfiter=200, gs_threshold=1e-9, nmom=4):
-    """-> array [norb, nmom] as Sigma_momenta.check stores it (orbital-major)."""
+def apply_c_dw(h_from, h_to, vec, iorb, create):
+    """The down twin of apply_c_up: |out> = c^(+)_{iorb,dw} |vec>; the sign is taken inside the down word alone, as
+    apply_op_C does (ED_SECTOR.f90:516-527: c(ipos, iud(ispin), r, sgn) on the species' own word)."""
+    out = np.zeros(h_to.dim)
+    rank_to = {int(s): i for i, s in enumerate(h_to.mapdw)}
+    bit = 1 << iorb
+    occ = (h_from.mapdw & bit) != 0
+    sel = np.nonzero(~occ if create else occ)[0]
+    sgn = 1.0 - 2.0 * (_popcount_below(h_from.mapdw[sel], iorb) & 1)
+    tgt = np.array([rank_to[int(s) ^ bit] for s in h_from.mapdw[sel]], dtype=np.int64)
+    v2 = vec.reshape(h_from.dimdw, h_from.dimup)
+    o2 = out.reshape(h_to.dimdw, h_to.dimup)
+    o2[tgt, :] = v2[sel, :] * sgn[:, None]
+    return out
+
+
+def sigma_momenta_normal(om, tridiag, beta=1000.0, lmats=4096, ngfiter=200, gs_threshold=1e-9, nmom=4, states=None):
+    """-> array [norb, nmom] as Sigma_momenta.check stores it (orbital-major): the spin-up component (Nspin = 2: the
+    up species' G and G0, from be[0], bv[0], hloc[0,0]).  The ground states are found by a dense scan of all (nup, ndw)
+    sectors, or handed in as states = [((nup, ndw), HNormal, energy, vector)] by a caller that has them already."""
     assert om.ed_mode == "normal" and om.bath_type in ("normal", "hybrid", "replica", "general")
     secs = []
-    for sec in O.sectors(om):
+    for sec in O.sectors(om) if states is None else ():
         h = O.HNormal(om, *sec)
         if h.dim:
             w, v = np.linalg.eigh(h.dense())
             secs.append((sec, h, w, v))
-    e0 = min(w[0] for _, _, w, _ in secs)
-    states = [(sec, h, w[k], v[:, k]) for sec, h, w, v in secs for k in range(len(w)) if w[k] - e0 <= gs_threshold]
+    if states is None:
+        e0 = min(w[0] for _, _, w, _ in secs)
+        states = [(sec, h, w[k], v[:, k]) for sec, h, w, v in secs for k in range(len(w)) if w[k] - e0 <= gs_threshold]
     zeta = float(len(states))
     wm = np.pi / beta * (2.0 * np.arange(1, lmats + 1) - 1.0)
     z = 1j * wm

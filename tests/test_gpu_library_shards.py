@@ -40,9 +40,9 @@ CASES = [
 NPH = 3
 
 
-def _reference(mode, bath, norb, nbath, sector, seed=31, cmplx=False, phonon=False):
+def _reference(mode, bath, norb, nbath, sector, seed=31, cmplx=False, phonon=False, spin_split=False):
     from oracle import oracle as O
-    om, pm = make_models(mode, bath, norb, nbath, seed=seed)
+    om, pm = make_models(mode, bath, norb, nbath, seed=seed, spin_split=spin_split)
     if phonon:
         for m in (om, pm):
             m.nph, m.w0_ph, m.a_ph, m.g_ph = NPH, 0.8, 0.15, np.diag([0.4, -0.3][:norb])
@@ -75,8 +75,9 @@ def _rank_main(rank, world, name, case, q):
         from edipack_amd import capi
         from edipack_amd.sharding import LibraryComm, library_sharded_sector
         capi.init(0)
-        mode, bath, norb, nbath, sector, direct, exchange = case
-        ho, pm, v = _reference(mode, bath, norb, nbath, sector, cmplx=exchange == "cmplx", phonon=exchange == "phonon")
+        mode, bath, norb, nbath, sector, direct, exchange = case[:7]
+        ho, pm, v = _reference(mode, bath, norb, nbath, sector, cmplx=exchange == "cmplx", phonon=exchange == "phonon",
+                               spin_split=len(case) > 7 and case[7])
         comm = LibraryComm(rank, world, shm_name=name, slot_bytes=1 << 22)
         block = exchange.startswith("block")
         if block:      # small sectors get the impurity-block image + local-block tables on request only
@@ -118,6 +119,37 @@ def test_library_shards_share_one_gpu(gpu, world, case):
         p.join(timeout=60)
     for r in res:
         assert r[8] is None, r[8]
+    got = np.zeros_like(ref)
+    for rank, ix, _, hv, a, b, nd, n2, _ in res:
+        got[ix] = hv
+        assert nd == 20 and abs(n2 - np.real(np.vdot(v, v))) < 1e-10 * abs(n2)
+        assert rel_err(a, a_ref) < 1e-10 and rel_err(b, b_ref) < 1e-10      # every rank holds the same coefficients
+    assert rel_err(got, ref) < 1e-12
+
+
+# Nspin = 2 with the down species' one-body data drawn on its own (make_models(..., spin_split=True)): the case tuple's
+# eighth field
+SPLIT_CASES = [
+    ("normal", "normal", 2, 3, (4, 4), False, "auto", True),
+    ("normal", "normal", 2, 3, (4, 4), False, "allgather", True),
+    ("normal", "normal", 2, 3, (4, 4), False, "block", True),
+    ("normal", "hybrid", 3, 5, (4, 3), False, "block", True),
+    ("nonsu2", "hybrid", 2, 3, 5, True, "auto", True),
+]
+
+
+@pytest.mark.parametrize("case", SPLIT_CASES, ids=[f"{c[0]}-{c[1]}-{c[6]}{'-direct' if c[5] else ''}" for c in SPLIT_CASES])
+@pytest.mark.parametrize("world", [2, 3])
+def test_library_shards_spin_split(gpu, world, case):
+    """test_library_shards_share_one_gpu's checks (product, 20 coefficients on every rank, the exchange kind asserted
+    inside the ranks) on models whose two spin species differ; nup == ndw in the normal-mode sectors."""
+    mode, bath, norb, nbath, sector, direct, exchange, _ = case
+    ho, pm, v = _reference(mode, bath, norb, nbath, sector, spin_split=True)
+    assert pm.nspin == 2 and not np.array_equal(pm.be[1], pm.be[0]) and not np.array_equal(pm.bv[1], pm.bv[0])
+    ref = ho.matvec(v)
+    a_ref, b_ref, _ = ho.lanc_tridiag(v, 20)
+    name = f"edigpu_split_{os.getpid()}_{world}_{abs(hash(case)) % 100000}"
+    res = _run_world(_rank_main, world, (name, case))
     got = np.zeros_like(ref)
     for rank, ix, _, hv, a, b, nd, n2, _ in res:
         got[ix] = hv

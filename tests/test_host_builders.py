@@ -60,6 +60,13 @@ CASES = [
                                    spin_field=np.array([[0, 0, 0.1], [0, 0, 0.2]]))),
     ("normal", 1, 4, (2, 3), dict(sundry=[(0.6, (0, 0), (0, 1), (0, 1), (0, 0))])),
     ("hybrid", 3, 3, (3, 3), dict()),
+    # Nspin = 2: the down species has its own levels, amplitudes, impHloc block and replica matrices
+    ("normal", 2, 2, (3, 2), dict(spin_split=True)),
+    ("hybrid", 3, 3, (3, 3), dict(spin_split=True)),
+    ("normal", 1, 4, (2, 3), dict(spin_split=True)),
+    ("replica", 2, 2, (3, 3), dict(spin_split=True)),
+    ("general", 2, 3, (4, 3), dict(spin_split=True)),
+    ("normal", 2, 2, (2, 2), dict(spin_split=True, zero_dw=(1, 0))),
 ]
 
 
@@ -76,6 +83,22 @@ def test_normal_builder_images_equal_oracle(shim, bath, norb, nbath, sec, extra)
         assert np.abs(ref - O.HNormal(om0, *sec).dense()).max() > 1e-3   # the switch does something
     for form in (0, 1):
         got = _host_dense(shim, pm, sec[0], sec[1], form, h.dim)
+        assert np.abs(got - ref).max() < 1e-13, (form, np.abs(got - ref).max())
+
+
+@pytest.mark.parametrize("site", [0, 1])
+def test_afm_fixture_model_images_equal_oracle(shim, site):
+    """The single-site problems of test/src/INEQ_NORMAL_NORMAL (Nspin = 2, bath levels split by SB_FIELD): the host images
+    of a small sector with nup == ndw against the oracle, whose ground state tests/test_oracle_golden.py pins."""
+    import json
+    from tests.common import afm_site_models
+    inp = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_checks.json")))["INEQ_NORMAL_NORMAL"]["input"]
+    om, pm = afm_site_models(inp, site)
+    h = O.HNormal(om, 2, 2)
+    ref = h.dense()
+    assert np.abs(ref - ref.T).max() < 1e-14
+    for form in (0, 1):
+        got = _host_dense(shim, pm, 2, 2, form, h.dim)
         assert np.abs(got - ref).max() < 1e-13, (form, np.abs(got - ref).max())
 
 
@@ -105,6 +128,8 @@ FLAT_CASES = [
     ("nonsu2", "hybrid", 3, 1, 4, dict(spin_field=np.array([[0.3, 0.1, 0.2], [0.0, -0.25, -0.15], [0.05, 0.0, 0.0]]))),
     ("nonsu2", "replica", 2, 2, 5, dict(exc_field=np.array([0.1, 0.2, 0.0, -0.2]), sundry=SUNDRY2 + SUNDRY_FLIP,
                                         spin_field=np.array([[0.0, 0.4, 0.1], [0.2, 0.0, 0.2]]))),
+    ("nonsu2", "normal", 2, 2, 5, dict(spin_split=True)),        # e, v of the down species drawn, not copied
+    ("nonsu2", "hybrid", 2, 3, 4, dict(spin_split=True)),
 ]
 
 

@@ -54,6 +54,12 @@ CASES = [
     ("normal", 2, 2, (3, 2), 480, dict(sundry=SUNDRY2)),
     ("hybrid", 3, 3, (2, 3), 6, dict(exc_field=np.array([0.12, 0.5, 0.5, 0.07]))),
     ("normal", 2, 3, (4, 3), 480, dict(spin_field=np.array([[0.3, 0.1, 0.2], [0.0, 0.0, -0.15]]))),
+    # Nspin = 2: the image of the down side holds numbers of its own
+    ("normal", 2, 3, (4, 4), 16, dict(spin_split=True)),
+    ("hybrid", 3, 5, (4, 4), 24, dict(spin_split=True)),
+    ("hybrid", 3, 5, (1, 7), 480, dict(spin_split=True)),
+    ("normal", 1, 7, (4, 3), 480, dict(spin_split=True)),
+    ("normal", 2, 3, (4, 4), 16, dict(spin_split=True, zero_dw=(1, 2))),
 ]
 
 
@@ -114,6 +120,17 @@ def test_bath_bath_hops_of_replica_baths(shim, bath, norb, nbath, sec, rows):
     rc = shim.host_ib_check2(C.byref(m), sec[0], sec[1], rows, -1, info2, C.byref(d2))
     if norb > 1:
         assert rc == 1 and "bath-bath hops in a row staged in halves" in shim.host_ib_error().decode()
+
+
+@pytest.mark.parametrize("bath,norb,nbath,sec,rows", [("replica", 2, 2, (3, 3), 480), ("general", 3, 2, (5, 4), 480),
+                                                      ("replica", 2, 3, (4, 3), 12)])
+def test_bath_bath_hops_spin_split(shim, bath, norb, nbath, sec, rows):
+    """Nspin = 2: the replica matrices hb[1, 1] and (general) the amplitudes v[1] of the down species drawn on their own."""
+    _, pm = make_models("normal", bath, norb, nbath, seed=33, spin_split=True)
+    assert not np.array_equal(np.asarray(pm.hb)[1, 1], np.asarray(pm.hb)[0, 0])
+    rc, info, diff, msg = _check(shim, pm, sec[0], sec[1], rows)
+    assert rc == 0, msg
+    assert info[0] == 1 and diff < 1e-13, (info, diff)
 
 
 def test_chunks_follow_the_row_budget(shim):

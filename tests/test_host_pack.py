@@ -204,8 +204,8 @@ def test_ell16_pads_an_odd_width_with_a_dead_half_word(shim):
     assert np.array_equal(decode_ell(img, True), csr_triples(a))
 
 
-def model_sector(lib, norb, nbath, nup, ndw, bath="normal", seed=11):
-    _, pm = make_models("normal", bath, norb, nbath, seed=seed)
+def model_sector(lib, norb, nbath, nup, ndw, bath="normal", seed=11, **extra):
+    _, pm = make_models("normal", bath, norb, nbath, seed=seed, **extra)
     m = pm.to_c()
     dims = np.zeros(5, I64)
     assert lib.hp_build_normal(C.addressof(m), nup, ndw, ptr(dims)) == 0, lib.hp_error().decode()
@@ -224,6 +224,24 @@ def model_sector(lib, norb, nbath, nup, ndw, bath="normal", seed=11):
 def sector44(shim):
     """norb = 2, nbath = 3, (4, 4): Jx = Jp != 0, so the factored Hnd has terms"""
     return model_sector(shim, 2, 3, 4, 4)
+
+
+@pytest.mark.parametrize("bath,norb,nbath,extra", [("normal", 2, 3, {}), ("hybrid", 3, 2, {}),
+                                                   ("normal", 2, 3, dict(zero_dw=(1, 2)))])
+def test_ell_images_of_a_spin_split_sector(shim, bath, norb, nbath, extra):
+    """Nspin = 2, nup == ndw: H up and H dw have the same pattern (but for a zeroed down amplitude) and different
+    numbers; each side's image decodes to its own matrix."""
+    n = (norb * (nbath + 1)) // 2 if bath == "normal" else (norb + nbath) // 2
+    up, dw = model_sector(shim, norb, nbath, n, n, bath=bath, spin_split=True, **extra)[:2]
+    assert up.nrow == dw.nrow
+    tu, td = csr_triples(up), csr_triples(dw)
+    assert (tu.shape != td.shape) == bool(extra) and not np.array_equal(tu, td)
+    for a, want in ((up, tu), (dw, td)):
+        for lds in (False, True):
+            img = encode_ell(shim, a, lds)
+            assert img["typed"] == 1
+            assert np.array_equal(decode_ell(img, lds), want)
+        check_ell16(img)
 
 
 @pytest.mark.parametrize("norb,nbath,nup", [(1, 13, 7), (2, 3, 4)])

@@ -60,6 +60,14 @@ CASES = [
     ("normal", 2, 2, (3, 2), 1, 480, dict(sundry=SUNDRY2)),
     ("hybrid", 3, 4, (2, 3), 2, 12, dict(exc_field=np.array([0.12, 0.5, 0.5, 0.07]))),
     ("normal", 2, 3, (4, 3), 2, 480, dict(spin_field=np.array([[0.3, 0.1, 0.2], [0.0, 0.0, -0.15]]))),
+    # Nspin = 2: the tables of the down side hold numbers of their own
+    ("normal", 2, 3, (4, 4), 2, 16, dict(spin_split=True)),
+    ("hybrid", 3, 5, (4, 4), 2, 24, dict(spin_split=True)),
+    ("hybrid", 3, 5, (1, 7), 2, 480, dict(spin_split=True)),
+    ("normal", 1, 7, (4, 3), 4, 480, dict(spin_split=True)),
+    # one walked level of the down species without a hop (v = 0): its korb mask differs from the up species'; a level
+    # with no orbital is still "at most one orbital per level", so the per-orbital walk stays admitted (info[4] == 1)
+    ("normal", 2, 3, (4, 4), 2, 16, dict(spin_split=True, zero_dw=(1, 2))),
 ]
 
 
@@ -179,3 +187,13 @@ def test_sharded_local_block_product_matches_explicit_arrays(shim, bath, norb, n
     assert info[0] == 1 and diff < 1e-13, (info, diff)
     assert tuple(info[1:3]) + tuple(info[4:6]) == geom, info
     assert info[6] > 0                                          # Hnd terms inside the panels
+
+
+def test_sharded_local_block_product_spin_split(shim):
+    """The same emulation on a model whose down species has its own levels and amplitudes (Nspin = 2), world 3."""
+    _, pm = make_models("normal", "normal", 2, 3, seed=41, spin_split=True)
+    assert pm.nspin == 2 and not np.array_equal(pm.bv[1], pm.bv[0])
+    rc, info, diff, msg = _check_shard(shim, pm, 4, 4, 3, 24, 3)
+    assert rc == 0, msg
+    assert info[0] == 1 and diff < 1e-13, (info, diff)
+    assert tuple(info[1:3]) + tuple(info[4:6]) == (24, 2, 0, 0) and info[6] > 0

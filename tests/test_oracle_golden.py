@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from tests.common import make_models, rel_err, replica_golden_models
+from tests.common import afm_site_models, make_models, rel_err, replica_golden_models
 
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_checks.json")))
 
@@ -543,3 +543,64 @@ def test_oracle_reproduces_phisc_magx(name):
         assert np.max(np.abs(phi.real - np.array(g["phisc"]))) < tol and np.max(np.abs(phi.imag)) < tol
     if "magX" in g:
         assert np.max(np.abs(ob.magx(om, states, cops, hsector) - np.array(g["magX"]))) < tol
+
+
+# ---------------------------------------------------------------------------------------------------------
+# INEQ_NORMAL_NORMAL: normal mode with Nspin = 2 (an antiferromagnet of two sites whose baths are split by SB_FIELD), the
+# reference's only pin of spin-dependent one-body data in normal mode
+# ---------------------------------------------------------------------------------------------------------
+def _sparse_eigvec(sec, h):
+    """Dense LAPACK on the small sectors, implicitly restarted Lanczos on the oracle's product for the others (the twin
+    sectors are not degenerate here: all (nup, ndw) are scanned)."""
+    if h.dim <= 1200:
+        return np.linalg.eigh(h.dense())
+    import scipy.sparse.linalg as sla
+    w, v = sla.eigsh(sla.LinearOperator((h.dim, h.dim), matvec=h.matvec, dtype=float), k=3, which="SA", tol=1e-14, ncv=40)
+    order = np.argsort(w)
+    return w[order], v[:, order]
+
+
+@pytest.fixture(scope="module")
+def afm_ground_states():
+    from tests import observables as ob
+    out = []
+    for site in range(2):
+        om, _ = afm_site_models(GOLD["INEQ_NORMAL_NORMAL"]["input"], site)
+        e0, states = ob.ground_manifold(om, eigvec=_sparse_eigvec)
+        out.append((om, e0, states))
+    return out
+
+
+@pytest.mark.parametrize("site", [0, 1])
+def test_oracle_reproduces_afm_fixture(afm_ground_states, site):
+    """dens, docc, energy, doubles of either site at the reference's own tolerance (absolute 1e-9, ASSERTING.f90:74-80).
+    The ground state is in (4, 4) and polarised: a builder that read the up species' levels for the down species would
+    give the unpolarised state of another Hamiltonian."""
+    from tests import observables as ob
+    g = GOLD["INEQ_NORMAL_NORMAL"]
+    om, e0, states = afm_ground_states[site]
+    assert [s[0] for s in states] == [(4, 4)]
+    dens, docc = ob.dens_docc(om, states)
+    up, dw = ob._densities(om, states)
+    assert abs(up[0] - dw[0]) > 0.1                       # magnetised
+    doubles, energy, _ = ob.doubles_energy_imp(om, states, e0)
+    assert abs(dens[0] - g["dens"][site]) < 1e-9 and abs(docc[0] - g["docc"][site]) < 1e-9
+    assert np.max(np.abs(energy - np.array(g["energy"]).reshape(2, 4)[site])) < 1e-9
+    assert np.max(np.abs(doubles - np.array(g["doubles"]).reshape(2, 4)[site])) < 1e-9
+
+
+@pytest.mark.parametrize("site", [0, 1])
+def test_oracle_tridiag_reproduces_afm_sigma_momenta(afm_ground_states, site):
+    """Sigma_momenta.check of the antiferromagnet: the spin-up self-energy (Smats(ilat,1,1,1,1,:)) of either site."""
+    from tests.gf_normal import sigma_momenta_normal
+    g = GOLD["INEQ_NORMAL_NORMAL"]
+    om, e0, states = afm_ground_states[site]
+
+    def tridiag(sec, v, nl):
+        a, b, _ = O.HNormal(om, *sec).lanc_tridiag(v.copy(), nl)
+        return a, b
+
+    m = sigma_momenta_normal(om, tridiag, beta=g["input"]["BETA"], ngfiter=int(g["input"]["LANC_NGFITER"]),
+                             states=[(sec, h, e0, v) for sec, h, v in states])
+    gold = np.array(g["Sigma_momenta"]).reshape(2, 4)[site]
+    assert np.max(np.abs(m[0] - gold) / np.abs(gold)) < 1e-10
