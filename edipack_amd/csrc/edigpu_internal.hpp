@@ -216,6 +216,25 @@ struct RdmDev;
 void free_rdm(edigpu_sector* s);
 // device bytes of those tables (made lazily: the sector cache adds them like occ_table_bytes)
 int64_t rdm_table_bytes(const edigpu_sector* s);
+// The same on the down rows [first, first + count) of the sector, one of `world` ranges of edigpu_shard_plan
+// (edigpu_sector::rdm_shard; host_rdm.hpp RdmShardPlan), kept like the occupation tables' shard view and built on every
+// rank, rows or not.  A run of down rows a rank boundary cuts belongs to the rank it starts on: every rank sends its first
+// H rows (rdm_shard_pack: nvec x nblk x H x DimUp x cw doubles, zero-padded), and rdm_shard_enqueue fills the owner's slab
+// (nvec x nblk x tail_ld x DimUp x cw doubles) from the gathered halos, runs the tiles kernel on the shard in place and
+// on the slab, and leaves the nvec x ntri x cw packed sums of this rank in *tri_dev, all on the handle's stream.
+struct RdmShardDev;
+struct RdmShardInfo {
+  int H = 0, tail_ld = 0, cw = 1;
+  int64_t ntri = 0;
+};
+// the refusals that need no communicator: ed_total_ud=F, hand-over handle, superc / nonsu2, norb
+int rdm_shard_refuse(const edigpu_sector* s, const std::string& who);
+int rdm_shard_prepare(edigpu_sector* s, int64_t first, int64_t count, int world, const std::string& who, RdmShardInfo* info);
+int rdm_shard_pack(edigpu_sector* s, const double* v_dev, int nvec, double* send_dev);
+int rdm_shard_enqueue(edigpu_sector* s, const double* v_dev, int nvec, const double* halos_dev, double* slab_dev,
+                      const double** tri_dev);
+// the summed packed triangles -> nvec dense matrices and traces, as edigpu_imp_rdm returns them
+void rdm_shard_expand(const edigpu_sector* s, const double* tri, int nvec, double* rdm_host, double* norm2_host);
 
 // The same of edigpu_imp_rdm_flat on a library-built whole superc / nonsu2 sector (host_rdm_flat.hpp; kernels_rdm_flat.hip).
 struct RdmFlatDev;
@@ -366,6 +385,7 @@ struct edigpu_sector {
   edigpu::OccDev* occ_shard = nullptr;  // the view of a rank's rows (edigpu_*_sharded)
   // ---- impurity reduced density matrix (lazily built) ----
   edigpu::RdmDev* rdm = nullptr;
+  edigpu::RdmShardDev* rdm_shard = nullptr;  // the view of a rank's rows (edigpu_imp_rdm_sharded)
   edigpu::RdmFlatDev* rdm_flat = nullptr;
   // ---- phonon displacement seed and phonon density matrix (lazily built) ----
   edigpu::PhDev* ph = nullptr;

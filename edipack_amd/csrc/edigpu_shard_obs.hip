@@ -1,5 +1,6 @@
-// edigpu_shard_obs.hip -- occupation and phonon observables on sharded vectors (include/edigpu.h:
-// edigpu_occ_moments_sharded, edigpu_apply_occ_sharded, edigpu_apply_xph_sharded, edigpu_ph_rdm_sharded).
+// edigpu_shard_obs.hip -- occupation and phonon observables and the impurity density matrix on sharded vectors
+// (include/edigpu.h: edigpu_occ_moments_sharded, edigpu_apply_occ_sharded, edigpu_apply_xph_sharded,
+// edigpu_ph_rdm_sharded, edigpu_imp_rdm_sharded).
 //
 // The four operators are local to a row and to the row's phonon blocks, and a rank holds all phonon blocks of its rows:
 // the kernels of kernels_occ.hip / kernels_ph.hip run unchanged on tables made for the rank's rows (the shard views of
@@ -7,6 +8,8 @@
 // the fixed-order final kernels, one all-reduce adds the packed sums of the ranks (in rank order on every rank), and the
 // host expansions of the single-GPU entries follow: no floating-point atomics, the same bits on every rank and call.
 // Takes the place of gathering every state on one rank (es_return_dvector_mpi, ED_EIGENSPACE.f90:723-793).
+// The impurity density matrix is not local to a row -- it needs the whole run of down rows of a bath word -- and
+// exchanges the few rows a rank boundary cuts off first (at the end of this file).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -199,6 +202,46 @@ int edigpu_ph_rdm_sharded(edigpu_handle s, edigpu_comm c, const double* v_shard,
       tr += ph_expand_slots(sums.data() + ((size_t)k * ncls + cl) * nslot, dimph, cw, rho_host + ((size_t)k * ncls + cl) * nmat);
     if (norm2_host) norm2_host[k] = tr;
   }
+  return 0;
+}
+
+// rho_imp = Tr_bath |v><v| needs the whole run of down rows of a bath word, and a rank boundary can cut one: every rank
+// sends its first H rows (those of a run that starts on an earlier rank), one all-gather, and the rank a cut run starts on
+// completes it in a slab (edigpu_internal.hpp rdm_shard_*; host_rdm.hpp RdmShardPlan).  H is the same on every rank, so
+// the all-gather is issued by all or by none.
+int edigpu_imp_rdm_sharded(edigpu_handle s, edigpu_comm c, const double* v_shard, int nvec, double* rdm_host, double* norm2_host) {
+  const std::string who = "edigpu_imp_rdm_sharded";
+  if (!s || !c || !rdm_host || nvec <= 0) {
+    set_error(who + (!s || !c || !rdm_host ? ": NULL argument" : ": nvec must be positive"));
+    return 1;
+  }
+  if (rdm_shard_refuse(s, who)) return 1;
+  ShardGeom g;
+  if (shard_geometry(real_image(s), c, g)) return 1;
+  if (g.count > 0 && !v_shard) {
+    set_error(who + ": NULL argument");
+    return 1;
+  }
+  EDIGPU_HIP(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  RdmShardInfo ri;
+  if (rdm_shard_prepare(s, g.first, g.count, c->world, who, &ri)) return 1;
+  const int nblk = s->nph + 1;
+  const int64_t rowlen = s->dim_up * ri.cw, len = g.count * rowlen * nblk;
+  const double* vd = nullptr;
+  if (g.count > 0 && stage_in(c, v_shard, len * nvec, 0, len * nvec, st, &vd)) return 1;
+  ShardWorkspace& w = c->ws;
+  if (ri.H > 0) {
+    const int64_t n = (int64_t)nvec * nblk * ri.H * rowlen;
+    if (dev_grow(&w.halo, &w.halo_cap, n) || dev_grow(&w.halos, &w.halos_cap, n * c->world)) return 1;
+    if (rdm_shard_pack(s, vd, nvec, w.halo) || comm_all_gather(c, w.halo, w.halos, (size_t)n, st)) return 1;
+  }
+  if (dev_grow(&w.slab, &w.slab_cap, (int64_t)nvec * nblk * ri.tail_ld * rowlen)) return 1;
+  const double* mine = nullptr;
+  if (rdm_shard_enqueue(s, vd, nvec, w.halos, w.slab, &mine)) return 1;
+  std::vector<double> tri;
+  if (reduce_to_host(c, mine, (size_t)nvec * ri.ntri * ri.cw, st, tri)) return 1;
+  rdm_shard_expand(s, tri.data(), nvec, rdm_host, norm2_host);
   return 0;
 }
 

@@ -218,12 +218,13 @@ void rdm_plan(const RdmRanks& rk, const RdmLayout& l, const RdmRuns& up, const R
   }
 }
 
-std::string rdm_plan_emulate(const RdmPlan& p, int64_t ntri, int64_t nel, int64_t dim_up, int64_t dim_dw, const double* v,
-                             int cw, double* tri) {
+// rdm_tiles_kernel over the work list of p: the workgroups' sums into partial (written: one flag per entry)
+static std::string emulate_tiles(const RdmPlan& p, int64_t ntri, int64_t nel, int64_t dim_up, int64_t dim_dw, const double* v,
+                                 int cw, std::vector<double>& partial, std::vector<char>& written) {
   const int64_t stage_n = (int64_t)p.ld_max * p.stride, acc_n = (int64_t)p.ept_max * kRdmThreads;
-  std::vector<double> stage((size_t)stage_n * cw), acc((size_t)acc_n * cw), partial((size_t)p.partial_entries * cw, 0.0);
+  const int64_t partial_entries = (int64_t)written.size();
+  std::vector<double> stage((size_t)stage_n * cw), acc((size_t)acc_n * cw);
   std::vector<uint16_t> rel((size_t)p.rel_max);
-  std::vector<char> written((size_t)p.partial_entries, 0);
   if ((int64_t)p.ent.size() != ntri) return "ent does not have ntri entries";
   for (const RdmWork& w : p.work) {
     const int nrel = w.kb[kRdmMaxOrb + 1];
@@ -268,19 +269,25 @@ std::string rdm_plan_emulate(const RdmPlan& p, int64_t ntri, int64_t nel, int64_
     for (int t = 0; t < kRdmThreads; t++)
       for (int e = w.e0 + t, k = 0; e < w.e1; e += kRdmThreads, k++) {
         const int64_t o = w.pofs + (e - w.e0);
-        if (o < 0 || o >= p.partial_entries) return "partial sum out of range";
+        if (o < 0 || o >= partial_entries) return "partial sum out of range";
         if (written[(size_t)o]) return "a partial sum is written twice";
         written[(size_t)o] = 1;
         for (int c = 0; c < cw; c++) partial[(size_t)o * cw + c] = acc[((size_t)k * kRdmThreads + t) * cw + c];
       }
   }
+  return "";
+}
+
+// rdm_final_kernel over the groups (after the memset of the packed result)
+static std::string emulate_final(const std::vector<RdmGroup>& groups, int64_t ntri, int cw, const std::vector<double>& partial,
+                                 const std::vector<char>& written, double* tri) {
   for (char c : written)
     if (!c) return "a partial sum is never written";
   std::fill(tri, tri + ntri * cw, 0.0);
   std::vector<char> done((size_t)ntri, 0);
-  for (const RdmGroup& g : p.groups) {
+  for (const RdmGroup& g : groups) {
     const int64_t E = g.e1 - g.e0;
-    if (g.pbase + (int64_t)g.nwg * E > p.partial_entries) return "group out of range";
+    if (g.e0 < 0 || g.e1 > ntri || g.pbase < 0 || g.pbase + (int64_t)g.nwg * E > (int64_t)written.size()) return "group out of range";
     for (int64_t e = 0; e < E; e++) {
       if (done[(size_t)(g.e0 + e)]) return "two groups write one entry";
       done[(size_t)(g.e0 + e)] = 1;
@@ -292,6 +299,151 @@ std::string rdm_plan_emulate(const RdmPlan& p, int64_t ntri, int64_t nel, int64_
     }
   }
   return "";
+}
+
+std::string rdm_plan_emulate(const RdmPlan& p, int64_t ntri, int64_t nel, int64_t dim_up, int64_t dim_dw, const double* v,
+                             int cw, double* tri) {
+  std::vector<double> partial((size_t)p.partial_entries * cw, 0.0);
+  std::vector<char> written((size_t)p.partial_entries, 0);
+  const std::string why = emulate_tiles(p, ntri, nel, dim_up, dim_dw, v, cw, partial, written);
+  return why.empty() ? emulate_final(p.groups, ntri, cw, partial, written, tri) : why;
+}
+
+// rows from `first` up to the first run start in [first, first + count) (count when there is none); *run = that run
+static int32_t shard_head(const RdmRuns& dw, int64_t first, int64_t count, size_t* run) {
+  const size_t j = (size_t)(std::lower_bound(dw.start.begin(), dw.start.end() - 1, (int32_t)first) - dw.start.begin());
+  if (run) *run = j;
+  if (j >= dw.k.size() || dw.start[j] >= first + count) return (int32_t)count;
+  return (int32_t)(dw.start[j] - first);
+}
+
+std::string rdm_shard_plan(const RdmRanks& rk, const RdmLayout& l, const RdmRuns& up, const RdmRuns& dw, int64_t dim_up,
+                           int64_t dim_dw, int nblk, int cw, int target_wgs, int world, int64_t first, int64_t count,
+                           RdmShardPlan& p) {
+  p = RdmShardPlan();
+  if (world < 1 || first < 0 || count < 0) return "bad range";
+  if (dw.start.empty() || dw.start.back() != dim_dw) return "the down runs do not have the sector's rows";
+  p.world = world;
+  p.q = (dim_dw + world - 1) / world;
+  p.first = std::min(first, dim_dw);
+  p.count = std::max<int64_t>(0, std::min(count, dim_dw - p.first));
+  p.rank = -1;
+  if (p.count > 0) {
+    if (p.first % p.q != 0 || p.count != std::min(p.q, dim_dw - p.first)) return "the rows are not a rank's range of edigpu_shard_plan";
+    p.rank = (int)(p.first / p.q);
+  }
+  auto range = [&](int r, int64_t& f, int64_t& c) {
+    f = std::min<int64_t>((int64_t)r * p.q, dim_dw);
+    c = std::max<int64_t>(0, std::min(p.q, dim_dw - f));
+  };
+  p.heads.assign((size_t)world, 0);
+  for (int r = 0; r < world; r++) {
+    int64_t f, c;
+    range(r, f, c);
+    p.heads[(size_t)r] = shard_head(dw, f, c, nullptr);
+    p.H = std::max(p.H, (int)p.heads[(size_t)r]);
+  }
+  if (p.H > kRdmMaxRun - 1) return "a halo longer than a run";
+  // the halo this rank sends
+  p.pack.nrows = p.H;
+  const int32_t head = p.rank >= 0 ? p.heads[(size_t)p.rank] : 0;
+  for (int i = 0; i < head; i++) {
+    p.pack.sel[i] = 1;
+    p.pack.row[i] = i;
+  }
+  // interior runs and the tail run
+  RdmRuns in;
+  size_t j = 0;
+  if (p.count > 0) shard_head(dw, p.first, p.count, &j);
+  for (; p.count > 0 && j < dw.k.size() && dw.start[j] < p.first + p.count; j++) {
+    if (dw.start[j + 1] <= p.first + p.count) {
+      in.start.push_back((int32_t)(dw.start[j] - p.first));
+      in.k.push_back(dw.k[j]);
+      continue;
+    }
+    p.tail_row = (int32_t)(dw.start[j] - p.first);
+    p.tail_own = (int32_t)(p.count - p.tail_row);
+    p.tail_ld = dw.start[j + 1] - dw.start[j];
+    p.tail_k = dw.k[j];
+  }
+  in.start.push_back((int32_t)p.count);
+  rdm_plan(rk, l, up, in, dim_up, p.count, nblk, cw, target_wgs, p.in);
+  if (p.tail_ld > 0) {
+    p.fill.nrows = p.tail_ld;
+    int n = 0;
+    for (; n < p.tail_own; n++) {
+      p.fill.sel[n] = 1;
+      p.fill.row[n] = p.tail_row + n;
+    }
+    for (int r = p.rank + 1; r < world && n < p.tail_ld; r++)
+      for (int i = 0; i < p.heads[(size_t)r] && n < p.tail_ld; i++, n++) {
+        p.fill.sel[n] = 2;
+        p.fill.rank[n] = r;
+        p.fill.row[n] = i;
+      }
+    if (n != p.tail_ld) return "the following ranks' heads do not complete the tail run";
+    RdmRuns one;
+    one.start = {0, p.tail_ld};
+    one.k = {(uint8_t)p.tail_k};
+    rdm_plan(rk, l, up, one, dim_up, p.tail_ld, nblk, cw, target_wgs, p.slab);
+  }
+  // one buffer of partial sums: per group the workgroups of `in`, then those of `slab` (no slab: `in` as it stands)
+  for (const RdmPlan* q : {&p.in, &p.slab})
+    for (const RdmGroup& g : q->groups) {
+      auto it = std::find_if(p.groups.begin(), p.groups.end(), [&](const RdmGroup& m) { return m.e0 == g.e0; });
+      if (it == p.groups.end()) {
+        p.groups.push_back(g);
+      } else {
+        if (it->e1 != g.e1) return "the two work lists split a down class differently";
+        it->nwg += g.nwg;
+      }
+    }
+  for (RdmGroup& g : p.groups) {
+    g.pbase = p.partial_entries;
+    p.partial_entries += (int64_t)g.nwg * (g.e1 - g.e0);
+  }
+  std::vector<int32_t> next(p.groups.size(), 0);
+  for (RdmPlan* q : {&p.in, &p.slab})
+    for (RdmWork& w : q->work) {
+      const size_t g = (size_t)(std::find_if(p.groups.begin(), p.groups.end(), [&](const RdmGroup& m) { return m.e0 == w.e0; }) -
+                                p.groups.begin());
+      if (g >= p.groups.size() || p.groups[g].e1 != w.e1) return "a workgroup without a group";
+      w.pofs = p.groups[g].pbase + (int64_t)next[g]++ * (w.e1 - w.e0);
+    }
+  return "";
+}
+
+std::string rdm_rows_emulate(const RdmShardPlan& p, const RdmRowCopy& t, int nblk, int64_t rowlen, const double* v,
+                             const double* halos, double* dst) {
+  if (t.nrows < 0 || t.nrows > kRdmMaxRun) return "more rows than a run";
+  const int64_t rank_stride = (int64_t)nblk * p.H * rowlen;  // of one vector
+  for (int b = 0; b < nblk; b++)
+    for (int r = 0; r < t.nrows; r++)
+      for (int64_t c = 0; c < rowlen; c++) {
+        double x = 0.0;
+        if (t.sel[r] == 1) {
+          if (t.row[r] < 0 || t.row[r] >= p.count || !v) return "shard row out of range";
+          x = v[((int64_t)b * p.count + t.row[r]) * rowlen + c];
+        } else if (t.sel[r] == 2) {
+          if (t.rank[r] < 0 || t.rank[r] >= p.world || !halos) return "halo rank out of range";
+          if (t.row[r] < 0 || t.row[r] >= p.heads[(size_t)t.rank[r]]) return "halo row past its rank's head";
+          x = halos[t.rank[r] * rank_stride + ((int64_t)b * p.H + t.row[r]) * rowlen + c];
+        } else if (t.sel[r] != 0) {
+          return "unknown row source";
+        }
+        dst[((int64_t)b * t.nrows + r) * rowlen + c] = x;
+      }
+  return "";
+}
+
+std::string rdm_shard_emulate(const RdmShardPlan& p, int64_t ntri, int64_t dim_up, int nblk, const double* v_shard,
+                              const double* slab, int cw, double* tri) {
+  std::vector<double> partial((size_t)p.partial_entries * cw, 0.0);
+  std::vector<char> written((size_t)p.partial_entries, 0);
+  std::string why = emulate_tiles(p.in, ntri, p.count * dim_up * nblk, dim_up, p.count, v_shard, cw, partial, written);
+  if (why.empty() && p.tail_ld > 0)
+    why = emulate_tiles(p.slab, ntri, (int64_t)p.tail_ld * dim_up * nblk, dim_up, p.tail_ld, slab, cw, partial, written);
+  return why.empty() ? emulate_final(p.groups, ntri, cw, partial, written, tri) : why;
 }
 
 }  // namespace edigpu

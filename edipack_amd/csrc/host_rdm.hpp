@@ -1,5 +1,5 @@
 // host_rdm.hpp -- host tables of the impurity reduced density matrix (edigpu_imp_rdm).  No HIP in here:
-// tests/host_rdm.cpp compiles this with g++.
+// tests/host_rdm.cpp and tests/host_rdm_shard.cpp compile this with g++.
 //
 // rho_imp = Tr_bath |v><v| of a normal-mode (ed_total_ud=T) sector, imp_rdm_normal (ED_RDM_NORMAL.f90:146-209).  A spin
 // word is I + 2^norb B (I: impurity pattern, B: bath pattern) and both sector maps ascend, so an index range of one spin
@@ -90,5 +90,50 @@ void rdm_plan(const RdmRanks& rk, const RdmLayout& l, const RdmRuns& up, const R
 // index checked against the sizes of what it reads or writes: "" on success, else the first violation.
 std::string rdm_plan_emulate(const RdmPlan& p, int64_t ntri, int64_t nel, int64_t dim_up, int64_t dim_dw, const double* v,
                              int cw, double* tri);
+
+// ---- a rank's down rows [first, first + count) of the sector (edigpu_imp_rdm_sharded) ----
+// The ranges are those of edigpu_shard_plan: q = ceil(dim_dw / world) rows per rank, rank r starts at min(r q, dim_dw).
+// A tile needs the whole down run of its bath word, and a rank boundary can cut a run.  The rank in whose range a run
+// STARTS owns it:
+//   interior runs lie wholly inside the range and are walked on the caller's shard in place (starts relative to `first`,
+//            block stride `count`); with first = 0, count = dim_dw they are the runs of the sector and `in` is rdm_plan's;
+//   the head is the rows from `first` up to the first run start inside the range (the whole range when no run starts
+//            there): rows of a run an earlier rank owns.  Every rank computes every rank's head, so the halo size
+//            H = max_r head(r) <= kRdmMaxRun - 1 is known everywhere; a rank sends its head rows of every block, padded to H;
+//   the tail run starts inside the range and ends beyond it: its owner copies its own last rows and the head rows of
+//            the following ranks, in rank order (more than one rank when q < the run's length), into a slab of one run per
+//            block, which the tiles kernel walks with the work list `slab`.
+// One table of row sources describes a copy of rows, for the halo (pack) and for the slab alike:
+struct RdmRowCopy {
+  int32_t nrows = 0;                    // rows of one block of the destination
+  int8_t sel[kRdmMaxRun] = {0};         // 0: zeros, 1: row[] of the shard's block, 2: row[] of rank[]'s halo
+  int32_t rank[kRdmMaxRun] = {0};
+  int32_t row[kRdmMaxRun] = {0};
+};
+struct RdmShardPlan {
+  int world = 1, rank = 0;              // rank: -1 for a range that holds no row
+  int64_t first = 0, count = 0, q = 0;  // the range cut to the sector
+  int H = 0;                            // rows of a rank's halo (the same on every rank)
+  std::vector<int32_t> heads;           // [world]
+  int32_t tail_row = 0, tail_own = 0, tail_ld = 0, tail_k = -1;  // the run this rank owns across its end: first row
+                                        // relative to `first`, rows held here, length, class; tail_ld = 0: none
+  RdmRowCopy pack, fill;                // the halo this rank sends (H rows), the slab (tail_ld rows)
+  RdmPlan in, slab;                     // work lists of the interior runs and of the slab; their partial sums share one
+  std::vector<RdmGroup> groups;         // buffer: per group the workgroups of `in`, then those of `slab`
+  int64_t partial_entries = 0;
+};
+// "" on success; a message when (first, count) is not a rank's range of edigpu_shard_plan for `world` ranks
+std::string rdm_shard_plan(const RdmRanks& rk, const RdmLayout& l, const RdmRuns& up, const RdmRuns& dw, int64_t dim_up,
+                           int64_t dim_dw, int nblk, int cw, int target_wgs, int world, int64_t first, int64_t count,
+                           RdmShardPlan& p);
+// The row-copy kernel restated (kernels_rdm.hip rdm_rows_kernel), every index checked: dst[nblk][t.nrows][rowlen] of one
+// vector from the shard v[nblk][count][rowlen] (null when count = 0) and the gathered halos [world][nblk][H][rowlen]
+// (null for the pack); a halo row past its rank's head is a violation.
+std::string rdm_rows_emulate(const RdmShardPlan& p, const RdmRowCopy& t, int nblk, int64_t rowlen, const double* v,
+                             const double* halos, double* dst);
+// The two tile launches and the final sums restated on the host as rdm_plan_emulate does: `in` on the shard, `slab`
+// on the slab [nblk][tail_ld][dim_up] (null when tail_ld = 0), tri = this rank's packed sums.
+std::string rdm_shard_emulate(const RdmShardPlan& p, int64_t ntri, int64_t dim_up, int nblk, const double* v_shard,
+                              const double* slab, int cw, double* tri);
 
 }  // namespace edigpu

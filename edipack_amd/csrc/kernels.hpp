@@ -320,6 +320,17 @@ size_t rdm_lds_bytes(const RdmArgs& a);
 // blocks of pstride doubles; groups: host array.  Enqueued on st, no synchronisation.
 int launch_imp_rdm(const RdmArgs& a, int nwork, const RdmGroup* groups, int ngroups, const double* v, int64_t vstride,
                    int nvec, double* partial, int64_t pstride, double* out, int64_t ostride, hipStream_t st);
+// The same of a rank's down rows (edigpu_imp_rdm_sharded; host_rdm.hpp RdmShardPlan): the work list of `in` on the
+// shards v, that of `slab` (nslab workgroups, 0: none) on the boundary slabs, their partial sums in one buffer of nvec
+// blocks of pstride doubles; the final sums run over the groups of both.
+int launch_imp_rdm_shard(const RdmArgs& in, int nin, const double* v, int64_t vstride, const RdmArgs& slab, int nslab,
+                         const double* vslab, int64_t sstride, const RdmGroup* groups, int ngroups, int nvec, double* partial,
+                         int64_t pstride, double* out, int64_t ostride, hipStream_t st);
+// dst[nvec][nblk][t.nrows][rowlen] <- the rows t names: of the shards v (vstride doubles apart, nblk blocks of `count`
+// rows of rowlen doubles), of the gathered halos [world][nvec][nblk][H][rowlen], or zeros.  The halo a rank sends
+// (RdmShardPlan::pack, halos = null) and the slab of its tail run (RdmShardPlan::fill).
+int launch_rdm_rows(const RdmRowCopy& t, int nblk, int rowlen, int nvec, const double* v, int64_t vstride, int64_t count,
+                    const double* halos, int H, double* dst, hipStream_t st);
 
 // ---- the same of superc / nonsu2 vectors (kernels_rdm_flat.hip; tables and work list: host_rdm_flat.hpp) ----
 struct RdmFlatArgs {  // the device copies of an RdmFlatPlan

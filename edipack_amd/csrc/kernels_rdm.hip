@@ -13,6 +13,10 @@
 //   at the end the workgroup writes its e1 - e0 sums to its own place.
 // rdm_final_kernel adds the workgroups of a group in workgroup order (16 sub-ranges, then those in order): a fixed
 // order, no floating-point atomics, the same bits on every call.
+//
+// Sharded vectors (edigpu_imp_rdm_sharded; host_rdm.hpp RdmShardPlan): the same two kernels over two work lists -- the
+// runs inside the rank's rows on the shard in place, the run a rank boundary cuts on a slab -- whose partial sums share
+// one buffer; rdm_rows_kernel copies the few rows of the halo a rank sends and of the slab.
 #include "kernels.hpp"
 
 namespace edigpu {
@@ -113,6 +117,23 @@ __global__ __launch_bounds__(64 * kRdmFinalGroups) void rdm_final_kernel(const d
   }
 }
 
+// dst[vec][blk][row][0:rowlen) <- the source t names for `row` (host_rdm.hpp RdmRowCopy, whose rdm_rows_emulate is this
+// kernel on the host): a row of the shard's block, a row of a rank's gathered halo, or zeros.  One double per thread,
+// consecutive threads on consecutive doubles of the row on both sides (the vectors may be 8-byte aligned only).
+__global__ __launch_bounds__(kRdmThreads) void rdm_rows_kernel(RdmRowCopy t, int nblk, int rowlen, const double* __restrict__ v,
+                                                               int64_t vstride, int64_t count, const double* __restrict__ halos,
+                                                               int H, int64_t rank_stride, double* __restrict__ dst) {
+  const int c = blockIdx.x * kRdmThreads + threadIdx.x;
+  if (c >= rowlen) return;
+  const int b = blockIdx.y / t.nrows, r = blockIdx.y - b * t.nrows, k = blockIdx.z;
+  const int sel = t.sel[r];
+  const int64_t row = t.row[r];
+  double x = 0.0;
+  if (sel == 1) x = v[k * vstride + ((int64_t)b * count + row) * rowlen + c];
+  else if (sel == 2) x = halos[t.rank[r] * rank_stride + (((int64_t)k * nblk + b) * H + row) * rowlen + c];
+  dst[(((int64_t)k * nblk + b) * t.nrows + r) * rowlen + c] = x;
+}
+
 }  // namespace
 
 size_t rdm_lds_bytes(const RdmArgs& a) {
@@ -120,10 +141,8 @@ size_t rdm_lds_bytes(const RdmArgs& a) {
   return doubles * sizeof(double) + (((size_t)a.rel_max * sizeof(uint16_t) + 15) & ~(size_t)15);
 }
 
-int launch_imp_rdm(const RdmArgs& a, int nwork, const RdmGroup* groups, int ngroups, const double* v, int64_t vstride,
-                   int nvec, double* partial, int64_t pstride, double* out, int64_t ostride, hipStream_t st) {
-  EDIGPU_HIP(hipMemsetAsync(out, 0, (size_t)nvec * ostride * sizeof(double), st));  // classes the sector does not hold
-  if (nwork <= 0) return 0;
+static int launch_rdm_tiles(const RdmArgs& a, int nwork, const double* v, int64_t vstride, int nvec, double* partial,
+                            int64_t pstride, hipStream_t st) {
   const size_t lds = rdm_lds_bytes(a);
   const dim3 grid((unsigned)nwork, (unsigned)nvec);
   if (a.cw == 2) {
@@ -134,12 +153,43 @@ int launch_imp_rdm(const RdmArgs& a, int nwork, const RdmGroup* groups, int ngro
     rdm_tiles_kernel<1><<<grid, kRdmThreads, lds, st>>>(a, v, vstride, partial, pstride);
   }
   EDIGPU_HIP(hipGetLastError());
+  return 0;
+}
+
+static int launch_rdm_final(const RdmGroup* groups, int ngroups, int cw, int nvec, const double* partial, int64_t pstride,
+                            double* out, int64_t ostride, hipStream_t st) {
   for (int k = 0; k < ngroups; k++) {
-    const int n = (groups[k].e1 - groups[k].e0) * a.cw;
+    const int n = (groups[k].e1 - groups[k].e0) * cw;
     rdm_final_kernel<<<dim3((unsigned)((n + 63) / 64), (unsigned)nvec), 64 * kRdmFinalGroups, 0, st>>>(partial, pstride, groups[k],
-                                                                                                     a.cw, out, ostride);
+                                                                                                     cw, out, ostride);
     EDIGPU_HIP(hipGetLastError());
   }
+  return 0;
+}
+
+int launch_imp_rdm(const RdmArgs& a, int nwork, const RdmGroup* groups, int ngroups, const double* v, int64_t vstride,
+                   int nvec, double* partial, int64_t pstride, double* out, int64_t ostride, hipStream_t st) {
+  EDIGPU_HIP(hipMemsetAsync(out, 0, (size_t)nvec * ostride * sizeof(double), st));  // classes the sector does not hold
+  if (nwork <= 0) return 0;
+  if (launch_rdm_tiles(a, nwork, v, vstride, nvec, partial, pstride, st)) return 1;
+  return launch_rdm_final(groups, ngroups, a.cw, nvec, partial, pstride, out, ostride, st);
+}
+
+int launch_imp_rdm_shard(const RdmArgs& in, int nin, const double* v, int64_t vstride, const RdmArgs& slab, int nslab,
+                         const double* vslab, int64_t sstride, const RdmGroup* groups, int ngroups, int nvec, double* partial,
+                         int64_t pstride, double* out, int64_t ostride, hipStream_t st) {
+  EDIGPU_HIP(hipMemsetAsync(out, 0, (size_t)nvec * ostride * sizeof(double), st));  // classes the rows do not hold
+  if (nin > 0 && launch_rdm_tiles(in, nin, v, vstride, nvec, partial, pstride, st)) return 1;
+  if (nslab > 0 && launch_rdm_tiles(slab, nslab, vslab, sstride, nvec, partial, pstride, st)) return 1;
+  return launch_rdm_final(groups, ngroups, in.cw, nvec, partial, pstride, out, ostride, st);
+}
+
+int launch_rdm_rows(const RdmRowCopy& t, int nblk, int rowlen, int nvec, const double* v, int64_t vstride, int64_t count,
+                    const double* halos, int H, double* dst, hipStream_t st) {
+  if (t.nrows <= 0 || nblk <= 0 || rowlen <= 0 || nvec <= 0) return 0;
+  const dim3 grid((unsigned)((rowlen + kRdmThreads - 1) / kRdmThreads), (unsigned)(t.nrows * nblk), (unsigned)nvec);
+  rdm_rows_kernel<<<grid, kRdmThreads, 0, st>>>(t, nblk, rowlen, v, vstride, count, halos, H, (int64_t)nvec * nblk * H * rowlen, dst);
+  EDIGPU_HIP(hipGetLastError());
   return 0;
 }
 

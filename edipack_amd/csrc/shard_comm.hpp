@@ -27,8 +27,12 @@ struct ShardWorkspace {
   // observables on shards (edigpu_shard_obs.hip): host vectors staged for the kernels, the packed sums of a reduction
   double *obs = nullptr, *red = nullptr;
   int64_t obs_cap = 0, red_cap = 0;
+  // impurity reduced density matrix on shards: the halo rows this rank sends, the halos of all ranks, the boundary slab
+  double *halo = nullptr, *halos = nullptr, *slab = nullptr;
+  int64_t halo_cap = 0, halos_cap = 0, slab_cap = 0;
   void release() {  // (with the communicator's device current)
-    dev_free_all(vin, vout, tmp, vfull, send, recv, hvc, back, hist, work, scr, bp[0], bp[1], bp[2], bp[3], bp[4], obs, red);
+    dev_free_all(vin, vout, tmp, vfull, send, recv, hvc, back, hist, work, scr, bp[0], bp[1], bp[2], bp[3], bp[4], obs, red, halo,
+                 halos, slab);
   }
   ~ShardWorkspace() { release(); }
 };

@@ -176,7 +176,7 @@ class LibraryComm:
             out.ctypes.data_as(C.c_void_p) if out.size else None, n, a, cr, io, sp), "edigpu_apply_cops_sharded")
         return out
 
-    # ---- occupation and phonon observables on shards (csrc/edigpu_shard_obs.hip) -------------------------------
+    # ---- occupation and phonon observables, impurity density matrix on shards (csrc/edigpu_shard_obs.hip) -----
     # A shard is a numpy array of this rank's elements (several vectors: [nvec, nloc]) or an int, the address of
     # the same on the device -- e.g. the evecs of eigh_multi uploaded, or a torch tensor's data_ptr().  The library
     # knows the shard's length from the handle and the communicator; a rank that owns no row passes an empty array.
@@ -254,6 +254,21 @@ class LibraryComm:
         p, _keep = self._shard_ptr(h, v_shard)
         self._capi.check(self._capi.lib().edigpu_ph_rdm_sharded(h._h, self._c, p, nvec, rho.ctypes.data_as(C.POINTER(C.c_double)),
                                                                 self._capi.pd(nrm)), "edigpu_ph_rdm_sharded")
+        return rho, nrm
+
+    def imp_rdm(self, h, v_shard, nvec: int = 1):
+        """SectorHamiltonian.imp_rdm of nvec vectors held as shards (normal mode): (rho[nvec, D, D], norm2[nvec]),
+        D = 4^norb, not normalised, complex on complex handles -- what rdm_average, rdm_occupations and
+        entanglement_entropy of edipack_amd.observables take.  The sums over all ranks, the same bits on every rank.
+        Collective: a run of down rows that a rank boundary cuts is completed by one all-gather of a few rows."""
+        import ctypes as C
+        import numpy as np
+        D = 4 ** (h.norb or self._capi.MAXORB)
+        rho = np.zeros((nvec, D, D), dtype=np.complex128 if h.is_complex else np.float64)
+        nrm = np.zeros(nvec)
+        p, _keep = self._shard_ptr(h, v_shard)
+        self._capi.check(self._capi.lib().edigpu_imp_rdm_sharded(h._h, self._c, p, nvec, rho.ctypes.data_as(C.POINTER(C.c_double)),
+                                                                 self._capi.pd(nrm)), "edigpu_imp_rdm_sharded")
         return rho, nrm
 
     def bench(self, h, warmup: int, steps: int):

@@ -462,6 +462,13 @@ module EDIGPU_SHIM
        real(c_double), intent(inout) :: rho(*), norm2(*)
        integer(c_int) :: ierr
      end function edigpu_ph_rdm_sharded
+     function edigpu_imp_rdm_sharded(h, c, v_shard, nvec, rdm, norm2) bind(C, name="edigpu_imp_rdm_sharded") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, c, v_shard
+       integer(c_int), value :: nvec
+       real(c_double), intent(inout) :: rdm(*), norm2(*)
+       integer(c_int) :: ierr
+     end function edigpu_imp_rdm_sharded
      function edigpu_destroy(h) bind(C, name="edigpu_destroy") result(ierr)
        import :: c_ptr, c_int
        type(c_ptr), value :: h
@@ -496,6 +503,7 @@ module EDIGPU_SHIM
   public :: gpu_sp_eigh_mpi_d, gpu_sp_eigh_mpi_c, gpu_apply_op_mpi_d
   ! observables and the chi_spin / chi_dens / phonon seeds on the shards the MPI solve leaves
   public :: gpu_occ_moments_mpi, gpu_apply_op_N_mpi, gpu_apply_op_Sz_mpi, gpu_apply_xph_mpi, gpu_ph_rdm_mpi
+  public :: gpu_imp_rdm_mpi
 
 contains
 
@@ -1288,6 +1296,19 @@ contains
     if (size(rho, 4) /= size(norm2) .or. size(rho, 1) /= size(rho, 2)) stop "gpu_ph_rdm_mpi: shapes"
     call gpu_check(edigpu_ph_rdm_sharded(h, gpu_comm, v_shard, int(size(norm2), c_int), rho, norm2), "gpu_ph_rdm_mpi")
   end subroutine gpu_ph_rdm_mpi
+
+  !> gpu_imp_rdm of size(nrm) REAL vectors held as shards (imp_rdm_normal under -D_MPI, ED_RDM_NORMAL.f90:146-209, without
+  !! es_return_dvector_mpi): rho(io, jo, k), D = 4**Norb, io = Iup + 2**Norb Idw + 1, not normalised (nrm(k) = its
+  !! trace), symmetric; the sums over all ranks, the same bits on every rank.  v_shard: this rank's down rows, host or
+  !! device, c_null_ptr on a rank without rows.  Normal mode only.  Complex handles return interleaved (re, im): call
+  !! edigpu_imp_rdm_sharded.  Collective.
+  subroutine gpu_imp_rdm_mpi(h, v_shard, rho, nrm)
+    type(c_ptr), intent(in) :: h, v_shard
+    real(8), intent(inout) :: rho(:, :, :), nrm(:)
+    if (.not. c_associated(gpu_comm)) stop "gpu_imp_rdm_mpi: no communicator"
+    if (size(rho, 3) /= size(nrm) .or. size(rho, 1) /= size(rho, 2)) stop "gpu_imp_rdm_mpi: shapes"
+    call gpu_check(edigpu_imp_rdm_sharded(h, gpu_comm, v_shard, int(size(nrm), c_int), rho, nrm), "gpu_imp_rdm_mpi")
+  end subroutine gpu_imp_rdm_mpi
 
   !> delete_Hv_sector_* counterpart (ED_NORMAL/ED_HAMILTONIAN_NORMAL.f90:212-279)
   subroutine gpu_delete_sector()

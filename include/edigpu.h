@@ -836,7 +836,7 @@ int edigpu_apply_cops_sharded(edigpu_handle src, edigpu_handle dst, edigpu_comm 
  * occ_moments / ph_rdm are collective: the results have the shapes of the single-GPU entries, hold the sums over all
  * ranks and are bit-identical on every rank and from call to call.  apply_occ (v_dst may be v_src) and apply_xph (no
  * overlap) exchange nothing: `c` only gives the geometry.  All four return after the device has finished.  The
- * impurity density matrix is not among them: a bath word's run of down rows can straddle two ranks.
+ * impurity density matrix has its own entry below: a bath word's run of down rows can straddle ranks.
  */
 int edigpu_occ_moments_sharded(edigpu_handle h, edigpu_comm c, const double *v_shard, int nvec, double *moments_host,
                                double *norm2_host);
@@ -845,6 +845,22 @@ int edigpu_apply_occ_sharded(edigpu_handle h, edigpu_comm c, const double *v_src
 int edigpu_apply_xph_sharded(edigpu_handle h, edigpu_comm c, const double *v_src_shard, double *v_dst_shard);
 int edigpu_ph_rdm_sharded(edigpu_handle h, edigpu_comm c, const double *v_shard, int nvec, double *rho_host,
                           double *norm2_host);
+/*
+ * edigpu_imp_rdm on shards (imp_rdm_normal under -D_MPI, rdm_flag=T, without es_return_dvector_mpi): normal mode only --
+ * real, _CMPLX_NORMAL and phonon sectors, Norb <= 5 -- on the handles and vectors of edigpu_occ_moments_sharded (the whole
+ * sector or the rank's down-row shard; v_shard: nvec consecutive shards in the reference's row layout, host or device,
+ * read only; NULL on a rank that owns no row).  A tile needs the C(Norb, k) <= 10 consecutive down rows of one bath word,
+ * and a rank boundary can cut such a run: every rank sends the rows at the start of its range that belong to a run begun
+ * on an earlier rank (at most 9, the same padded count H on every rank, known without communication; one all-gather,
+ * skipped everywhere when H = 0), the rank a cut run starts on completes it, and one all-reduce adds the packed
+ * triangles.  Collective.  Every rank receives nvec matrices and traces as edigpu_imp_rdm returns them (D = 4^Norb,
+ * io = Iup + 2^Norb Idw, not normalised, exactly Hermitian, (re, im) interleaved on complex handles; norm2_host may be
+ * NULL), bit-identical on every rank and from call to call; a world of one returns the bits of edigpu_imp_rdm.  Refused
+ * before any collective: superc / nonsu2, ed_total_ud=F and hand-over handles, Norb out of range, nvec <= 0, NULL
+ * arguments, and what the sharded product refuses of a handle.
+ */
+int edigpu_imp_rdm_sharded(edigpu_handle h, edigpu_comm c, const double *v_shard, int nvec, double *rdm_host,
+                           double *norm2_host);
 /* bench.py --gpus N: `warmup` + `steps` sharded Lanczos steps on a seeded random vector; wall time per step between
  * two collectives that act as barriers, and the bytes this rank sends per product */
 int edigpu_lanczos_bench_sharded(edigpu_handle h, edigpu_comm c, int warmup, int steps, double *ms_per_step,

@@ -14,6 +14,12 @@ edigpu_dev_download of the vector plus the numpy restatement of imp_rdm_normal (
 it (wall clock, once); for the flat sectors the restatement is tests/rdm_flat_cases.py::numpy_rdm_flat.
 
     python scripts/time_rdm.py [--workloads cfg2,cfg3_ns16 | cfg5,superc_ns13] [--steps 21]
+
+--sharded (normal-mode sectors only) times edigpu_imp_rdm_sharded instead: a world of ONE rank on the RCCL communicator
+with its collectives forced (EDIGPU_FORCE_COLLECTIVES=1), the vector passed as a device pointer, against edigpu_imp_rdm
+on the same vector -- both as whole calls by the wall clock (kernels, the download of the packed result, its placement),
+medians of --steps calls after --warmup.  A one-GPU rehearsal of the calls, not a scaling measurement: the line goes
+into profiles/rdm.json under "sharded_rehearsal".
 """
 import argparse
 import ctypes as C
@@ -52,12 +58,59 @@ def host_baseline(h, model, sector, v_ptr):
     return t1 - t0, t3 - t2, rho
 
 
+def wall_median_ms(call, warmup, steps):
+    ts = []
+    for k in range(warmup + steps):
+        t0 = time.perf_counter()
+        call()
+        if k >= warmup:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def sharded_rehearsal(args):
+    os.environ["EDIGPU_FORCE_COLLECTIVES"] = "1"          # read when the communicator is made
+    import torch
+    from edipack_amd import capi
+    from edipack_amd.sharding import LibraryComm
+    from edipack_amd.synthetic import WORKLOADS, build_workload
+    capi.init(0)
+    comm = LibraryComm(0, 1, unique_id=LibraryComm.unique_id())
+    out = {"script": "scripts/time_rdm.py --sharded", "kernel_source_hash": capi.kernel_source_hash(), "steps": args.steps,
+           "warmup": args.warmup, "world": 1, "collectives": "forced (RCCL)", "sectors": []}
+    for name in args.workloads.split(","):
+        w = WORKLOADS[name]
+        if w.ed_mode != "normal":
+            raise SystemExit("time_rdm.py --sharded: normal-mode workloads only")
+        h = build_workload(w)
+        gen = torch.Generator(device="cuda").manual_seed(1234)
+        v = torch.randn(h.dim * (2 if h.is_complex else 1), dtype=torch.float64, device="cuda", generator=gen)
+        torch.cuda.synchronize()
+        rho, n2 = h.imp_rdm(v.data_ptr())
+        rho_s, n2_s = comm.imp_rdm(h, v.data_ptr())
+        ms_one = wall_median_ms(lambda: h.imp_rdm(v.data_ptr()), args.warmup, args.steps)
+        ms_sh = wall_median_ms(lambda: comm.imp_rdm(h, v.data_ptr()), args.warmup, args.steps)
+        ms_kernels = h.time_rdm(v.data_ptr(), args.warmup, args.steps)
+        out["sectors"].append({"workload": name, "note": w.note, "dim": h.dim, "norb": h.norb,
+                               "imp_rdm_call_ms": ms_one, "imp_rdm_sharded_call_ms": ms_sh, "ratio": ms_sh / ms_one,
+                               "imp_rdm_kernels_ms": ms_kernels,
+                               "same_bits": bool(np.array_equal(rho, rho_s) and np.array_equal(n2, n2_s))})
+        h.destroy()
+        del v
+        torch.cuda.empty_cache()
+    comm.destroy()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="cfg2,cfg3_ns16")
     ap.add_argument("--steps", type=int, default=21)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--sharded", action="store_true", help="one-rank rehearsal of edigpu_imp_rdm_sharded against edigpu_imp_rdm")
     args = ap.parse_args()
+    if args.sharded:
+        return sharded_rehearsal(args)
     import torch
     from edipack_amd import capi
     from edipack_amd.synthetic import WORKLOADS, Workload, build_workload, synthetic_model
