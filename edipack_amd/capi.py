@@ -183,6 +183,9 @@ SIGNATURES = {
     "edigpu_lanczos_eigh_sharded": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, _pd, _vp, _pint]),
     "edigpu_exchange_bench": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int32), _pd]),
     "edigpu_apply_cops_sharded": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _pd, _vp, _vp, _vp]),
+    "edigpu_apply_cops_sharded_info": (C.c_int, [_vp, _vp, _vp, C.c_int, _pd, _vp, _vp, _vp, _pi64]),
+    "edigpu_apply_pairs_sharded": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _pd, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32]),
+    "edigpu_apply_pairs_sharded_info": (C.c_int, [_vp, _vp, _vp, C.c_int, _pd, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32, _pi64]),
     "edigpu_occ_moments_sharded": (C.c_int, [_vp, _vp, _vp, C.c_int, _pd, _pd]),
     "edigpu_apply_occ_sharded": (C.c_int, [_vp, _vp, _vp, _vp, _pd, _pd]),
     "edigpu_apply_xph_sharded": (C.c_int, [_vp, _vp, _vp, _vp]),

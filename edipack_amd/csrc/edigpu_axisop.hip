@@ -81,7 +81,8 @@ std::string axis_label(const std::vector<int>& u, const std::vector<int>& d) {
   return s + ")";
 }
 
-// every check of a call and the host tables; need_kind4: the _z entry point
+// every check of a call and the host tables; need_kind4: the _z entry point; v_src = v_dst = null: no vectors to compare
+// (the sharded call checks its shards itself)
 int axis_prepare(const edigpu_sector* src, const edigpu_sector* dst, const double* v_src, const double* v_dst, int nops,
                  const int32_t* create, const int32_t* iorb, const int32_t* ispin, bool need_kind4, const std::string& who,
                  AxisTables& tab) {
@@ -146,11 +147,13 @@ int axis_prepare(const edigpu_sector* src, const edigpu_sector* dst, const doubl
     set_error(who + ": the tables do not have the handles' dimensions");
     return 1;
   }
-  const char *a0 = (const char*)v_src, *a1 = a0 + src->dim * w * (int64_t)sizeof(double);
-  const char *b0 = (const char*)v_dst, *b1 = b0 + dst->dim * w * (int64_t)sizeof(double);
-  if (a0 < b1 && b0 < a1) {
-    set_error(who + ": v_dst_dev overlaps v_src_dev (the gather cannot run in place)");
-    return 1;
+  if (v_src && v_dst) {
+    const char *a0 = (const char*)v_src, *a1 = a0 + src->dim * w * (int64_t)sizeof(double);
+    const char *b0 = (const char*)v_dst, *b1 = b0 + dst->dim * w * (int64_t)sizeof(double);
+    if (a0 < b1 && b0 < a1) {
+      set_error(who + ": v_dst_dev overlaps v_src_dev (the gather cannot run in place)");
+      return 1;
+    }
   }
   return 0;
 }
@@ -188,6 +191,15 @@ int axis_call(edigpu_sector* dst, const AxisTables& tab, const double* cre, cons
 }
 
 }  // namespace
+
+int axisop_tables(const edigpu_sector* src, const edigpu_sector* dst, int nops, const int32_t* create, const int32_t* iorb,
+                  const int32_t* ispin, bool cplx_coef, const char* who, AxisTables& tab) {
+  return axis_prepare(src, dst, nullptr, nullptr, nops, create, iorb, ispin, cplx_coef, who, tab);
+}
+
+int axisop_upload(edigpu_sector* dst, const AxisTables& tab, const double* cre, const double* cim, AxisArgs& a, hipStream_t st) {
+  return axis_upload(dst, tab, cre, cim, a, st);
+}
 
 bool axisop_route(const edigpu_sector* src, const edigpu_sector* dst) {
   auto old_kind = [](const edigpu_sector* s) { return s->kind == kNormal && s->built_by_library && s->nph == 0; };

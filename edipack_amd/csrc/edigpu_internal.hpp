@@ -11,6 +11,7 @@
 
 #include "../../include/edigpu.h"
 #include "host_build.hpp"
+#include "shard_src.hpp"
 #include "switches.hpp"
 
 namespace edigpu {
@@ -265,6 +266,21 @@ bool axisop_route(const edigpu_sector* src, const edigpu_sector* dst);
 int axisop_apply(edigpu_sector* src, edigpu_sector* dst, const double* v_src, double* v_dst, int nops, const double* cre,
                  const double* cim, const int32_t* create, const int32_t* iorb, const int32_t* ispin, hipStream_t st,
                  const char* who);
+// The two halves of axisop_apply for the call on shards (edigpu_shard_seeds.hip): every check of the handles and
+// operators with the host tables (no device is touched), and the tables into the destination handle's scratch.
+struct AxisTables;
+struct AxisArgs;
+int axisop_tables(const edigpu_sector* src, const edigpu_sector* dst, int nops, const int32_t* create, const int32_t* iorb,
+                  const int32_t* ispin, bool cplx_coef, const char* who, AxisTables& tab);
+int axisop_upload(edigpu_sector* dst, const AxisTables& tab, const double* cre, const double* cim, AxisArgs& a, hipStream_t st);
+// The same of edigpu_apply_pairs_normal (edigpu_pairs.hip): checks and host tables; upload, launch, wait, free.  win = null:
+// no term moves a down electron and the call runs on the rank's `rows` down rows alone, else the window + source form.
+struct PairsTables;
+int pairs_shard_tables(const edigpu_sector* src, const edigpu_sector* dst, int nterms, const double* coef, const int32_t* create1,
+                       const int32_t* iorb1, const int32_t* ispin1, const int32_t* create2, const int32_t* iorb2,
+                       const int32_t* ispin2, const std::string& who, PairsTables& tab);
+int pairs_shard_call(const edigpu_sector* src, const PairsTables& tab, const ShardWindow* win, int64_t rows, const double* v_src,
+                     double* v_dst, hipStream_t st);
 
 // Interleaved workspace of edigpu_apply_multi_dev / edigpu_lanczos_tridiag_batch_dev (edigpu_batch.hip; kernels_multi.hip):
 // two buffers of W vectors, the per-column partial sums and scalars.  Allocated by the first batch call on the handle,
@@ -463,9 +479,15 @@ int trl_solve(int device, hipStream_t st, int cplx, int64_t n, int64_t len, int6
               int* nconv_out, int* nmatvec_out);
 // edigpu_ops.hip: apply_Cops on a window of destination units: v_dst_rows = sum_s coef_s O_s v_src for the
 // destination's down rows (normal mode) / rows (superc, nonsu2) [first, first + count); v_src_full holds the WHOLE source
-// vector in the reference's layout; coef2 = (re, im) per operator (normal mode: real).  Returns after the stream finished.
+// vector in the reference's layout; coef2 = (re, im) per operator (normal mode: real).  gathered (superc / nonsu2 only):
+// v_src_full is the all-gather of the ranks' padded chunks instead, shard_src.hpp counted in double2 -- the form phonon row
+// shards need.  checked: the caller has made apply_cops_rows_check with the same arguments.  Returns after the stream finished.
 int apply_cops_rows(edigpu_sector* src, edigpu_sector* dst, const double* v_src_full, double* v_dst_rows, int64_t first,
                     int64_t count, int nops, const double* coef2, const int32_t* create, const int32_t* iorb,
-                    const int32_t* ispin, hipStream_t st, const char* who);
+                    const int32_t* ispin, hipStream_t st, const char* who, const ShardSrc* gathered = nullptr,
+                    bool checked = false);
+// its checks of the handles and operators alone (no device is touched), every operator before any launch
+int apply_cops_rows_check(const edigpu_sector* src, const edigpu_sector* dst, int nops, const double* coef2, const int32_t* create,
+                          const int32_t* iorb, const int32_t* ispin, const char* who, const ShardSrc* gathered = nullptr);
 
 }  // namespace edigpu

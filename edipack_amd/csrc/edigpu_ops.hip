@@ -10,13 +10,8 @@
 
 namespace edigpu {
 
-// one term of apply_Cops / apply_op_C / apply_op_CDG on device vectors of two normal-mode sectors:
-// v_dst (=|+=) coef * c^(+)_{iorb,ispin} v_src
-// one operator of apply_Cops on normal-mode sectors: the destination's down rows [fd, fd + cd) (v_dst_dev holds those
-// rows), v_src_dev = the whole source vector
-static int apply_op_normal_term(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev,
-                                int iorb, int ispin, int create, double coef, int accumulate, hipStream_t st,
-                                const char* who, int64_t fd = 0, int64_t cd = -1) {
+// the checks of one term of apply_Cops on normal-mode sectors, on the handles alone (no device is touched)
+static int normal_term_check(const edigpu_sector* src, const edigpu_sector* dst, int iorb, int ispin, int create, const char* who) {
   const std::string w(who);
   if (src->kind != kNormal || dst->kind != kNormal || !src->from_model() || !dst->from_model() || src->has_phonons() || dst->has_phonons()) {
     set_error(w + ": both handles must be normal-mode sectors built by edigpu_normal_build");
@@ -38,6 +33,19 @@ static int apply_op_normal_term(edigpu_handle src, edigpu_handle dst, const doub
     set_error(w + ": destination sector is not (source sector +- one particle of that spin)");
     return 1;
   }
+  return 0;
+}
+
+// one term of apply_Cops / apply_op_C / apply_op_CDG on device vectors of two normal-mode sectors:
+// v_dst (=|+=) coef * c^(+)_{iorb,ispin} v_src on the destination's down rows [fd, fd + cd) (v_dst_dev holds those rows),
+// v_src_dev = the whole source vector.  checked: the caller has made normal_term_check
+static int apply_op_normal_term(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev,
+                                int iorb, int ispin, int create, double coef, int accumulate, hipStream_t st,
+                                const char* who, int64_t fd = 0, int64_t cd = -1, bool checked = false) {
+  const std::string w(who);
+  if (!checked && normal_term_check(src, dst, iorb, ispin, create, who)) return 1;
+  const int ns = model_ns(src->model);
+  const int nup_s = src->sec_a, ndw_s = src->sec_b;
   if (cd < 0) cd = dst->dim_dw - fd;
   if (fd < 0 || fd + cd > dst->dim_dw) {
     set_error(w + ": row window outside the destination sector");
@@ -70,11 +78,10 @@ static int apply_op_normal_term(edigpu_handle src, edigpu_handle dst, const doub
   return rc;
 }
 
-// one operator of apply_Cops on superc / nonsu2 sectors (whole sectors or row shards of library-built ones): the
-// destination's rows [fd, fd + cd), v_src_dev = the whole source vector (complex)
-static int apply_op_flat_term(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev, int iorb,
-                              int ispin, int create, double cre, double cim, int accumulate, hipStream_t st, const char* who,
-                              int64_t fd = 0, int64_t cd = -1) {
+// the checks of one term of apply_Cops on superc / nonsu2 sectors, on the handles alone (no device is touched); windowed: a
+// row window was asked for; gathered: as for apply_op_flat_term
+static int flat_term_check(const edigpu_sector* src, const edigpu_sector* dst, int iorb, int ispin, int create, const char* who,
+                           bool windowed, const ShardSrc* gathered) {
   const std::string w(who);
   if ((!src->is_flat_family()) || (!dst->is_flat_family()) || !src->built_by_library ||
       !dst->built_by_library) {
@@ -86,7 +93,7 @@ static int apply_op_flat_term(edigpu_handle src, edigpu_handle dst, const double
     return 1;
   }
   const int nblk = src->nph + 1;
-  if (nblk > 1 && (!src->is_whole() || !dst->is_whole() || fd != 0 || cd >= 0)) {
+  if (nblk > 1 && !gathered && (!src->is_whole() || !dst->is_whole() || windowed)) {
     set_error(w + ": phonon sectors are served as whole sectors only (no shards, no row window)");
     return 1;
   }
@@ -106,6 +113,20 @@ static int apply_op_flat_term(edigpu_handle src, edigpu_handle dst, const double
     set_error(w + ": destination sector is not the one the operator leads to");
     return 1;
   }
+  return 0;
+}
+
+// one operator of apply_Cops on superc / nonsu2 sectors (whole sectors or row shards of library-built ones): the
+// destination's rows [fd, fd + cd), v_src_dev = the whole source vector (complex); gathered: v_src_dev is the all-gather
+// of the ranks' padded chunks instead (shard_src.hpp, counted in double2), which phonon row shards need.  checked: the
+// caller has made flat_term_check
+static int apply_op_flat_term(edigpu_handle src, edigpu_handle dst, const double* v_src_dev, double* v_dst_dev, int iorb,
+                              int ispin, int create, double cre, double cim, int accumulate, hipStream_t st, const char* who,
+                              int64_t fd = 0, int64_t cd = -1, const ShardSrc* gathered = nullptr, bool checked = false) {
+  const std::string w(who);
+  if (!checked && flat_term_check(src, dst, iorb, ispin, create, who, fd != 0 || cd >= 0, gathered)) return 1;
+  const int nblk = src->nph + 1;
+  const int ns = model_ns(src->model);
   EDIGPU_HIP(hipSetDevice(src->device));
   HostDirect hs, hd;
   std::string e = build_direct(src->model, src->sec_a, 0, -1, hs, src->jz, src->sec_b, !src->sw.direct_nosort);
@@ -125,26 +146,40 @@ static int apply_op_flat_term(edigpu_handle src, edigpu_handle dst, const double
   rc |= dev_upload(&d_rk, hs.rk_up.data(), hs.rk_up.size());
   if (!rc)
     rc = launch_apply_op_flat(cd, ns, 1u << (iorb + ispin * ns), create, d_states + fd, d_off, d_rk, v_src_dev, v_dst_dev, st,
-                              cre, cim, accumulate, nblk, hs.dim);  // phonon sectors: every electronic block, one launch
+                              cre, cim, accumulate, nblk, hs.dim, gathered);  // phonon sectors: every electronic block, one launch
   (void)hipStreamSynchronize(st);
   dev_free_all(d_states, d_off, d_rk);
   return rc;
 }
 
-int apply_cops_rows(edigpu_sector* src, edigpu_sector* dst, const double* v_src_full, double* v_dst_rows, int64_t first,
-                    int64_t count, int nops, const double* coef2, const int32_t* create, const int32_t* iorb,
-                    const int32_t* ispin, hipStream_t st, const char* who) {
+int apply_cops_rows_check(const edigpu_sector* src, const edigpu_sector* dst, int nops, const double* coef2, const int32_t* create,
+                          const int32_t* iorb, const int32_t* ispin, const char* who, const ShardSrc* gathered) {
   for (int s = 0; s < nops; s++) {
     if (src->kind == kNormal) {
       if (coef2[2 * s + 1] != 0.0) {
         set_error(std::string(who) + ": complex coefficients belong to the _CMPLX_NORMAL build");
         return 1;
       }
+      if (normal_term_check(src, dst, iorb[s], ispin[s], create[s] > 0, who)) return 1;
+    } else if (flat_term_check(src, dst, iorb[s], ispin[s], create[s] > 0, who, true, gathered)) {
+      return 1;
+    }
+  }
+  return 0;
+}
+
+int apply_cops_rows(edigpu_sector* src, edigpu_sector* dst, const double* v_src_full, double* v_dst_rows, int64_t first,
+                    int64_t count, int nops, const double* coef2, const int32_t* create, const int32_t* iorb,
+                    const int32_t* ispin, hipStream_t st, const char* who, const ShardSrc* gathered, bool checked) {
+  // every check of every operator once, before the first launch
+  if (!checked && apply_cops_rows_check(src, dst, nops, coef2, create, iorb, ispin, who, gathered)) return 1;
+  for (int s = 0; s < nops; s++) {
+    if (src->kind == kNormal) {
       if (apply_op_normal_term(src, dst, v_src_full, v_dst_rows, iorb[s], ispin[s], create[s] > 0, coef2[2 * s], s > 0, st, who,
-                               first, count))
+                               first, count, true))
         return 1;
     } else if (apply_op_flat_term(src, dst, v_src_full, v_dst_rows, iorb[s], ispin[s], create[s] > 0, coef2[2 * s],
-                                  coef2[2 * s + 1], s > 0, st, who, first, count)) {
+                                  coef2[2 * s + 1], s > 0, st, who, first, count, gathered, true)) {
       return 1;
     }
   }

@@ -50,7 +50,8 @@ bool same_model_shape(const edigpu_model& a, const edigpu_model& b) {
          a.nph == b.nph;
 }
 
-// every check of a call and the host tables
+// every check of a call and the host tables; v_src = v_dst = null: no vectors to compare (the sharded call checks its
+// shards itself)
 int pairs_prepare(const edigpu_sector* src, const edigpu_sector* dst, const double* v_src, const double* v_dst,
                   const std::vector<PairsTerm>& terms, const std::string& who, PairsTables& tab) {
   if (pairs_refuse(src, who, "source") || pairs_refuse(dst, who, "destination")) return 1;
@@ -78,11 +79,13 @@ int pairs_prepare(const edigpu_sector* src, const edigpu_sector* dst, const doub
     set_error(who + ": the tables do not have the handles' dimensions");
     return 1;
   }
-  const char *a0 = (const char*)v_src, *a1 = a0 + src->dim * (int64_t)sizeof(double);
-  const char *b0 = (const char*)v_dst, *b1 = b0 + dst->dim * (int64_t)sizeof(double);
-  if (a0 < b1 && b0 < a1) {
-    set_error(who + ": v_dst_dev overlaps v_src_dev (the gather cannot run in place)");
-    return 1;
+  if (v_src && v_dst) {
+    const char *a0 = (const char*)v_src, *a1 = a0 + src->dim * (int64_t)sizeof(double);
+    const char *b0 = (const char*)v_dst, *b1 = b0 + dst->dim * (int64_t)sizeof(double);
+    if (a0 < b1 && b0 < a1) {
+      set_error(who + ": v_dst_dev overlaps v_src_dev (the gather cannot run in place)");
+      return 1;
+    }
   }
   return 0;
 }
@@ -125,6 +128,35 @@ int pairs_call(const edigpu_sector* src, const PairsTables& tab, const double* v
 }
 
 }  // namespace
+
+int pairs_shard_tables(const edigpu_sector* src, const edigpu_sector* dst, int nterms, const double* coef, const int32_t* create1,
+                       const int32_t* iorb1, const int32_t* ispin1, const int32_t* create2, const int32_t* iorb2,
+                       const int32_t* ispin2, const std::string& who, PairsTables& tab) {
+  if (nterms < 1 || nterms > kPairsMaxTerms) {
+    set_error(who + ": nterms must be 1 .. " + std::to_string(kPairsMaxTerms));
+    return 1;
+  }
+  return pairs_prepare(src, dst, nullptr, nullptr, pairs_terms(nterms, coef, create1, iorb1, ispin1, create2, iorb2, ispin2), who,
+                       tab);
+}
+
+int pairs_shard_call(const edigpu_sector* src, const PairsTables& tab, const ShardWindow* win, int64_t rows, const double* v_src,
+                     double* v_dst, hipStream_t st) {
+  PairsDevTables dev;
+  PairsArgs a;
+  if (pairs_upload(tab, src->nph + 1, dev, a, st)) return 1;
+  if (win) {
+    if (launch_apply_pairs_window(a, *win, v_src, v_dst, st)) return 1;
+  } else {
+    // no term moves a down electron (every bit of id_dw is set: the down tables are not read): the rank's rows are a
+    // vector of `rows` down rows on both sides
+    a.dd_src = a.dd_dst = rows;
+    if (launch_apply_pairs(a, v_src, v_dst, st)) return 1;
+  }
+  EDIGPU_HIP(hipStreamSynchronize(st));  // the tables are freed only after the kernel has read them
+  return 0;
+}
+
 }  // namespace edigpu
 
 using namespace edigpu;

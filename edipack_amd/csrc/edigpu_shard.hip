@@ -11,6 +11,8 @@
 //   sp_lanc_tridiag(MpiComm, spHtimesV_p, vvloc, alanc, blanc)   ED_NORMAL/ED_HAMILTONIAN_NORMAL.f90:357-365
 //   scatter / gather of the seed: ED_AUX_FUNX.f90:598-928 (each rank hands over its own shard here)
 //
+// (The c / c^+ and pair seeds on shards: edigpu_shard_seeds.hip.)
+//
 // One process per GPU.  The exchange of a product runs on the communicator's side stream and overlaps the part of H*v
 // that needs no remote data.  A whole tridiagonalisation is enqueued without host synchronisation (RCCL) -- the
 // coefficients are read back once at the end.
@@ -27,10 +29,8 @@
 
 namespace edigpu {
 
-int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g) {
-  g.loop = LoopSwitches::sample();
+void shard_rows(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g) {
   g.w = s->is_complex ? 2 : 1;
-  g.transposed = s->kind == kNormal && s->is_whole() && normal_transposable_el(s);
   g.nblk = s->has_phonons() ? s->nph + 1 : 1;
   if (s->kind == kNormal) {
     g.units = s->dim_dw;
@@ -45,6 +45,12 @@ int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g)
   g.blk = g.count * g.unit_len;
   g.nloc = g.blk * g.nblk;
   g.chunk = g.q * g.unit_len * g.nblk;
+}
+
+int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g) {
+  g.loop = LoopSwitches::sample();
+  shard_rows(s, c, g);
+  g.transposed = s->kind == kNormal && s->is_whole() && normal_transposable_el(s);
   if (g.transposed) {
     g.halo = s->col_halo;
     g.pcol = (s->dim_up + c->world - 1) / c->world;
@@ -524,44 +530,6 @@ int edigpu_lanczos_eigh_sharded(edigpu_handle h, edigpu_comm c, int nitermax, do
   const int ncv = std::max(8, std::min(nitermax, 48));
   const int maxrestart = std::max(1, nitermax / std::max(1, ncv / 2));
   return edigpu_lanczos_eigh_multi_sharded(h, c, 1, ncv, tol, maxrestart, v0_shard, eval, evec_shard, &nconv, nmatvec);
-}
-
-int edigpu_apply_cops_sharded(edigpu_handle src, edigpu_handle dst, edigpu_comm c, const double* v_src_shard,
-                              double* v_dst_shard, int nops, const double* coef_re_im, const int32_t* create,
-                              const int32_t* iorb, const int32_t* ispin) {
-  if (!src || !dst || !c || nops <= 0 || !coef_re_im || !create || !iorb || !ispin) {
-    set_error("edigpu_apply_cops_sharded: bad argument");
-    return 1;
-  }
-  if (src->kind == kCmplxNormal || dst->kind == kCmplxNormal || src->has_phonons() || dst->has_phonons()) {
-    set_error("edigpu_apply_cops_sharded: complex normal-mode and phonon sectors are not supported");
-    return 1;
-  }
-  ShardGeom gs, gd;
-  if (shard_geometry(src, c, gs) || shard_geometry(dst, c, gd)) return 1;
-  EDIGPU_HIP(hipSetDevice(src->device));
-  hipStream_t st = src->stream;
-  const size_t chunk = (size_t)std::max<int64_t>(gs.chunk * gs.w, 1), nsrc = (size_t)(gs.nloc * gs.w);  // (as zero_chunk)
-  const size_t ndst = (size_t)(gd.nloc * gd.w);
-  if ((nsrc && !v_src_shard) || (ndst && !v_dst_shard)) {
-    set_error("edigpu_apply_cops_sharded: NULL vector");
-    return 1;
-  }
-  struct Bufs {
-    double *send = nullptr, *full = nullptr, *out = nullptr;
-    ~Bufs() { dev_free_all(send, full, out); }
-  } b;
-  if (dev_alloc(&b.send, chunk) || dev_alloc(&b.full, chunk * (size_t)c->world) || dev_alloc(&b.out, ndst)) return 1;
-  if (zero_chunk(b.send, gs, st)) return 1;
-  if (nsrc) EDIGPU_HIP(hipMemcpyAsync(b.send, v_src_shard, nsrc * sizeof(double), hipMemcpyDefault, st));
-  // equal padded chunks in rank order = the whole source vector in the reference's layout (+ a tail nobody reads)
-  if (comm_all_gather(c, b.send, b.full, chunk, st)) return 1;
-  if (ndst && apply_cops_rows(src, dst, b.full, b.out, gd.first, gd.count, nops, coef_re_im, create, iorb, ispin, st,
-                              "edigpu_apply_cops_sharded"))
-    return 1;
-  if (ndst) EDIGPU_HIP(hipMemcpyAsync(v_dst_shard, b.out, ndst * sizeof(double), hipMemcpyDefault, st));
-  EDIGPU_HIP(hipStreamSynchronize(st));
-  return 0;
 }
 
 // bench.py --gpus N: what the transport itself reports and costs.  *rccl_ranks = ncclCommCount of the communicator (0:

@@ -43,15 +43,6 @@ int obs_geometry(edigpu_sector* s, edigpu_comm_s* c, const std::string& who, boo
   return 0;
 }
 
-bool on_device(const void* p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();  // (a plain host pointer, on runtimes that do not know "unregistered")
-    return false;
-  }
-  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 // the vector the kernels read: v itself when it lives on the device, else its copy in the communicator's buffer at
 // `offset` doubles (the buffer holds at least `cap` doubles after this)
 int stage_in(edigpu_comm_s* c, const double* v, int64_t n, int64_t offset, int64_t cap, hipStream_t st, const double** out) {

@@ -208,7 +208,8 @@ int launch_phonon_rows(const edigpu_sector* s, int64_t dw_first, int64_t dw_coun
 int launch_apply_op_flat(int64_t ndst, int ns, uint32_t bit, int create, const int32_t* dst_states,
                          const int32_t* src_offdw, const int32_t* src_rkup, const double* src, double* dst,
                          hipStream_t st, double cre = 1.0, double cim = 0.0, int accumulate = 0, int nblk = 1,
-                         int64_t nsrc = 0);  // nblk > 1: phonon blocks of ndst (destination) / nsrc (source) elements
+                         int64_t nsrc = 0,  // nblk > 1: phonon blocks of ndst (destination) / nsrc (source) elements
+                         const ShardSrc* gathered = nullptr);  // src = the all-gathered shards, counted in double2 (nsrc unused)
 
 // ---- ed_total_ud = F sectors (kernels_orbs.hip) ----
 int launch_orbs(const edigpu_sector* s, const double* v, double* hv, hipStream_t st);
@@ -291,6 +292,9 @@ struct PairsArgs {
 // dst[p][jdw][jup] = sum_t coef_t s_t src[p][pd_t(jdw)][pu_t(jup)], acc = 0 then acc = fma(coef_t, +-x_t, acc) for t
 // ascending; every element of dst is written once; enqueued on st, no synchronisation; dst must not overlap src
 int launch_apply_pairs(const PairsArgs& a, const double* src, double* dst, hipStream_t st);
+// the window + source form (shard_src.hpp ShardWindow): dst = the down rows [w.j_first, w.j_first + w.j_count) of every block,
+// src = the all-gathered shards (w.s.unit_len = du_src); the same arithmetic in the same order, element by element
+int launch_apply_pairs_window(const PairsArgs& a, const ShardWindow& w, const double* src, double* dst, hipStream_t st);
 
 // ---- c / c^+ along one axis of a vector [O][A][I] (kernels_axisop.hip; tables: host_axisop.hpp) ----
 // the device copy of an AxisTables (part[nterms][a_dst]) and the coefficients; I in doubles
@@ -304,6 +308,10 @@ struct AxisArgs {
 // are double2 and the coefficients complex (I even), else cim is not read; every element of dst is written once; enqueued
 // on st, no synchronisation; dst must not overlap src
 int launch_apply_axisop(const AxisArgs& a, int cplx_coef, const double* src, double* dst, hipStream_t st);
+// the window + source form (shard_src.hpp ShardWindow): dst = the indices [w.j_first, w.j_first + w.j_count) of axis A in every
+// o, src = the all-gathered shards (a.O = w.s.nblk, w.s.unit_len = a.I, in doubles); the same arithmetic, element by element
+int launch_apply_axisop_window(const AxisArgs& a, const ShardWindow& w, int cplx_coef, const double* src, double* dst,
+                               hipStream_t st);
 
 // ---- impurity reduced density matrix (kernels_rdm.hip; tables and work list: host_rdm.hpp) ----
 struct RdmArgs {  // the device copies of an RdmPlan

@@ -23,6 +23,13 @@
 //       consecutive elements), so that four table reads and then four source reads are in flight; the element index is
 //       split with 32-bit divisions where the vector has fewer than 2^31 elements.
 // Both: capped grid, no LDS, no atomics; every element of dst is written once and never read, src is only read.
+//
+// Each kernel has two forms, chosen by the policy Win (shard_src.hpp).  WholeVector: the vectors above (what the single-GPU
+// calls launch; `if constexpr` leaves its code as it was).  ShardWindow (edigpu_apply_cops_sharded): the destination holds
+// the indices [j_first, j_first + j_count) of axis A only, dst[o][j - j_first][i], the partner table is still indexed by
+// the global j, and the source row of (o, part_t(j)) is found through shard_src_offset in the all-gathered shards.  In the
+// rows kernel that offset is computed on scalars, once per (unit, term), next to the readfirstlane of the partner; in the
+// gather kernel per lane.  Arithmetic and term order are the same in both forms.
 #include "kernels.hpp"
 
 namespace edigpu {
@@ -57,18 +64,23 @@ struct CplxAlg {
 };
 
 // a.I is counted in elements of Alg::T here (launch_apply_axisop halves it for double2)
-template <class Alg>
-__global__ __launch_bounds__(kAxisBlock) void axisop_rows_kernel(AxisArgs a, const typename Alg::T* __restrict__ src,
+template <class Alg, class Win>
+__global__ __launch_bounds__(kAxisBlock) void axisop_rows_kernel(AxisArgs a, Win w, const typename Alg::T* __restrict__ src,
                                                                  typename Alg::T* __restrict__ dst) {
   using T = typename Alg::T;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   constexpr int kWaves = kAxisBlock / 64;
   const int64_t nchunks = (a.I + kAxisChunk - 1) / kAxisChunk;
-  const int64_t nunits = a.O * a.a_dst * nchunks;
+  int64_t na = a.a_dst, j0 = 0;  // destination rows per o, the first of them
+  if constexpr (Win::kWindow) {
+    na = w.j_count;
+    j0 = w.j_first;
+  }
+  const int64_t nunits = a.O * na * nchunks;
   for (int64_t u = (int64_t)blockIdx.x * kWaves + wave; u < nunits; u += (int64_t)gridDim.x * kWaves) {
     const int64_t row = u / nchunks, c0 = (u - row * nchunks) * kAxisChunk;
-    const int64_t o = row / a.a_dst, j = row - o * a.a_dst;
+    const int64_t o = row / na, j = row - o * na + j0;
     T acc[kAxisPer];
     for (int t = 0; t < a.nterms; t++) {
       // the partner of (o, j) under term t: the same for every lane
@@ -77,7 +89,9 @@ __global__ __launch_bounds__(kAxisBlock) void axisop_rows_kernel(AxisArgs a, con
 #pragma unroll
       for (int c = 0; c < kAxisPer; c++) x[c] = Alg::zero();
       if (p != kNone) {
-        const T* srow = src + (o * a.a_src + (int64_t)(p & kIdx)) * a.I;
+        const T* srow;
+        if constexpr (Win::kWindow) srow = src + shard_src_offset(w.s, o, (int64_t)(p & kIdx));  // (wave-uniform)
+        else srow = src + (o * a.a_src + (int64_t)(p & kIdx)) * a.I;
 #pragma unroll
         for (int c = 0; c < kAxisPer; c++) {  // the loads of a term are independent
           const int64_t i = c0 + lane + 64 * c;
@@ -102,17 +116,23 @@ __global__ __launch_bounds__(kAxisBlock) void axisop_rows_kernel(AxisArgs a, con
 
 // Ix: the type the element index is split in.  The two divisions per element are what this kernel spends its
 // instructions on, so vectors of fewer than 2^31 elements take them in 32 bits; the addresses are 64-bit either way.
-template <class Alg, class Ix>
-__global__ __launch_bounds__(kAxisBlock) void axisop_gather_kernel(AxisArgs a, const typename Alg::T* __restrict__ src,
+template <class Alg, class Ix, class Win>
+__global__ __launch_bounds__(kAxisBlock) void axisop_gather_kernel(AxisArgs a, Win w, const typename Alg::T* __restrict__ src,
                                                                    typename Alg::T* __restrict__ dst) {
   using T = typename Alg::T;
-  const Ix nI = (Ix)a.I, na = (Ix)a.a_dst;
-  const Ix nel = (Ix)(a.O * a.a_dst * a.I), step = (Ix)gridDim.x * kAxisBlock;
+  Ix na = (Ix)a.a_dst, j0 = 0;  // destination rows per o, the first of them
+  if constexpr (Win::kWindow) {
+    na = (Ix)w.j_count;
+    j0 = (Ix)w.j_first;
+  }
+  const Ix nI = (Ix)a.I;
+  const Ix nel = (Ix)(a.O * (int64_t)na * a.I), step = (Ix)gridDim.x * kAxisBlock;
   // kAxisBatch elements per lane and pass, a grid apart: the table reads of a batch are in flight together, then its
   // source reads (each element is two dependent loads; one element per pass leaves the memory system waiting)
   for (Ix e0 = (Ix)blockIdx.x * kAxisBlock + threadIdx.x; e0 < nel; e0 += kAxisBatch * step) {
     Ix j[kAxisBatch];
-    int64_t base[kAxisBatch];  // offset of (o, row 0, i) in src
+    int64_t base[kAxisBatch];  // offset of (o, row 0, i) in src; window form: i, with the block o kept beside it
+    [[maybe_unused]] int64_t blk[kAxisBatch];
     bool in[kAxisBatch];
     T acc[kAxisBatch];
 #pragma unroll
@@ -121,8 +141,13 @@ __global__ __launch_bounds__(kAxisBlock) void axisop_gather_kernel(AxisArgs a, c
       in[b] = e < nel;
       const Ix row = e / nI, i = e - row * nI;
       const Ix o = row / na;
-      j[b] = row - o * na;
-      base[b] = (int64_t)o * a.a_src * a.I + (int64_t)i;
+      j[b] = row - o * na + j0;
+      if constexpr (Win::kWindow) {
+        base[b] = (int64_t)i;
+        blk[b] = (int64_t)o;
+      } else {
+        base[b] = (int64_t)o * a.a_src * a.I + (int64_t)i;
+      }
     }
     for (int t = 0; t < a.nterms; t++) {
       uint32_t p[kAxisBatch];
@@ -132,7 +157,10 @@ __global__ __launch_bounds__(kAxisBlock) void axisop_gather_kernel(AxisArgs a, c
 #pragma unroll
       for (int b = 0; b < kAxisBatch; b++) {
         x[b] = Alg::zero();
-        if (p[b] != kNone) x[b] = src[base[b] + (int64_t)(p[b] & kIdx) * a.I];
+        if (p[b] != kNone) {
+          if constexpr (Win::kWindow) x[b] = src[shard_src_offset(w.s, blk[b], (int64_t)(p[b] & kIdx)) + base[b]];
+          else x[b] = src[base[b] + (int64_t)(p[b] & kIdx) * a.I];
+        }
       }
 #pragma unroll
       for (int b = 0; b < kAxisBatch; b++) {
@@ -146,21 +174,23 @@ __global__ __launch_bounds__(kAxisBlock) void axisop_gather_kernel(AxisArgs a, c
   }
 }
 
-template <class Alg>
-void axisop_launch(const AxisArgs& a, bool rows, const double* src, double* dst, hipStream_t st) {
+template <class Alg, class Win>
+void axisop_launch(const AxisArgs& a, const Win& w, bool rows, const double* src, double* dst, hipStream_t st) {
   using T = typename Alg::T;
-  const int64_t nrows = a.O * a.a_dst, nel = nrows * a.I;
+  int64_t na = a.a_dst;
+  if constexpr (Win::kWindow) na = w.j_count;
+  const int64_t nrows = a.O * na, nel = nrows * a.I;
   if (rows) {
     const int64_t nunits = nrows * ((a.I + kAxisChunk - 1) / kAxisChunk), per = kAxisBlock / 64;
     const unsigned grid = (unsigned)std::min<int64_t>((nunits + per - 1) / per, kAxisMaxBlocks);
-    axisop_rows_kernel<Alg><<<grid, kAxisBlock, 0, st>>>(a, reinterpret_cast<const T*>(src), reinterpret_cast<T*>(dst));
+    axisop_rows_kernel<Alg, Win><<<grid, kAxisBlock, 0, st>>>(a, w, reinterpret_cast<const T*>(src), reinterpret_cast<T*>(dst));
   } else {
     const int64_t per = (int64_t)kAxisBlock * kAxisBatch;
     const unsigned grid = (unsigned)std::min<int64_t>((nel + per - 1) / per, kAxisMaxBlocks);
     if (nel < ((int64_t)1 << 31))  // a pass adds at most 4 * 2^18 to an index below 2^31: no wrap in 32 bits
-      axisop_gather_kernel<Alg, uint32_t><<<grid, kAxisBlock, 0, st>>>(a, reinterpret_cast<const T*>(src), reinterpret_cast<T*>(dst));
+      axisop_gather_kernel<Alg, uint32_t, Win><<<grid, kAxisBlock, 0, st>>>(a, w, reinterpret_cast<const T*>(src), reinterpret_cast<T*>(dst));
     else
-      axisop_gather_kernel<Alg, int64_t><<<grid, kAxisBlock, 0, st>>>(a, reinterpret_cast<const T*>(src), reinterpret_cast<T*>(dst));
+      axisop_gather_kernel<Alg, int64_t, Win><<<grid, kAxisBlock, 0, st>>>(a, w, reinterpret_cast<const T*>(src), reinterpret_cast<T*>(dst));
   }
 }
 
@@ -176,9 +206,34 @@ int launch_apply_axisop(const AxisArgs& args, int cplx_coef, const double* src, 
   if (cplx_coef) {
     AxisArgs a = args;
     a.I /= 2;
-    axisop_launch<CplxAlg>(a, rows, src, dst, st);
+    axisop_launch<CplxAlg>(a, WholeVector(), rows, src, dst, st);
   } else {
-    axisop_launch<RealAlg>(args, rows, src, dst, st);
+    axisop_launch<RealAlg>(args, WholeVector(), rows, src, dst, st);
+  }
+  EDIGPU_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_apply_axisop_window(const AxisArgs& args, const ShardWindow& win, int cplx_coef, const double* src, double* dst,
+                               hipStream_t st) {
+  if (args.O * win.j_count * args.I <= 0) return 0;
+  const ShardSrc& s = win.s;
+  // every source row the tables can name lies inside the gathered vector, every destination row inside the axis
+  if (args.nterms < 1 || args.nterms > 8 || (cplx_coef && ((args.I | s.chunk) & 1)) || win.j_first < 0 ||
+      win.j_first + win.j_count > args.a_dst || s.nblk != args.O || s.unit_len != args.I || s.units != args.a_src || s.q < 1 ||
+      s.chunk != s.q * s.unit_len * s.nblk) {
+    set_error("launch_apply_axisop_window: bad argument");
+    return 1;
+  }
+  const bool rows = args.I >= 64;  // in doubles, whichever the element type
+  if (cplx_coef) {
+    AxisArgs a = args;
+    a.I /= 2;
+    ShardWindow w = win;
+    w.s = shard_src_in_pairs(s);
+    axisop_launch<CplxAlg>(a, w, rows, src, dst, st);
+  } else {
+    axisop_launch<RealAlg>(args, win, rows, src, dst, st);
   }
   EDIGPU_HIP(hipGetLastError());
   return 0;

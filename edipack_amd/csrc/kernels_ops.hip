@@ -35,9 +35,12 @@ __global__ void __launch_bounds__(256)
 
 // flat (superc / nonsu2) sectors: one map over the 2*Ns-bit states; the sign counts every occupied level
 // below the operator's level (ED_AUX_FUNX.f90:334-384), complex vectors.  Phonon sectors: the same map in each of the nblk
-// electronic blocks, dst[p * ndst + j] <- src[p * nsrc + i], one launch for all blocks
+// electronic blocks, dst[p * ndst + j] <- src[p * nsrc + i], one launch for all blocks.  Win (shard_src.hpp): WholeVector =
+// that; ShardWindow (phonon row shards, edigpu_apply_cops_sharded) = dst_states are the ndst rows of a rank, and element i
+// of block p of the source is found through shard_src_offset in the all-gathered shards (unit_len = 1 double2)
+template <class Win>
 __global__ void __launch_bounds__(256)
-    apply_op_flat_kernel(int64_t ndst, int64_t nsrc, int nblk, int ns, uint32_t bit, int create,
+    apply_op_flat_kernel(int64_t ndst, int64_t nsrc, int nblk, int ns, uint32_t bit, int create, Win w,
                          const int32_t* __restrict__ dst_states, const int32_t* __restrict__ src_offdw,
                          const int32_t* __restrict__ src_rkup, const double2* __restrict__ src, double2* __restrict__ dst,
                          double cre, double cim, int accumulate) {
@@ -50,7 +53,8 @@ __global__ void __launch_bounds__(256)
     if (create ? (t & bit) != 0u : (t & bit) == 0u) {
       const uint32_t sst = t ^ bit;
       const int64_t i = (int64_t)src_offdw[sst >> ns] + src_rkup[sst & lomask];
-      x = src[p * nsrc + i];
+      if constexpr (Win::kWindow) x = src[shard_src_offset(w.s, p, i)];
+      else x = src[p * nsrc + i];
       if (__popc(sst & (bit - 1u)) & 1) {
         x.x = -x.x;
         x.y = -x.y;
@@ -69,12 +73,28 @@ __global__ void __launch_bounds__(256)
 
 int launch_apply_op_flat(int64_t ndst, int ns, uint32_t bit, int create, const int32_t* dst_states,
                          const int32_t* src_offdw, const int32_t* src_rkup, const double* src, double* dst,
-                         hipStream_t st, double cre, double cim, int accumulate, int nblk, int64_t nsrc) {
+                         hipStream_t st, double cre, double cim, int accumulate, int nblk, int64_t nsrc,
+                         const ShardSrc* gathered) {
   if (ndst == 0 || nblk <= 0) return 0;
   int64_t nb = (ndst * nblk + 255) / 256;
   if (nb > 256 * 16) nb = 256 * 16;
-  hipLaunchKernelGGL(apply_op_flat_kernel, dim3((unsigned)nb), dim3(256), 0, st, ndst, nsrc, nblk, ns, bit, create, dst_states,
-                     src_offdw, src_rkup, reinterpret_cast<const double2*>(src), reinterpret_cast<double2*>(dst), cre, cim, accumulate);
+  if (gathered) {
+    const ShardSrc& s = *gathered;
+    if (s.nblk != nblk || s.unit_len != 1 || s.q < 1 || s.units != nsrc || s.chunk != s.q * s.nblk) {
+      set_error("launch_apply_op_flat: bad argument");
+      return 1;
+    }
+    ShardWindow w;
+    w.j_count = ndst;
+    w.s = s;
+    hipLaunchKernelGGL(apply_op_flat_kernel<ShardWindow>, dim3((unsigned)nb), dim3(256), 0, st, ndst, nsrc, nblk, ns, bit, create,
+                       w, dst_states, src_offdw, src_rkup, reinterpret_cast<const double2*>(src), reinterpret_cast<double2*>(dst),
+                       cre, cim, accumulate);
+  } else {
+    hipLaunchKernelGGL(apply_op_flat_kernel<WholeVector>, dim3((unsigned)nb), dim3(256), 0, st, ndst, nsrc, nblk, ns, bit, create,
+                       WholeVector(), dst_states, src_offdw, src_rkup, reinterpret_cast<const double2*>(src),
+                       reinterpret_cast<double2*>(dst), cre, cim, accumulate);
+  }
   EDIGPU_HIP(hipGetLastError());
   return 0;
 }

@@ -25,16 +25,26 @@ constexpr int kPairsChunk = 64 * kPairsCols;       // columns of a unit
 constexpr int kPairsMaxBlocks = 1024;              // 16 waves per CU on 256 CUs; the rest is grid-stride
 constexpr uint32_t kNone = 0xFFFFFFFFu, kIdx = 0x7FFFFFFFu;
 
-__global__ __launch_bounds__(kPairsBlock) void pairs_rows_kernel(PairsArgs a, const double* __restrict__ src,
+// Win (shard_src.hpp): WholeVector = the vectors above; ShardWindow (edigpu_apply_pairs_sharded) = the destination holds
+// the down rows [j_first, j_first + j_count) of every block, the down tables are indexed by the global row and the source
+// row pd_t(jdw) of block p is found through shard_src_offset in the all-gathered shards (on scalars in the rows kernel,
+// per lane in the flat kernel).  The up tables, the arithmetic and the term order are the same in both forms.
+template <class Win>
+__global__ __launch_bounds__(kPairsBlock) void pairs_rows_kernel(PairsArgs a, Win w, const double* __restrict__ src,
                                                                  double* __restrict__ dst) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   constexpr int kWaves = kPairsBlock / 64;
   const int64_t nchunks = (a.du_dst + kPairsChunk - 1) / kPairsChunk;
-  const int64_t nunits = a.dd_dst * a.nblk * nchunks;
+  int64_t nd = a.dd_dst, j0 = 0;  // destination rows per block, the first of them
+  if constexpr (Win::kWindow) {
+    nd = w.j_count;
+    j0 = w.j_first;
+  }
+  const int64_t nunits = nd * a.nblk * nchunks;
   for (int64_t u = (int64_t)blockIdx.x * kWaves + wave; u < nunits; u += (int64_t)gridDim.x * kWaves) {
     const int64_t row = u / nchunks, c0 = (u - row * nchunks) * kPairsChunk;
-    const int64_t blk = row / a.dd_dst, jdw = row - blk * a.dd_dst;
+    const int64_t blk = row / nd, jdw = row - blk * nd + j0;
     double acc[kPairsCols];
 #pragma unroll
     for (int c = 0; c < kPairsCols; c++) acc[c] = 0.0;
@@ -42,7 +52,9 @@ __global__ __launch_bounds__(kPairsBlock) void pairs_rows_kernel(PairsArgs a, co
       // the row's down partner under term t: the same for every lane
       const uint32_t pd = ((a.id_dw >> t) & 1u) ? (uint32_t)jdw : __builtin_amdgcn_readfirstlane(a.pd[t * a.dd_dst + jdw]);
       if (pd == kNone) continue;
-      const double* srow = src + (blk * a.dd_src + (int64_t)(pd & kIdx)) * a.du_src;
+      const double* srow;
+      if constexpr (Win::kWindow) srow = src + shard_src_offset(w.s, blk, (int64_t)(pd & kIdx));  // (wave-uniform)
+      else srow = src + (blk * a.dd_src + (int64_t)(pd & kIdx)) * a.du_src;
       const bool id_up = (a.id_up >> t) & 1u;
       const uint32_t* put = a.pu + t * a.du_dst;
       const double coef = a.coef[t];
@@ -74,39 +86,66 @@ __global__ __launch_bounds__(kPairsBlock) void pairs_rows_kernel(PairsArgs a, co
   }
 }
 
-__global__ __launch_bounds__(kPairsBlock) void pairs_flat_kernel(PairsArgs a, const double* __restrict__ src,
+template <class Win>
+__global__ __launch_bounds__(kPairsBlock) void pairs_flat_kernel(PairsArgs a, Win w, const double* __restrict__ src,
                                                                  double* __restrict__ dst) {
-  const int64_t nel = a.du_dst * a.dd_dst * a.nblk;
+  int64_t nd = a.dd_dst, j0 = 0;  // destination rows per block, the first of them
+  if constexpr (Win::kWindow) {
+    nd = w.j_count;
+    j0 = w.j_first;
+  }
+  const int64_t nel = a.du_dst * nd * a.nblk;
   for (int64_t e = (int64_t)blockIdx.x * kPairsBlock + threadIdx.x; e < nel; e += (int64_t)gridDim.x * kPairsBlock) {
     const int64_t row = e / a.du_dst, j = e - row * a.du_dst;
-    const int64_t blk = row / a.dd_dst, jdw = row - blk * a.dd_dst;
+    const int64_t blk = row / nd, jdw = row - blk * nd + j0;
     double acc = 0.0;
     for (int t = 0; t < a.nterms; t++) {
       const uint32_t pd = ((a.id_dw >> t) & 1u) ? (uint32_t)jdw : a.pd[t * a.dd_dst + jdw];
       const uint32_t pu = ((a.id_up >> t) & 1u) ? (uint32_t)j : a.pu[t * a.du_dst + j];
       if (pd == kNone || pu == kNone) continue;
-      const double y = src[(blk * a.dd_src + (int64_t)(pd & kIdx)) * a.du_src + (int64_t)(pu & kIdx)];
+      int64_t srow;
+      if constexpr (Win::kWindow) srow = shard_src_offset(w.s, blk, (int64_t)(pd & kIdx));
+      else srow = (blk * a.dd_src + (int64_t)(pd & kIdx)) * a.du_src;
+      const double y = src[srow + (int64_t)(pu & kIdx)];
       acc = __builtin_fma(a.coef[t], ((pu ^ pd) >> 31) ? -y : y, acc);
     }
     dst[e] = acc;
   }
 }
 
-}  // namespace
-
-int launch_apply_pairs(const PairsArgs& a, const double* src, double* dst, hipStream_t st) {
-  const int64_t nrows = a.dd_dst * a.nblk, nel = nrows * a.du_dst;
+template <class Win>
+int pairs_launch(const PairsArgs& a, const Win& w, const double* src, double* dst, hipStream_t st) {
+  int64_t nd = a.dd_dst;
+  if constexpr (Win::kWindow) nd = w.j_count;
+  const int64_t nrows = nd * a.nblk, nel = nrows * a.du_dst;
   if (nel <= 0) return 0;
   if (a.du_dst >= 64) {
     const int64_t nunits = nrows * ((a.du_dst + kPairsChunk - 1) / kPairsChunk), per = kPairsBlock / 64;
     const unsigned grid = (unsigned)std::min<int64_t>((nunits + per - 1) / per, kPairsMaxBlocks);
-    pairs_rows_kernel<<<grid, kPairsBlock, 0, st>>>(a, src, dst);
+    pairs_rows_kernel<Win><<<grid, kPairsBlock, 0, st>>>(a, w, src, dst);
   } else {
     const unsigned grid = (unsigned)std::min<int64_t>((nel + kPairsBlock - 1) / kPairsBlock, kPairsMaxBlocks);
-    pairs_flat_kernel<<<grid, kPairsBlock, 0, st>>>(a, src, dst);
+    pairs_flat_kernel<Win><<<grid, kPairsBlock, 0, st>>>(a, w, src, dst);
   }
   EDIGPU_HIP(hipGetLastError());
   return 0;
+}
+
+}  // namespace
+
+int launch_apply_pairs(const PairsArgs& a, const double* src, double* dst, hipStream_t st) {
+  return pairs_launch(a, WholeVector(), src, dst, st);
+}
+
+int launch_apply_pairs_window(const PairsArgs& a, const ShardWindow& w, const double* src, double* dst, hipStream_t st) {
+  const ShardSrc& s = w.s;
+  // every source row the tables can name lies inside the gathered vector, every destination row inside the sector
+  if (w.j_first < 0 || w.j_count < 0 || w.j_first + w.j_count > a.dd_dst || s.nblk != a.nblk || s.unit_len != a.du_src ||
+      s.units != a.dd_src || s.q < 1 || s.chunk != s.q * s.unit_len * s.nblk) {
+    set_error("launch_apply_pairs_window: bad argument");
+    return 1;
+  }
+  return pairs_launch(a, w, src, dst, st);
 }
 
 }  // namespace edigpu

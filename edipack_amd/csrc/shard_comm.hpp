@@ -1,6 +1,6 @@
 // shard_comm.hpp -- what the communicator (edigpu_comm.hip) and the sharded product and recurrence (edigpu_shard.hip)
-// share with the observables on shards (edigpu_shard_obs.hip): the communicator's state, its three collectives and two
-// predicates, the geometry of a shard.  Not part of the ABI.
+// share with the observables and the seeds on shards (edigpu_shard_obs.hip, edigpu_shard_seeds.hip): the communicator's
+// state, its three collectives and two predicates, the geometry of a shard.  Not part of the ABI.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -30,9 +30,13 @@ struct ShardWorkspace {
   // impurity reduced density matrix on shards: the halo rows this rank sends, the halos of all ranks, the boundary slab
   double *halo = nullptr, *halos = nullptr, *slab = nullptr;
   int64_t halo_cap = 0, halos_cap = 0, slab_cap = 0;
+  // c / c^+ and pair seeds on shards (edigpu_shard_seeds.hip): the padded chunk this rank sends, the gathered source, and
+  // the staging of host vectors (source and destination shard)
+  double *seed_send = nullptr, *seed_full = nullptr, *seed_io = nullptr;
+  int64_t seed_send_cap = 0, seed_full_cap = 0, seed_io_cap = 0;
   void release() {  // (with the communicator's device current)
     dev_free_all(vin, vout, tmp, vfull, send, recv, hvc, back, hist, work, scr, bp[0], bp[1], bp[2], bp[3], bp[4], obs, red, halo,
-                 halos, slab);
+                 halos, slab, seed_send, seed_full, seed_io);
   }
   ~ShardWorkspace() { release(); }
 };
@@ -69,6 +73,15 @@ inline bool force_collectives(const edigpu_comm_s* c) {
 }
 // nobody to exchange with: a collective is at most a local copy, and a product needs no side stream
 inline bool alone(const edigpu_comm_s* c) { return c->world == 1 && !force_collectives(c); }
+// whether p is device (or managed) memory; a plain host pointer is not
+inline bool on_device(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // (a plain host pointer, on runtimes that do not know "unregistered")
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
 // _CMPLX_NORMAL held as one real sector on the doubled up index: its down rows shard like any real sector's (each row
 // 2 DimUp doubles = DimUp complex elements), so every sharded call on a complex sector runs on that image
 inline edigpu_sector* real_image(edigpu_sector* s) { return s->kind == kCmplxNormal && s->sub_d ? s->sub_d : s; }
@@ -95,6 +108,9 @@ struct ShardGeom {
 // g <- the geometry of handle s on communicator c, 0; or 1 with the message set: the handle is not this rank's shard, a
 // phonon sector with a general g_ph(a,b), a four-product complex sector.  Complex normal-mode handles: pass real_image(s).
 int shard_geometry(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g);
+// its first part, which cannot fail: how the rows are cut (w, nblk, units, unit_len, q, first, count, blk, nloc, chunk) and
+// nothing of the product's exchange -- all that the seeds on shards need (edigpu_shard_seeds.hip)
+void shard_rows(const edigpu_sector* s, const edigpu_comm_s* c, ShardGeom& g);
 
 // The collectives (edigpu_comm.hip), each enqueued: on the communicator's own stream, bracketed by events so that it
 // runs after what `caller` holds so far and `caller` goes on after it; a caller that passes c->side places its own events.

@@ -160,21 +160,67 @@ class LibraryComm:
             self._capi.pd(e), x.ctypes.data_as(C.c_void_p) if x.size else None, C.byref(nm)), "edigpu_lanczos_eigh_sharded")
         return e[0], x, nm.value
 
-    def apply_cops(self, src, dst, v_src_shard, nloc_dst: int, ops):
-        """apply_Cops on shards: ops = [(coef, create, iorb, ispin)]; returns this rank's shard of the destination."""
+    # ---- c / c^+ and pair seeds on shards (csrc/edigpu_shard_seeds.hip) ------------------------------------------
+    @staticmethod
+    def _cops_args(ops):
         import ctypes as C
-        import numpy as np
-        v = np.ascontiguousarray(v_src_shard, dtype=src.dtype)
-        out = np.zeros(nloc_dst, dtype=dst.dtype)
         n = len(ops)
         a = (C.c_double * (2 * n))(*[x for o in ops for x in (complex(o[0]).real, complex(o[0]).imag)])
         cr = (C.c_int32 * n)(*[1 if o[1] else -1 for o in ops])
         io = (C.c_int32 * n)(*[int(o[2]) for o in ops])
         sp = (C.c_int32 * n)(*[int(o[3]) for o in ops])
-        self._capi.check(self._capi.lib().edigpu_apply_cops_sharded(
-            src._h, dst._h, self._c, v.ctypes.data_as(C.c_void_p) if v.size else None,
-            out.ctypes.data_as(C.c_void_p) if out.size else None, n, a, cr, io, sp), "edigpu_apply_cops_sharded")
-        return out
+        return n, a, cr, io, sp
+
+    def _seed_call(self, fn, name, src, dst, v_src_shard, nloc_dst, args, out):
+        """The source as a numpy shard (the seed is returned as a new array of nloc_dst elements of dst's dtype) or a
+        device pointer (`out`, a device pointer that does not overlap it, receives the seed; None is returned)."""
+        import ctypes as C
+        import numpy as np
+        p_src, keep = self._shard_ptr(src, v_src_shard)
+        if keep is None and not out and nloc_dst:
+            raise ValueError(f"{name}: a device shard needs `out` (the seed cannot overwrite its source)")
+        res = None if keep is None else np.zeros(nloc_dst, dtype=dst.dtype)
+        if keep is None:
+            p_dst = C.c_void_p(int(out)) if out else None
+        else:
+            p_dst = res.ctypes.data_as(C.c_void_p) if res.size else None
+        self._capi.check(fn(src._h, dst._h, self._c, p_src, p_dst, *args), name)
+        return res
+
+    def apply_cops(self, src, dst, v_src_shard, nloc_dst: int, ops, out=None):
+        """apply_Cops on shards: ops = [(coef, create, iorb, ispin)]; returns this rank's shard of the destination
+        (nloc_dst elements; 0 on a rank that owns no destination row).  Real and complex (normal_cmplx_from_model) normal-mode
+        sectors, phonon sectors included, as whole-sector handles; superc / nonsu2 row shards.  Collective; up operators of
+        phonon and complex normal-mode sectors exchange nothing (apply_cops_info)."""
+        return self._seed_call(self._capi.lib().edigpu_apply_cops_sharded, "edigpu_apply_cops_sharded", src, dst, v_src_shard,
+                               nloc_dst, self._cops_args(ops), out)
+
+    def apply_cops_info(self, src, dst, ops):
+        """(route: 0 local / 1 all-gather, doubles this rank contributes to the all-gather) of apply_cops with these
+        handles and operators; the same checks, host only."""
+        import ctypes as C
+        info = (C.c_int64 * 2)()
+        self._capi.check(self._capi.lib().edigpu_apply_cops_sharded_info(src._h, dst._h, self._c, *self._cops_args(ops), info),
+                         "edigpu_apply_cops_sharded_info")
+        return int(info[0]), int(info[1])
+
+    def apply_pairs(self, src, dst, v_shard, nloc_dst: int, terms, out=None):
+        """SectorHamiltonian.apply_pairs_to on shards: |dst> = sum_t coef_t O2_t O1_t |src> with the term lists of
+        edipack_amd.observables.pair_chi_seeds / exct_chi_seeds; returns this rank's shard of the destination.  Whole
+        real normal-mode handles (phonon sectors included), dst may be src.  Collective; term lists without a down
+        operator exchange nothing (apply_pairs_info)."""
+        from .hamiltonian import _pairs_args
+        return self._seed_call(self._capi.lib().edigpu_apply_pairs_sharded, "edigpu_apply_pairs_sharded", src, dst, v_shard,
+                               nloc_dst, _pairs_args(terms), out)
+
+    def apply_pairs_info(self, src, dst, terms):
+        """(route, doubles contributed to the all-gather) of apply_pairs; the same checks, host only."""
+        import ctypes as C
+        from .hamiltonian import _pairs_args
+        info = (C.c_int64 * 2)()
+        self._capi.check(self._capi.lib().edigpu_apply_pairs_sharded_info(src._h, dst._h, self._c, *_pairs_args(terms), info),
+                         "edigpu_apply_pairs_sharded_info")
+        return int(info[0]), int(info[1])
 
     # ---- occupation and phonon observables, impurity density matrix on shards (csrc/edigpu_shard_obs.hip) -----
     # A shard is a numpy array of this rank's elements (several vectors: [nvec, nloc]) or an int, the address of

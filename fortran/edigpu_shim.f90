@@ -436,6 +436,15 @@ module EDIGPU_SHIM
        integer(c_int32_t), intent(in) :: create(*), iorb(*), ispin(*)
        integer(c_int) :: ierr
      end function edigpu_apply_cops_sharded
+     function edigpu_apply_pairs_sharded(src, dst, c, v_src, v_dst, nterms, coef, create1, iorb1, ispin1, create2, iorb2, &
+          ispin2) bind(C, name="edigpu_apply_pairs_sharded") result(ierr)
+       import :: c_ptr, c_int, c_int32_t, c_double
+       type(c_ptr), value :: src, dst, c, v_src, v_dst
+       integer(c_int), value :: nterms
+       real(c_double), intent(in) :: coef(*)
+       integer(c_int32_t), intent(in) :: create1(*), iorb1(*), ispin1(*), create2(*), iorb2(*), ispin2(*)
+       integer(c_int) :: ierr
+     end function edigpu_apply_pairs_sharded
      function edigpu_occ_moments_sharded(h, c, v_shard, nvec, moments, norm2) &
           bind(C, name="edigpu_occ_moments_sharded") result(ierr)
        import :: c_ptr, c_int, c_double
@@ -504,6 +513,8 @@ module EDIGPU_SHIM
   ! observables and the chi_spin / chi_dens / phonon seeds on the shards the MPI solve leaves
   public :: gpu_occ_moments_mpi, gpu_apply_op_N_mpi, gpu_apply_op_Sz_mpi, gpu_apply_xph_mpi, gpu_ph_rdm_mpi
   public :: gpu_imp_rdm_mpi
+  ! the Green's-function and pair seeds on those shards (phonon and complex sectors included)
+  public :: gpu_apply_cops_mpi_d, gpu_apply_cops_mpi_c, gpu_apply_pairs_mpi
 
 contains
 
@@ -1237,6 +1248,61 @@ contains
     p2 = c_null_ptr; if (size(vv_shard) > 0) p2 = c_loc(vv_shard)
     call gpu_check(edigpu_apply_cops_sharded(hsrc, hdst, gpu_comm, p1, p2, 1_c_int, coef2, cr, io, sp), "gpu_apply_op_mpi_d")
   end subroutine gpu_apply_op_mpi_d
+
+  !> vvloc = apply_Cops(v_state, coefs, Os, orbs, spins, ...) on shards (lanc_build_gf_normal_diag / _mix under -D_MPI,
+  !! ED_NORMAL/ED_GF_NORMAL.f90:141-263, without the gather on the master rank and the scatter): v_shard = this rank's
+  !! shard of the state (sector hsrc), vv_shard = this rank's shard of the seed (sector hdst), host or device (c_loc of the
+  !! arrays, or gpu_vec_alloc buffers), c_null_ptr on a rank that owns no row of that sector.  Os(i) = +1 for c^+, -1 for c;
+  !! orbs and spins count from 1.  Real sectors, phonon sectors (Holstein) included: whole-sector handles of one model; all
+  !! operators act on one spin; up operators of a phonon sector exchange nothing.  Collective.  Compile-checked only.
+  subroutine gpu_apply_cops_mpi_d(hsrc, hdst, v_shard, vv_shard, coefs, Os, orbs, spins)
+    type(c_ptr), intent(in) :: hsrc, hdst, v_shard, vv_shard
+    real(8), intent(in) :: coefs(:)
+    integer, intent(in) :: Os(:), orbs(:), spins(:)
+    real(c_double) :: ri(2 * size(Os))
+    integer(c_int32_t) :: o(size(Os)), io(size(Os)), is(size(Os))
+    if (.not. c_associated(gpu_comm)) stop "gpu_apply_cops_mpi_d: no communicator"
+    if (size(coefs) /= size(Os) .or. size(orbs) /= size(Os) .or. size(spins) /= size(Os)) stop "gpu_apply_cops_mpi_d: shapes"
+    ri = 0d0
+    ri(1::2) = coefs
+    o = int(Os, c_int32_t); io = int(orbs - 1, c_int32_t); is = int(spins - 1, c_int32_t)
+    call gpu_check(edigpu_apply_cops_sharded(hsrc, hdst, gpu_comm, v_shard, vv_shard, int(size(Os), c_int), ri, o, io, is), &
+         "gpu_apply_cops_mpi_d")
+  end subroutine gpu_apply_cops_mpi_d
+
+  !> The same with complex coefficients on the handles of gpu_build_normal_cmplx (the _CMPLX_NORMAL build: the [one, xi]
+  !! combinations of ED_GF_NORMAL.f90:250-263) and on superc / nonsu2 row shards; vectors interleaved (re, im).
+  subroutine gpu_apply_cops_mpi_c(hsrc, hdst, v_shard, vv_shard, coefs, Os, orbs, spins)
+    type(c_ptr), intent(in) :: hsrc, hdst, v_shard, vv_shard
+    complex(8), intent(in) :: coefs(:)
+    integer, intent(in) :: Os(:), orbs(:), spins(:)
+    real(c_double) :: ri(2 * size(Os))
+    integer(c_int32_t) :: o(size(Os)), io(size(Os)), is(size(Os))
+    if (.not. c_associated(gpu_comm)) stop "gpu_apply_cops_mpi_c: no communicator"
+    if (size(coefs) /= size(Os) .or. size(orbs) /= size(Os) .or. size(spins) /= size(Os)) stop "gpu_apply_cops_mpi_c: shapes"
+    ri(1::2) = real(coefs, 8)
+    ri(2::2) = aimag(coefs)
+    o = int(Os, c_int32_t); io = int(orbs - 1, c_int32_t); is = int(spins - 1, c_int32_t)
+    call gpu_check(edigpu_apply_cops_sharded(hsrc, hdst, gpu_comm, v_shard, vv_shard, int(size(Os), c_int), ri, o, io, is), &
+         "gpu_apply_cops_mpi_c")
+  end subroutine gpu_apply_cops_mpi_c
+
+  !> gpu_apply_pairs on shards (the seeds of ED_CHI_PAIR.f90:129-241 / ED_CHI_EXCT.f90:178-592 under -D_MPI): real
+  !! normal-mode whole-sector handles, phonon sectors included, hdst may be hsrc.  Vectors as gpu_apply_cops_mpi_d.  Terms
+  !! without a down operator exchange nothing, everything else takes one all-gather.  Collective.  Compile-checked only.
+  subroutine gpu_apply_pairs_mpi(hsrc, hdst, v_shard, vv_shard, coefs, Os1, orbs1, spins1, Os2, orbs2, spins2)
+    type(c_ptr), intent(in) :: hsrc, hdst, v_shard, vv_shard
+    real(8), intent(in) :: coefs(:)
+    integer, intent(in) :: Os1(:), orbs1(:), spins1(:), Os2(:), orbs2(:), spins2(:)
+    integer(c_int32_t) :: o1(size(Os1)), io1(size(Os1)), is1(size(Os1)), o2(size(Os1)), io2(size(Os1)), is2(size(Os1))
+    if (.not. c_associated(gpu_comm)) stop "gpu_apply_pairs_mpi: no communicator"
+    if (size(coefs) /= size(Os1) .or. size(orbs1) /= size(Os1) .or. size(spins1) /= size(Os1) .or. &
+         size(Os2) /= size(Os1) .or. size(orbs2) /= size(Os1) .or. size(spins2) /= size(Os1)) stop "gpu_apply_pairs_mpi: shapes"
+    o1 = int(Os1, c_int32_t); io1 = int(orbs1 - 1, c_int32_t); is1 = int(spins1 - 1, c_int32_t)
+    o2 = int(Os2, c_int32_t); io2 = int(orbs2 - 1, c_int32_t); is2 = int(spins2 - 1, c_int32_t)
+    call gpu_check(edigpu_apply_pairs_sharded(hsrc, hdst, gpu_comm, v_shard, vv_shard, int(size(Os1), c_int), coefs, o1, io1, &
+         is1, o2, io2, is2), "gpu_apply_pairs_mpi")
+  end subroutine gpu_apply_pairs_mpi
 
   !> gpu_occ_moments on shards, on the module's communicator: v_shard = this rank's shard(s) of size(norm2) vectors of
   !! sector h, consecutive with stride Nloc as gpu_sp_eigh_mpi_* leaves eig_basis (c_loc of it, or a device vector;

@@ -814,16 +814,51 @@ int edigpu_lanczos_eigh_sharded(edigpu_handle h, edigpu_comm c, int nitermax, do
                                 double *eval, double *evec_shard, int *nmatvec);
 /*
  * apply_op_C / apply_op_CDG / apply_Cops on shards: the Green's-function seeds the reference builds on the master rank
- * from the gathered eigenvector and scatters again (ED_NORMAL/ED_GF_NORMAL.f90:141-175, ED_AUX_FUNX.f90:598-692).  Here
- * v_src_shard (host or device: this rank's shard of a vector of sector `src`) is all-gathered on the device and every
- * rank computes ITS shard of the destination vector; v_dst_shard (host or device) receives the nloc elements of this
- * rank's shard of sector `dst`.  Handles as for the other sharded calls (normal mode: whole sectors from
- * edigpu_normal_build; superc / nonsu2: this rank's row shards); coefficients as in edigpu_apply_cops_flat (normal mode:
- * imaginary parts must be zero).
+ * from the gathered eigenvector and scatters again (ED_NORMAL/ED_GF_NORMAL.f90:141-175, ED_AUX_FUNX.f90:598-692).  Every
+ * rank computes ITS shard of the destination vector: v_src_shard is this rank's shard of a vector of sector `src`,
+ * v_dst_shard receives the nloc elements of its shard of sector `dst`, both in the layout of the sharded product (phonon
+ * sectors: block after block of the rank's rows; complex handles: interleaved (re, im)).  Host or device memory; a rank
+ * that owns no row passes NULL; device vectors must not overlap ("v_dst_shard overlaps v_src_shard").  Collective: every
+ * rank calls it with the same operators.  The checks of the handles and operators give the same answer on every rank; the
+ * checks of a rank's own vectors (NULL where it owns rows, overlap) can fail on one rank alone, and the others then wait in
+ * the all-gather, as in the other sharded calls: a host must pass consistent vectors.  Returns after the device has finished.  Buffers are kept by the communicator
+ * and only grow.  Handles as for the other sharded calls:
+ *   real normal mode           whole sectors from edigpu_normal_build of one model and one nph, phonon sectors included;
+ *                              imaginary parts of coef_re_im must be zero
+ *   complex normal mode        whole sectors from edigpu_normal_build_z (served through their doubled real sector);
+ *                              complex coefficients with the arithmetic of edigpu_apply_cops_normal_z, all-real ones
+ *                              with that of edigpu_apply_cops_normal on the interleaved doubles
+ *   superc / nonsu2            this rank's row shards, stored or on the fly, phonon sectors included; coefficients as in
+ *                              edigpu_apply_cops_flat
+ * Routes.  All operators of a normal-mode call act on one spin.  Up operators of phonon and complex sectors leave the
+ * sharded index (the down row) alone: the single-GPU kernel runs on the rank's own rows, NO collective and no copy of the
+ * source.  Everything else: one all-gather of the ranks' padded chunks on the device, then the window + source form of the
+ * single-GPU kernel on the rank's destination rows.  Arithmetic and term order are those of edigpu_apply_cops_normal(_z) /
+ * edigpu_apply_cops_flat on the whole vector: the stitched shards are bit-identical to the single-GPU result.  (Real
+ * phonon-free normal-mode sectors keep their earlier route: one launch per operator on the gathered vector, up operators
+ * included.)  Not served: ed_total_ud=F sectors, hand-over handles, complex phonon sectors.
+ *
+ * edigpu_apply_pairs_sharded: edigpu_apply_pairs_normal on shards, for whole real normal-mode sectors built from a model,
+ * phonon sectors included; src == dst is allowed.  Local (no collective) when no term has a down operator, else one
+ * all-gather.  The refusals of edigpu_apply_pairs_normal, each message starting with this entry's name; down-row shard
+ * handles are refused as well ("must hold the whole sector").
+ *
+ * edigpu_apply_cops_sharded_info / edigpu_apply_pairs_sharded_info (host only, no device is touched): the same checks as
+ * the calls, then info[0] = route (0 local, 1 all-gather), info[1] = doubles this rank contributes to the all-gather (0
+ * on the local route).
  */
 int edigpu_apply_cops_sharded(edigpu_handle src, edigpu_handle dst, edigpu_comm c, const double *v_src_shard,
                               double *v_dst_shard, int nops, const double *coef_re_im, const int32_t *create,
                               const int32_t *iorb, const int32_t *ispin);
+int edigpu_apply_cops_sharded_info(edigpu_handle src, edigpu_handle dst, edigpu_comm c, int nops, const double *coef_re_im,
+                                   const int32_t *create, const int32_t *iorb, const int32_t *ispin, int64_t info[2]);
+int edigpu_apply_pairs_sharded(edigpu_handle src, edigpu_handle dst, edigpu_comm c, const double *v_src_shard,
+                               double *v_dst_shard, int nterms, const double *coef, const int32_t *create1,
+                               const int32_t *iorb1, const int32_t *ispin1, const int32_t *create2, const int32_t *iorb2,
+                               const int32_t *ispin2);
+int edigpu_apply_pairs_sharded_info(edigpu_handle src, edigpu_handle dst, edigpu_comm c, int nterms, const double *coef,
+                                    const int32_t *create1, const int32_t *iorb1, const int32_t *ispin1,
+                                    const int32_t *create2, const int32_t *iorb2, const int32_t *ispin2, int64_t info[2]);
 /*
  * Occupation and phonon observables on shards: edigpu_occ_moments, edigpu_apply_occ, edigpu_apply_xph and edigpu_ph_rdm
  * on this rank's shard of a vector, without gathering it (the -D_MPI host otherwise collects every state on one rank:

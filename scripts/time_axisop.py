@@ -14,6 +14,12 @@ moves (it stores every destination element once and loads the live half of them)
 rounds in this one process; over the rounds the median.
 
     python scripts/time_axisop.py [--steps 21] [--warmup 3] [--rounds 3]
+
+--sharded times edigpu_apply_cops_sharded instead (profiles/axisop.json, key sharded_rehearsal): a world of ONE rank on the
+RCCL communicator with the collectives forced (EDIGPU_FORCE_COLLECTIVES=1, so the all-gather is a real RCCL call), c up and
+c down of orbital 0 on the config-2 sector with nph = 4, device vectors, against edigpu_apply_cops_normal on the same
+vectors; both calls return after the device has finished and are timed on the host clock.  A rehearsal of the call's fixed
+costs on one GPU, not a scaling figure.
 """
 import argparse
 import dataclasses
@@ -27,12 +33,70 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def sharded(args):
+    import time
+    os.environ["EDIGPU_FORCE_COLLECTIVES"] = "1"
+    import torch
+    from edipack_amd import capi
+    from edipack_amd.hamiltonian import SectorHamiltonian as H
+    from edipack_amd.sharding import LibraryComm
+    from edipack_amd.synthetic import WORKLOADS, synthetic_model
+    if capi.device_count() < 1:
+        raise SystemExit("time_axisop.py: no HIP device (there is nothing to time on a CPU)")
+    capi.init(0)
+    w = WORKLOADS["cfg2"]
+    nup, ndw = w.sector
+    nph = 4
+    pm = synthetic_model(w)
+    pm.nph, pm.w0_ph, pm.a_ph, pm.g_ph = nph, 0.8, 0.0, np.diag(np.linspace(0.3, 0.5, w.norb))
+    comm = LibraryComm(0, 1, unique_id=LibraryComm.unique_id())
+    src = H.normal_from_model(pm, nup, ndw)
+    gen = torch.Generator(device="cuda").manual_seed(1234)
+    v = torch.randn(src.dim, dtype=torch.float64, device="cuda", generator=gen)
+
+    def median_ms(fn):
+        ms = []
+        for k in range(args.warmup + args.steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ms[args.warmup:]))
+
+    out = {"script": "scripts/time_axisop.py --sharded", "kernel_source_hash": capi.kernel_source_hash(), "steps": args.steps,
+           "warmup": args.warmup, "rounds": args.rounds, "world": 1, "forced_collectives": True, "nph": nph,
+           "source_sector": [nup, ndw], "doubles_src": src.dim, "cases": []}
+    for spin, dest in ((0, (nup - 1, ndw)), (1, (nup, ndw - 1))):
+        dst = H.normal_from_model(pm, *dest)
+        one = torch.empty(dst.dim, dtype=torch.float64, device="cuda")
+        sh = torch.empty(dst.dim, dtype=torch.float64, device="cuda")
+        ops = [(1.0, False, 0, spin)]
+        single = lambda: src.apply_cops_to(dst, v.data_ptr(), one.data_ptr(), [1.0], [False], [0], [spin])      # noqa: E731
+        shard = lambda: comm.apply_cops(src, dst, v.data_ptr(), dst.dim, ops, out=sh.data_ptr())               # noqa: E731
+        single(), shard()
+        torch.cuda.synchronize()
+        equal = bool(torch.equal(one.view(torch.int64), sh.view(torch.int64)))
+        rounds = [{"single_call_ms": median_ms(single), "sharded_call_ms": median_ms(shard)} for _ in range(args.rounds)]
+        med = {k: float(np.median([r[k] for r in rounds])) for k in rounds[0]}
+        route, contributed = comm.apply_cops_info(src, dst, ops)
+        out["cases"].append({"name": f"c {'down' if spin else 'up'} of orbital 0", "route": route, "allgather_doubles": contributed,
+                             "doubles_dst": dst.dim, **med, "ratio": med["sharded_call_ms"] / med["single_call_ms"],
+                             "bit_equal": equal, "per_round": rounds})
+        dst.destroy()
+    src.destroy()
+    comm.destroy()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=21)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--sharded", action="store_true", help="one-rank rehearsal of edigpu_apply_cops_sharded against edigpu_apply_cops_normal")
     args = ap.parse_args()
+    if args.sharded:
+        return sharded(args)
     import torch
     from edipack_amd import capi
     from edipack_amd.hamiltonian import SectorHamiltonian as H

@@ -17,6 +17,11 @@ of orbitals 0 and 1 added), both into the sector (6, 6):
 (bit patterns after adding +0.0: the chain writes -0.0 where a sign meets an empty intermediate element).
 
     python scripts/time_pairs.py [--steps 21] [--warmup 3] [--rounds 3]
+
+--sharded times edigpu_apply_pairs_sharded instead (profiles/pairs.json, key sharded_rehearsal): a world of ONE rank on the
+RCCL communicator with the collectives forced (EDIGPU_FORCE_COLLECTIVES=1), the 1-term pair seed on the config-2 sector
+with nph = 4, device vectors, against edigpu_apply_pairs_normal on the same vectors; both calls return after the device has
+finished and are timed on the host clock.  A rehearsal of the call's fixed costs on one GPU, not a scaling figure.
 """
 import argparse
 import json
@@ -29,13 +34,70 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def sharded(args):
+    import time
+    os.environ["EDIGPU_FORCE_COLLECTIVES"] = "1"
+    import torch
+    from edipack_amd import capi
+    from edipack_amd.hamiltonian import SectorHamiltonian, pairs_sector
+    from edipack_amd.observables import pair_chi_seeds
+    from edipack_amd.sharding import LibraryComm
+    from edipack_amd.synthetic import WORKLOADS, synthetic_model
+    if capi.device_count() < 1:
+        raise SystemExit("time_pairs.py: no HIP device (there is nothing to time on a CPU)")
+    capi.init(0)
+    w = WORKLOADS[args.workload]
+    nph = 4
+    pm = synthetic_model(w)
+    pm.nph, pm.w0_ph, pm.a_ph, pm.g_ph = nph, 0.8, 0.0, np.diag(np.linspace(0.3, 0.5, w.norb))
+    nup, ndw = w.sector
+    terms = pair_chi_seeds(0, 0)[0][0]
+    dest = pairs_sector(pm, nup, ndw, terms)
+    comm = LibraryComm(0, 1, unique_id=LibraryComm.unique_id())
+    src = SectorHamiltonian.normal_from_model(pm, nup, ndw)
+    dst = SectorHamiltonian.normal_from_model(pm, dest[0], dest[1])
+    gen = torch.Generator(device="cuda").manual_seed(1234)
+    v = torch.randn(src.dim, dtype=torch.float64, device="cuda", generator=gen)
+    one = torch.empty(dst.dim, dtype=torch.float64, device="cuda")
+    sh = torch.empty(dst.dim, dtype=torch.float64, device="cuda")
+
+    def median_ms(fn):
+        ms = []
+        for k in range(args.warmup + args.steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ms[args.warmup:]))
+
+    single = lambda: src.apply_pairs_to(dst, v.data_ptr(), one.data_ptr(), terms)                               # noqa: E731
+    shard = lambda: comm.apply_pairs(src, dst, v.data_ptr(), dst.dim, terms, out=sh.data_ptr())                # noqa: E731
+    single(), shard()
+    torch.cuda.synchronize()
+    equal = bool(torch.equal(one.view(torch.int64), sh.view(torch.int64)))
+    rounds = [{"single_call_ms": median_ms(single), "sharded_call_ms": median_ms(shard)} for _ in range(args.rounds)]
+    med = {k: float(np.median([r[k] for r in rounds])) for k in rounds[0]}
+    route, contributed = comm.apply_pairs_info(src, dst, terms)
+    print(json.dumps({"script": "scripts/time_pairs.py --sharded", "kernel_source_hash": capi.kernel_source_hash(),
+                      "workload": w.name, "nph": nph, "world": 1, "forced_collectives": True, "steps": args.steps,
+                      "warmup": args.warmup, "rounds": args.rounds, "source_sector": [nup, ndw], "destination_sector": list(dest[:2]),
+                      "doubles_src": src.dim, "doubles_dst": dst.dim, "seed": "pair lesser diag (1 term)", "route": route,
+                      "allgather_doubles": contributed, **med, "ratio": med["sharded_call_ms"] / med["single_call_ms"],
+                      "bit_equal": equal, "per_round": rounds}))
+    src.destroy(), dst.destroy()
+    comm.destroy()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="cfg2")
     ap.add_argument("--steps", type=int, default=21)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--sharded", action="store_true", help="one-rank rehearsal of edigpu_apply_pairs_sharded against edigpu_apply_pairs_normal")
     args = ap.parse_args()
+    if args.sharded:
+        return sharded(args)
     import torch
     from edipack_amd import capi
     from edipack_amd.hamiltonian import SectorHamiltonian, pairs_sector
