@@ -191,6 +191,8 @@ SIGNATURES = {
     "edigpu_apply_xph_sharded": (C.c_int, [_vp, _vp, _vp, _vp]),
     "edigpu_ph_rdm_sharded": (C.c_int, [_vp, _vp, _vp, C.c_int, _pd, _pd]),
     "edigpu_imp_rdm_sharded": (C.c_int, [_vp, _vp, _vp, C.c_int, _pd, _pd]),
+    "edigpu_imp_rdm_flat_sharded": (C.c_int, [_vp, _vp, _vp, C.c_int, _pd, _pd]),
+    "edigpu_imp_rdm_flat_sharded_info": (C.c_int, [_vp, _vp, _pi64]),
     "edigpu_apply_cops_flat": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _pd, _vp, _vp, _vp, _vp]),
     "edigpu_lanczos_bench_sharded": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _pd, _pi64]),
     "edigpu_destroy": (C.c_int, [_vp]),

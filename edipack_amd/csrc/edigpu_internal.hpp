@@ -240,6 +240,30 @@ void rdm_shard_expand(const edigpu_sector* s, const double* tri, int nvec, doubl
 // The same of edigpu_imp_rdm_flat on a library-built whole superc / nonsu2 sector (host_rdm_flat.hpp; kernels_rdm_flat.hip).
 struct RdmFlatDev;
 void free_rdm_flat(edigpu_sector* s);
+// The same on the elements [first, first + count) of the sector, one of `world` ranges of edigpu_shard_plan over the
+// electronic dimension (edigpu_sector::rdm_flat_shard; host_rdm_flat.hpp RdmFlatShardPlan), kept like rdm_shard, built on
+// every rank, elements or not, and freed by free_rdm_flat.  A slab -- the rows of one bath word down -- that a rank boundary
+// cuts belongs to the rank it starts on: every rank sends its first H elements (rdm_flat_shard_pack: nvec x nblk x H x cw
+// doubles, zero-padded), and rdm_flat_shard_enqueue fills the owner's slab (nvec x nblk x tail_len x cw doubles) from the
+// gathered halos, runs the tiles kernel on the shard in place and on the slab, and leaves the nvec x ntri x cw packed
+// sums of this rank in *tri_dev, all on the handle's stream.
+struct RdmFlatShardDev;
+struct RdmFlatShardInfo {
+  int64_t H = 0, nslab_in = 0, tail_start = -1, tail_len = 0, tail_own = 0, ntri = 0;
+  int cw = 1;
+};
+// the refusals that need no communicator: ed_total_ud=F, hand-over handle, normal mode, Jz_basis, Norb = 5
+int rdm_flat_shard_refuse(const edigpu_sector* s, const std::string& who);
+// the geometry alone, from host tables made for the call: touches no device and keeps nothing
+int rdm_flat_shard_info(const edigpu_sector* s, int64_t first, int64_t count, int world, const std::string& who,
+                        RdmFlatShardInfo* info);
+int rdm_flat_shard_prepare(edigpu_sector* s, int64_t first, int64_t count, int world, const std::string& who,
+                           RdmFlatShardInfo* info);
+int rdm_flat_shard_pack(edigpu_sector* s, const double* v_dev, int nvec, double* send_dev);
+int rdm_flat_shard_enqueue(edigpu_sector* s, const double* v_dev, int nvec, const double* halos_dev, double* slab_dev,
+                           const double** tri_dev);
+// the summed packed triangles -> nvec dense matrices and traces, as edigpu_imp_rdm_flat returns them
+void rdm_flat_shard_expand(const edigpu_sector* s, const double* tri, int nvec, double* rdm_host, double* norm2_host);
 
 // Tables and workspace of edigpu_apply_xph / edigpu_ph_rdm on a library-built whole phonon sector (host_ph.hpp;
 // kernels_ph.hip), made and uploaded by the first call on the handle and kept until edigpu_destroy.
@@ -403,6 +427,7 @@ struct edigpu_sector {
   edigpu::RdmDev* rdm = nullptr;
   edigpu::RdmShardDev* rdm_shard = nullptr;  // the view of a rank's rows (edigpu_imp_rdm_sharded)
   edigpu::RdmFlatDev* rdm_flat = nullptr;
+  edigpu::RdmFlatShardDev* rdm_flat_shard = nullptr;  // the view of a rank's elements (edigpu_imp_rdm_flat_sharded)
   // ---- phonon displacement seed and phonon density matrix (lazily built) ----
   edigpu::PhDev* ph = nullptr;
   edigpu::PhDev* ph_shard = nullptr;    // the view of a rank's rows

@@ -1,6 +1,6 @@
 // edigpu_shard_obs.hip -- occupation and phonon observables and the impurity density matrix on sharded vectors
 // (include/edigpu.h: edigpu_occ_moments_sharded, edigpu_apply_occ_sharded, edigpu_apply_xph_sharded,
-// edigpu_ph_rdm_sharded, edigpu_imp_rdm_sharded).
+// edigpu_ph_rdm_sharded, edigpu_imp_rdm_sharded, edigpu_imp_rdm_flat_sharded[_info]).
 //
 // The four operators are local to a row and to the row's phonon blocks, and a rank holds all phonon blocks of its rows:
 // the kernels of kernels_occ.hip / kernels_ph.hip run unchanged on tables made for the rank's rows (the shard views of
@@ -9,7 +9,8 @@
 // host expansions of the single-GPU entries follow: no floating-point atomics, the same bits on every rank and call.
 // Takes the place of gathering every state on one rank (es_return_dvector_mpi, ED_EIGENSPACE.f90:723-793).
 // The impurity density matrix is not local to a row -- it needs the whole run of down rows of a bath word -- and
-// exchanges the few rows a rank boundary cuts off first (at the end of this file).
+// exchanges the few rows a rank boundary cuts off first (at the end of this file); in superc / nonsu2 it needs the whole
+// slab of rows of a bath word down, and the ranks exchange the elements of the slabs their boundaries cut.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -233,6 +234,71 @@ int edigpu_imp_rdm_sharded(edigpu_handle s, edigpu_comm c, const double* v_shard
   std::vector<double> tri;
   if (reduce_to_host(c, mine, (size_t)nvec * ri.ntri * ri.cw, st, tri)) return 1;
   rdm_shard_expand(s, tri.data(), nvec, rdm_host, norm2_host);
+  return 0;
+}
+
+// The same of superc / nonsu2 vectors: a tile needs the whole SLAB of a bath word down -- its 2^Norb rows, a contiguous
+// range of elements -- and a row shard cuts anywhere in it.  Every rank sends its first H elements (those of a slab that
+// starts on an earlier rank), one all-gather, and the rank a cut slab starts on completes it in a buffer
+// (edigpu_internal.hpp rdm_flat_shard_*; host_rdm_flat.hpp RdmFlatShardPlan).  H is bounded by one slab and is the same
+// on every rank, so the all-gather is issued by all or by none.
+static int rdm_flat_sharded_checks(edigpu_sector* s, edigpu_comm_s* c, const std::string& who, ShardGeom& g) {
+  if (rdm_flat_shard_refuse(s, who)) return 1;
+  return shard_geometry(s, c, g);
+}
+
+int edigpu_imp_rdm_flat_sharded(edigpu_handle s, edigpu_comm c, const double* v_shard, int nvec, double* rdm_host,
+                                double* norm2_host) {
+  const std::string who = "edigpu_imp_rdm_flat_sharded";
+  if (!s || !c || !rdm_host || nvec <= 0) {
+    set_error(who + (!s || !c || !rdm_host ? ": NULL argument" : ": nvec must be positive"));
+    return 1;
+  }
+  ShardGeom g;
+  if (rdm_flat_sharded_checks(s, c, who, g)) return 1;
+  if (g.count > 0 && !v_shard) {
+    set_error(who + ": NULL argument");
+    return 1;
+  }
+  EDIGPU_HIP(hipSetDevice(s->device));
+  hipStream_t st = s->stream;
+  RdmFlatShardInfo ri;
+  if (rdm_flat_shard_prepare(s, g.first, g.count, c->world, who, &ri)) return 1;
+  const int nblk = s->nph + 1;
+  const int64_t len = g.count * nblk * ri.cw;
+  const double* vd = nullptr;
+  if (g.count > 0 && stage_in(c, v_shard, len * nvec, 0, len * nvec, st, &vd)) return 1;
+  ShardWorkspace& w = c->ws;
+  if (ri.H > 0) {
+    const int64_t n = (int64_t)nvec * nblk * ri.H * ri.cw;
+    if (dev_grow(&w.halo, &w.halo_cap, n) || dev_grow(&w.halos, &w.halos_cap, n * c->world)) return 1;
+    if (rdm_flat_shard_pack(s, vd, nvec, w.halo) || comm_all_gather(c, w.halo, w.halos, (size_t)n, st)) return 1;
+  }
+  if (dev_grow(&w.slab, &w.slab_cap, (int64_t)nvec * nblk * ri.tail_len * ri.cw)) return 1;
+  const double* mine = nullptr;
+  if (rdm_flat_shard_enqueue(s, vd, nvec, w.halos, w.slab, &mine)) return 1;
+  std::vector<double> tri;
+  if (reduce_to_host(c, mine, (size_t)nvec * ri.ntri * ri.cw, st, tri)) return 1;
+  rdm_flat_shard_expand(s, tri.data(), nvec, rdm_host, norm2_host);
+  return 0;
+}
+
+int edigpu_imp_rdm_flat_sharded_info(edigpu_handle s, edigpu_comm c, int64_t info[6]) {
+  const std::string who = "edigpu_imp_rdm_flat_sharded_info";
+  if (!s || !c || !info) {
+    set_error(who + ": NULL argument");
+    return 1;
+  }
+  ShardGeom g;
+  if (rdm_flat_sharded_checks(s, c, who, g)) return 1;
+  RdmFlatShardInfo ri;
+  if (rdm_flat_shard_info(s, g.first, g.count, c->world, who, &ri)) return 1;
+  info[0] = ri.H;
+  info[1] = ri.H * (s->nph + 1) * ri.cw;
+  info[2] = ri.nslab_in;
+  info[3] = ri.tail_start;
+  info[4] = ri.tail_len;
+  info[5] = ri.tail_own;
   return 0;
 }
 

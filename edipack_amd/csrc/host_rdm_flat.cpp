@@ -152,12 +152,17 @@ void rdm_flat_host_reference(const RdmFlatTables& t, int nblk, const double* v, 
       }
 }
 
-void rdm_flat_plan(const RdmFlatTables& t, int nblk, int cw, int target_wgs, RdmFlatPlan& p) {
+// rdm_flat_plan of the bath words down that `keep` names (null: all), on a vector whose element 0 is element `base` of the
+// sector and whose blocks are `stride` elements apart.  The panels and the class groups are those of the whole sector
+// whatever is kept, so every such list splits the packed entries alike and two of them can share their partial sums.
+static void flat_plan_core(const RdmFlatTables& t, int nblk, int cw, int target_wgs, const std::vector<char>* keep, int64_t base,
+                           int64_t stride, RdmFlatPlan& p) {
   p = RdmFlatPlan();
   const int norb = t.norb, nbw = 1 << (t.ns - norb), imask = (1 << norb) - 1, nrow = 1 << norb;
   p.norb = norb;
-  p.dim_el = t.dim_el;
+  p.dim_el = stride;
   p.rowstart = t.rowstart;
+  for (int64_t& r : p.rowstart) r -= base;
   int bmax = 1;
   for (int c = 0; c < t.nclass; c++) bmax = std::max(bmax, t.bn[c]);
   const int nb = kRdmFlatStageElems / bmax;  // bath words up of a chunk: its tiles hold at most nb * bmax elements
@@ -165,7 +170,7 @@ void rdm_flat_plan(const RdmFlatTables& t, int nblk, int cw, int target_wgs, Rdm
   for (int bd = 0; bd <= t.ns - norb; bd++) {
     const int32_t bdw0 = (int32_t)p.bdw.size();
     for (int b = 0; b < nbw; b++)
-      if (popc((uint32_t)b) == bd) p.bdw.push_back(b);
+      if (popc((uint32_t)b) == bd && (!keep || (*keep)[(size_t)b])) p.bdw.push_back(b);
     const int32_t nbdw = (int32_t)p.bdw.size() - bdw0;
     for (int b0 = 0; b0 < nbw; b0 += nb) {
       const int b1 = std::min(nbw, b0 + nb);
@@ -248,7 +253,7 @@ void rdm_flat_plan(const RdmFlatTables& t, int nblk, int cw, int target_wgs, Rdm
     wants.push_back({c, c1});
     c = c1 + 1;
   }
-  const int64_t total = (int64_t)wants.size() * t.dim_el * nblk;
+  const int64_t total = (int64_t)wants.size() * stride * nblk;
   for (const Want& w : wants) {
     RdmGroup g;
     g.e0 = (int32_t)t.tri_off[w.c0];
@@ -283,15 +288,22 @@ void rdm_flat_plan(const RdmFlatTables& t, int nblk, int cw, int target_wgs, Rdm
   }
 }
 
-std::string rdm_flat_plan_emulate(const RdmFlatPlan& p, int64_t ntri, int64_t nel, const double* v, int cw, double* tri) {
+void rdm_flat_plan(const RdmFlatTables& t, int nblk, int cw, int target_wgs, RdmFlatPlan& p) {
+  flat_plan_core(t, nblk, cw, target_wgs, nullptr, 0, t.dim_el, p);
+}
+
+// the tiles kernel on the work list of p: v holds nel elements in blocks p.dim_el apart; partial / written: the buffer of
+// partial sums (partial_entries of them) and which of them a workgroup has written
+static std::string emulate_tiles(const RdmFlatPlan& p, int64_t ntri, int64_t nel, const double* v, int cw, int64_t partial_entries,
+                                 std::vector<double>& partial, std::vector<char>& written) {
   const int norb = p.norb, nrow = 1 << norb;
   const int64_t stage_n = p.stage_max, acc_n = (int64_t)p.ept_max * kRdmFlatThreads;
   if (stage_n > kRdmFlatStageElems) return "a staged slab exceeds the staging area";
-  std::vector<double> stage((size_t)stage_n * cw), acc((size_t)acc_n * cw), partial((size_t)p.partial_entries * cw, 0.0);
+  std::vector<double> stage((size_t)stage_n * cw), acc((size_t)acc_n * cw);
   std::vector<int64_t> loaded((size_t)stage_n, -1);
   std::vector<uint16_t> rel((size_t)p.rel_max);
-  std::vector<char> written((size_t)p.partial_entries, 0);
   if ((int64_t)p.ent.size() != ntri) return "ent does not have ntri entries";
+  if (!p.work.empty() && !v) return "a work list without a vector";
   int64_t slab = 0;
   for (const RdmFlatWork& w : p.work) {
     if (w.panel < 0 || w.panel >= (int64_t)p.panels.size()) return "panel out of range";
@@ -313,6 +325,7 @@ std::string rdm_flat_plan_emulate(const RdmFlatPlan& p, int64_t ntri, int64_t ne
         if (row0 + idw + 1 >= (int64_t)p.rowstart.size()) return "row out of range";
         const int64_t r0 = p.rowstart[(size_t)(row0 + idw)], r1 = p.rowstart[(size_t)(row0 + idw + 1)];
         if (P.seg[kd] < 0 || L < 0 || P.seg[kd] + L > r1 - r0) return "segment outside its row";
+        if (r0 < 0 || r1 > p.dim_el) return "row outside its block";
         const int64_t g0 = (int64_t)b * p.dim_el + r0 + P.seg[kd];
         if (g0 < 0 || g0 + L > nel) return "vector read out of range";
         if (P.soff[idw] < 0 || P.soff[idw] + L > stage_n) return "staged write out of range";
@@ -352,19 +365,25 @@ std::string rdm_flat_plan_emulate(const RdmFlatPlan& p, int64_t ntri, int64_t ne
     for (int t = 0; t < kRdmFlatThreads; t++)
       for (int e = w.e0 + t, k = 0; e < w.e1; e += kRdmFlatThreads, k++) {
         const int64_t o = w.pofs + (e - w.e0);
-        if (o < 0 || o >= p.partial_entries) return "partial sum out of range";
+        if (o < 0 || o >= partial_entries) return "partial sum out of range";
         if (written[(size_t)o]) return "a partial sum is written twice";
         written[(size_t)o] = 1;
         for (int c = 0; c < cw; c++) partial[(size_t)o * cw + c] = acc[((size_t)k * kRdmFlatThreads + t) * cw + c];
       }
   }
+  return "";
+}
+
+// the final kernel over the groups: tri[ntri] = the workgroups' partial sums in workgroup order, 0 where no group writes
+static std::string emulate_final(const std::vector<RdmGroup>& groups, int64_t ntri, int cw, int64_t partial_entries,
+                                 const std::vector<double>& partial, const std::vector<char>& written, double* tri) {
   for (char c : written)
     if (!c) return "a partial sum is never written";
   std::fill(tri, tri + ntri * cw, 0.0);
   std::vector<char> done((size_t)ntri, 0);
-  for (const RdmGroup& g : p.groups) {
+  for (const RdmGroup& g : groups) {
     const int64_t E = g.e1 - g.e0;
-    if (g.e0 < 0 || g.e1 > ntri || g.pbase + (int64_t)g.nwg * E > p.partial_entries) return "group out of range";
+    if (g.e0 < 0 || g.e1 > ntri || g.pbase + (int64_t)g.nwg * E > partial_entries) return "group out of range";
     for (int64_t e = 0; e < E; e++) {
       if (done[(size_t)(g.e0 + e)]) return "two groups write one entry";
       done[(size_t)(g.e0 + e)] = 1;
@@ -374,6 +393,252 @@ std::string rdm_flat_plan_emulate(const RdmFlatPlan& p, int64_t ntri, int64_t ne
         tri[(g.e0 + e) * cw + c] = s;
       }
     }
+  }
+  return "";
+}
+
+std::string rdm_flat_plan_emulate(const RdmFlatPlan& p, int64_t ntri, int64_t nel, const double* v, int cw, double* tri) {
+  std::vector<double> partial((size_t)p.partial_entries * cw, 0.0);
+  std::vector<char> written((size_t)p.partial_entries, 0);
+  const std::string why = emulate_tiles(p, ntri, nel, v, cw, p.partial_entries, partial, written);
+  return why.empty() ? emulate_final(p.groups, ntri, cw, p.partial_entries, partial, written, tri) : why;
+}
+
+// the non-empty slabs of the sector in ascending order: [start[j], start[j + 1]) is the slab of bath word down bdw[j]
+struct FlatSlabs {
+  std::vector<int64_t> start;
+  std::vector<int32_t> bdw;
+};
+static void flat_slabs(const RdmFlatTables& t, FlatSlabs& s) {
+  const int nbw = 1 << (t.ns - t.norb);
+  for (int b = 0; b < nbw; b++) {
+    const int64_t s0 = t.rowstart[(size_t)b << t.norb], s1 = t.rowstart[(size_t)(b + 1) << t.norb];
+    if (s1 == s0) continue;
+    s.start.push_back(s0);
+    s.bdw.push_back(b);
+  }
+  s.start.push_back(t.dim_el);
+}
+
+// elements from `first` up to the first slab start in [first, first + count) (count when there is none); *slab = that slab
+static int64_t flat_head(const FlatSlabs& s, int64_t first, int64_t count, size_t* slab) {
+  const size_t j = (size_t)(std::lower_bound(s.start.begin(), s.start.end() - 1, first) - s.start.begin());
+  if (slab) *slab = j;
+  if (j >= s.bdw.size() || s.start[j] >= first + count) return count;
+  return s.start[j] - first;
+}
+
+std::string rdm_flat_shard_plan(const RdmFlatTables& t, int nblk, int cw, int target_wgs, int world, int64_t first,
+                                int64_t count, RdmFlatShardPlan& p) {
+  p = RdmFlatShardPlan();
+  if (world < 1 || first < 0 || count < 0) return "bad range";
+  if (t.rowstart.empty() || t.rowstart.back() != t.dim_el) return "no tables of the sector";
+  const int64_t dim = t.dim_el;
+  p.world = world;
+  p.q = (dim + world - 1) / world;
+  p.first = std::min(first, dim);
+  p.count = std::max<int64_t>(0, std::min(count, dim - p.first));
+  p.rank = -1;
+  if (p.count > 0) {
+    if (p.first % p.q != 0 || p.count != std::min(p.q, dim - p.first)) return "the elements are not a rank's range of edigpu_shard_plan";
+    p.rank = (int)(p.first / p.q);
+  }
+  FlatSlabs sl;
+  flat_slabs(t, sl);
+  int64_t longest = 0;
+  for (size_t j = 0; j < sl.bdw.size(); j++) longest = std::max(longest, sl.start[j + 1] - sl.start[j]);
+  p.heads.assign((size_t)world, 0);
+  for (int r = 0; r < world; r++) {
+    const int64_t f = std::min<int64_t>((int64_t)r * p.q, dim), c = std::max<int64_t>(0, std::min(p.q, dim - f));
+    p.heads[(size_t)r] = flat_head(sl, f, c, nullptr);
+    p.H = std::max(p.H, p.heads[(size_t)r]);
+  }
+  if (p.H > 0 && p.H >= longest) return "a halo as long as a slab";
+  // the halo this rank sends: its head, then zeros
+  const int64_t head = p.rank >= 0 ? p.heads[(size_t)p.rank] : 0;
+  if (head > 0) p.pack.push_back({1, 0, 0, 0, head});
+  if (p.H > head) p.pack.push_back({0, 0, 0, head, p.H - head});
+  // interior slabs and the tail slab
+  const int nbw = 1 << (t.ns - t.norb);
+  std::vector<char> keep((size_t)nbw, 0);
+  for (int b = 0; b < nbw; b++)  // empty slabs stay in the lists (no panel names them): a world of one IS rdm_flat_plan
+    keep[(size_t)b] = t.rowstart[(size_t)b << t.norb] == t.rowstart[(size_t)(b + 1) << t.norb];
+  const std::vector<char> empty = keep;
+  size_t j = 0;
+  if (p.count > 0) flat_head(sl, p.first, p.count, &j);
+  for (; p.count > 0 && j < sl.bdw.size() && sl.start[j] < p.first + p.count; j++) {
+    if (sl.start[j + 1] <= p.first + p.count) {
+      keep[(size_t)sl.bdw[j]] = 1;
+      p.nslab_in++;
+      continue;
+    }
+    p.tail_start = sl.start[j] - p.first;
+    p.tail_own = p.count - p.tail_start;
+    p.tail_len = sl.start[j + 1] - sl.start[j];
+    p.tail_bdw = sl.bdw[j];
+  }
+  flat_plan_core(t, nblk, cw, target_wgs, &keep, p.first, p.count, p.in);
+  if (p.tail_len > 0) {
+    p.fill.push_back({1, 0, p.tail_start, 0, p.tail_own});
+    int64_t n = p.tail_own;
+    for (int r = p.rank + 1; r < world && n < p.tail_len; r++) {
+      const int64_t take = std::min(p.heads[(size_t)r], p.tail_len - n);
+      if (take <= 0) continue;
+      p.fill.push_back({2, r, 0, n, take});
+      n += take;
+    }
+    if (n != p.tail_len) return "the following ranks' heads do not complete the tail slab";
+    keep = empty;
+    keep[(size_t)p.tail_bdw] = 1;
+    flat_plan_core(t, nblk, cw, target_wgs, &keep, p.first + p.tail_start, p.tail_len, p.slab);
+  }
+  // one buffer of partial sums: per group the workgroups of `in`, then those of `slab` (no slab: `in` as it stands)
+  for (const RdmFlatPlan* q : {&p.in, &p.slab})
+    for (const RdmGroup& g : q->groups) {
+      auto it = std::find_if(p.groups.begin(), p.groups.end(), [&](const RdmGroup& m) { return m.e0 == g.e0; });
+      if (it == p.groups.end()) {
+        p.groups.push_back(g);
+      } else {
+        if (it->e1 != g.e1) return "the two work lists split the classes differently";
+        it->nwg += g.nwg;
+      }
+    }
+  for (RdmGroup& g : p.groups) {
+    g.pbase = p.partial_entries;
+    p.partial_entries += (int64_t)g.nwg * (g.e1 - g.e0);
+  }
+  std::vector<int32_t> next(p.groups.size(), 0);
+  for (RdmFlatPlan* q : {&p.in, &p.slab})
+    for (RdmFlatWork& w : q->work) {
+      const size_t g = (size_t)(std::find_if(p.groups.begin(), p.groups.end(), [&](const RdmGroup& m) { return m.e0 == w.e0; }) -
+                                p.groups.begin());
+      if (g >= p.groups.size() || p.groups[g].e1 != w.e1) return "a workgroup without a group";
+      w.pofs = p.groups[g].pbase + (int64_t)next[g]++ * (w.e1 - w.e0);
+    }
+  return "";
+}
+
+std::string rdm_flat_segs_emulate(const RdmFlatShardPlan& p, const std::vector<RdmFlatSeg>& segs, int64_t dlen, int nblk, int cw,
+                                  const double* v, const double* halos, double* dst) {
+  const int64_t rank_stride = (int64_t)nblk * p.H;  // elements of one vector's halo
+  std::vector<char> written((size_t)dlen, 0);
+  for (int b = 0; b < nblk; b++) {
+    std::fill(written.begin(), written.end(), 0);
+    for (const RdmFlatSeg& s : segs) {
+      if (s.len <= 0 || s.dst < 0 || s.dst + s.len > dlen) return "segment outside its destination";
+      if (s.sel == 1) {
+        if (s.src < 0 || s.src + s.len > p.count || !v) return "shard element out of range";
+      } else if (s.sel == 2) {
+        if (s.rank < 0 || s.rank >= p.world || !halos) return "halo rank out of range";
+        if (s.src < 0 || s.src + s.len > p.heads[(size_t)s.rank]) return "halo element past its rank's head";
+      } else if (s.sel != 0) {
+        return "unknown segment source";
+      }
+      for (int64_t i = 0; i < s.len; i++) {
+        if (written[(size_t)(s.dst + i)]) return "a destination element is written twice";
+        written[(size_t)(s.dst + i)] = 1;
+        for (int c = 0; c < cw; c++) {
+          double x = 0.0;
+          if (s.sel == 1) x = v[((int64_t)b * p.count + s.src + i) * cw + c];
+          else if (s.sel == 2) x = halos[(s.rank * rank_stride + (int64_t)b * p.H + s.src + i) * cw + c];
+          dst[((int64_t)b * dlen + s.dst + i) * cw + c] = x;
+        }
+      }
+    }
+    for (char c : written)
+      if (!c) return "a destination element is never written";
+  }
+  return "";
+}
+
+std::string rdm_flat_shard_emulate(const RdmFlatShardPlan& p, int64_t ntri, int nblk, const double* v_shard, const double* slab,
+                                   int cw, double* tri) {
+  std::vector<double> partial((size_t)p.partial_entries * cw, 0.0);
+  std::vector<char> written((size_t)p.partial_entries, 0);
+  std::string why = emulate_tiles(p.in, ntri, p.count * nblk, v_shard, cw, p.partial_entries, partial, written);
+  if (why.empty() && p.tail_len > 0) why = emulate_tiles(p.slab, ntri, p.tail_len * nblk, slab, cw, p.partial_entries, partial, written);
+  return why.empty() ? emulate_final(p.groups, ntri, cw, p.partial_entries, partial, written, tri) : why;
+}
+
+std::string rdm_flat_world_emulate(const RdmFlatTables& t, int nblk, int cw, int target_wgs, int world, const double* v,
+                                   double* tri, int64_t* H_out) {
+  if (world < 1) return "bad world";
+  const int64_t dim = t.dim_el, q = (dim + world - 1) / world;
+  std::vector<RdmFlatShardPlan> plans((size_t)world);
+  for (int r = 0; r < world; r++) {
+    const std::string why = rdm_flat_shard_plan(t, nblk, cw, target_wgs, world, (int64_t)r * q, q, plans[(size_t)r]);
+    if (!why.empty()) return why;
+    if (plans[(size_t)r].H != plans[0].H || plans[(size_t)r].heads != plans[0].heads) return "the ranks disagree on the heads";
+  }
+  const int64_t H = plans[0].H;
+  if (H_out) *H_out = H;
+  // one owner per slab, every element read once
+  FlatSlabs sl;
+  flat_slabs(t, sl);
+  std::vector<int> owners(sl.bdw.size(), 0);
+  std::vector<int> reads((size_t)dim, 0);
+  auto slab_of = [&](int32_t bdw) { return (size_t)(std::find(sl.bdw.begin(), sl.bdw.end(), bdw) - sl.bdw.begin()); };
+  for (int r = 0; r < world; r++) {
+    const RdmFlatShardPlan& p = plans[(size_t)r];
+    int64_t walked = 0;
+    for (int32_t b : p.in.bdw) {
+      if (t.rowstart[(size_t)b << t.norb] == t.rowstart[(size_t)(b + 1) << t.norb]) continue;
+      const size_t j = slab_of(b);
+      if (j >= sl.bdw.size()) return "an interior slab that is no slab of the sector";
+      if (sl.start[j] < p.first || sl.start[j + 1] > p.first + p.count) return "an interior slab outside the range";
+      owners[j]++;
+      walked++;
+      for (int64_t i = sl.start[j]; i < sl.start[j + 1]; i++) reads[(size_t)i]++;
+    }
+    if (walked != p.nslab_in) return "the bath word lists do not hold the interior slabs";
+    if (p.tail_len > 0) {
+      const size_t j = slab_of(p.tail_bdw);
+      if (j >= sl.bdw.size() || sl.start[j] != p.first + p.tail_start || sl.start[j + 1] - sl.start[j] != p.tail_len)
+        return "the tail slab is no slab of the sector";
+      owners[j]++;
+      int64_t want = sl.start[j];
+      for (const RdmFlatSeg& s : p.fill) {
+        const int64_t g0 = s.sel == 1 ? p.first + s.src : s.sel == 2 ? std::min<int64_t>((int64_t)s.rank * q, dim) + s.src : -1;
+        if (g0 != want) return "the tail slab is not filled in order";
+        for (int64_t i = 0; i < s.len; i++) reads[(size_t)(g0 + i)]++;
+        want += s.len;
+      }
+      if (want != sl.start[j + 1]) return "the tail slab is not filled to its end";
+    }
+  }
+  for (int o : owners)
+    if (o != 1) return "a slab without exactly one owner";
+  for (int n : reads)
+    if (n != 1) return "an element that is not read exactly once";
+  // pack, all-gather
+  std::vector<std::vector<double>> shards((size_t)world);
+  std::vector<double> halos((size_t)(world * nblk * H * cw), 0.0);
+  for (int r = 0; r < world; r++) {
+    const RdmFlatShardPlan& p = plans[(size_t)r];
+    std::vector<double>& s = shards[(size_t)r];
+    s.resize((size_t)(p.count * nblk * cw));
+    for (int b = 0; b < nblk; b++)
+      for (int64_t i = 0; i < p.count * cw; i++) s[(size_t)(b * p.count * cw + i)] = v[((int64_t)b * dim + p.first) * cw + i];
+    if (H > 0) {
+      const std::string why = rdm_flat_segs_emulate(p, p.pack, H, nblk, cw, p.count > 0 ? s.data() : nullptr, nullptr,
+                                                    halos.data() + (size_t)r * nblk * H * cw);
+      if (!why.empty()) return why;
+    }
+  }
+  std::fill(tri, tri + t.ntri * cw, 0.0);
+  std::vector<double> mine((size_t)t.ntri * cw);
+  for (int r = 0; r < world; r++) {
+    const RdmFlatShardPlan& p = plans[(size_t)r];
+    std::vector<double> slab((size_t)(p.tail_len * nblk * cw));
+    if (p.tail_len > 0) {
+      const std::string why = rdm_flat_segs_emulate(p, p.fill, p.tail_len, nblk, cw, shards[(size_t)r].data(),
+                                                    H > 0 ? halos.data() : nullptr, slab.data());
+      if (!why.empty()) return why;
+    }
+    const std::string why = rdm_flat_shard_emulate(p, t.ntri, nblk, p.count > 0 ? shards[(size_t)r].data() : nullptr,
+                                                   p.tail_len > 0 ? slab.data() : nullptr, cw, mine.data());
+    if (!why.empty()) return why;
+    for (size_t i = 0; i < mine.size(); i++) tri[i] += mine[i];
   }
   return "";
 }

@@ -90,4 +90,57 @@ void rdm_flat_plan(const RdmFlatTables& t, int nblk, int cw, int target_wgs, Rdm
 // writes: "" on success, else the first violation.  nel = elements of the vector (nblk * dim_el).
 std::string rdm_flat_plan_emulate(const RdmFlatPlan& p, int64_t ntri, int64_t nel, const double* v, int cw, double* tri);
 
+// ---- a rank's elements [first, first + count) of the sector (edigpu_imp_rdm_flat_sharded) ----
+// The ranges are those of edigpu_shard_plan over the elements: q = ceil(dim_el / world) per rank, rank r starts at
+// min(r q, dim_el).  A SLAB is the 2^norb rows of one bath word down: a contiguous range of elements, which a rank
+// boundary cuts anywhere.  The rank in whose range a (non-empty) slab STARTS owns it:
+//   interior slabs lie wholly inside the range and are walked on the caller's shard in place: `in` is rdm_flat_plan with
+//            the bdw lists filtered to them, row starts relative to `first`, block stride `count`; with first = 0, count =
+//            dim_el it IS rdm_flat_plan;
+//   the head is the elements from `first` up to the first slab start inside the range (the whole range when no slab
+//            starts there): elements of a slab an earlier rank owns.  Every rank computes every rank's head, so the halo
+//            size H = max_r head(r) < the longest slab is known everywhere; a rank sends its head of every block, padded to H;
+//   the tail slab starts inside the range and ends beyond it: its owner copies its own last elements and the heads of the
+//            following ranks, in rank order (more than one rank when q < the slab's length), into a buffer of one slab per
+//            block, which the tiles kernel walks with the work list `slab`: rdm_flat_plan of that one bath word with row
+//            starts relative to the slab, block stride tail_len.
+// One table of segments describes a copy, for the halo (pack) and for the slab (fill) alike: len elements to dst of a
+// block of the destination from
+struct RdmFlatSeg {
+  int32_t sel = 0;   // 0: zeros, 1: src of the shard's block, 2: src of rank's halo block
+  int32_t rank = 0;
+  int64_t src = 0, dst = 0, len = 0;
+};
+struct RdmFlatShardPlan {
+  int world = 1, rank = 0;              // rank: -1 for a range that holds no element
+  int64_t first = 0, count = 0, q = 0;  // the range cut to the sector
+  int64_t H = 0;                        // elements of a rank's halo (the same on every rank)
+  std::vector<int64_t> heads;           // [world]
+  int64_t nslab_in = 0;                 // slabs walked in place
+  int64_t tail_start = -1, tail_len = 0, tail_own = 0;  // the slab this rank owns across its end: first element relative to
+  int32_t tail_bdw = -1;                                // `first`, length, elements held here, bath word; tail_len = 0: none
+  std::vector<RdmFlatSeg> pack, fill;   // the halo this rank sends (H elements), the slab (tail_len elements)
+  RdmFlatPlan in, slab;                 // work lists of the interior slabs and of the tail slab; their partial sums share
+  std::vector<RdmGroup> groups;         // one buffer: per group the workgroups of `in`, then those of `slab`
+  int64_t partial_entries = 0;
+};
+// "" on success; a message when (first, count) is not a rank's range of edigpu_shard_plan for `world` ranks
+std::string rdm_flat_shard_plan(const RdmFlatTables& t, int nblk, int cw, int target_wgs, int world, int64_t first,
+                                int64_t count, RdmFlatShardPlan& p);
+// The segment-copy kernel restated (kernels_rdm_flat.hip rdm_flat_seg_kernel), every index checked: dst[nblk][dlen] (cw
+// doubles per element) of one vector from the shard v[nblk][count] (null when count = 0) and the gathered halos
+// [world][nblk][H] (null for the pack); a halo element past its rank's head is a violation, and so is a destination
+// element written twice or never.
+std::string rdm_flat_segs_emulate(const RdmFlatShardPlan& p, const std::vector<RdmFlatSeg>& segs, int64_t dlen, int nblk, int cw,
+                                  const double* v, const double* halos, double* dst);
+// The two tile launches and the final sums restated as rdm_flat_plan_emulate does: `in` on the shard, `slab` on the
+// buffer [nblk][tail_len] (null when tail_len = 0), tri = this rank's packed sums.
+std::string rdm_flat_shard_emulate(const RdmFlatShardPlan& p, int64_t ntri, int nblk, const double* v_shard, const double* slab,
+                                   int cw, double* tri);
+// A whole world on the host: every rank's plan, pack, the all-gather, fill and launches on its shard of v[nblk][dim_el];
+// tri = the ranks' sums added in rank order; *H_out = the halo.  Checks on the way that every rank computes the same
+// heads, that every non-empty slab has one owner and that every element of the sector is read exactly once.
+std::string rdm_flat_world_emulate(const RdmFlatTables& t, int nblk, int cw, int target_wgs, int world, const double* v,
+                                   double* tri, int64_t* H_out);
+
 }  // namespace edigpu

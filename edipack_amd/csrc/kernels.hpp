@@ -356,5 +356,16 @@ size_t rdm_flat_lds_bytes(const RdmFlatArgs& a);
 // as launch_imp_rdm
 int launch_imp_rdm_flat(const RdmFlatArgs& a, int nwork, const RdmGroup* groups, int ngroups, const double* v, int64_t vstride,
                         int nvec, double* partial, int64_t pstride, double* out, int64_t ostride, hipStream_t st);
+// The same of a rank's elements (edigpu_imp_rdm_flat_sharded; host_rdm_flat.hpp RdmFlatShardPlan), as launch_imp_rdm_shard:
+// the work list of `in` on the shards v, that of `slab` (nslab workgroups, 0: none) on the tail slabs, their partial sums in
+// one buffer; the final sums run over the groups of both.
+int launch_imp_rdm_flat_shard(const RdmFlatArgs& in, int nin, const double* v, int64_t vstride, const RdmFlatArgs& slab, int nslab,
+                              const double* vslab, int64_t sstride, const RdmGroup* groups, int ngroups, int nvec, double* partial,
+                              int64_t pstride, double* out, int64_t ostride, hipStream_t st);
+// dst[nvec][nblk][dlen] (cw doubles per element) <- the nseg segments of the device table segs (the longest of maxlen
+// elements): of the shards v (vstride doubles apart, nblk blocks of `count` elements), of the gathered halos
+// [world][nvec][nblk][H], or zeros.  The halo a rank sends (RdmFlatShardPlan::pack, halos = null) and its tail slab (fill).
+int launch_rdm_flat_segs(const RdmFlatSeg* segs, int nseg, int64_t maxlen, int nblk, int cw, int nvec, const double* v,
+                         int64_t vstride, int64_t count, const double* halos, int64_t H, double* dst, int64_t dlen, hipStream_t st);
 
 }  // namespace edigpu

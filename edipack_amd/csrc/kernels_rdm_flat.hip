@@ -14,6 +14,9 @@
 //   at the end the workgroup writes its e1 - e0 sums to its own place.
 // rdm_flat_final_kernel adds the workgroups of a group in workgroup order (16 sub-ranges, then those in order): a fixed
 // order, no floating-point atomics, the same bits on every call.
+// Sharded vectors (edigpu_imp_rdm_flat_sharded; host_rdm_flat.hpp RdmFlatShardPlan): the same two kernels over two work
+// lists -- the interior slabs on the caller's shard in place, the tail slab in a buffer that rdm_flat_seg_kernel fills
+// from the shard and the gathered halos -- whose partial sums share one buffer.
 #include "kernels.hpp"
 
 namespace edigpu {
@@ -120,6 +123,24 @@ __global__ __launch_bounds__(64 * kRdmFlatFinalGroups) void rdm_flat_final_kerne
   }
 }
 
+// dst[vec][blk][s.dst + i] <- element s.src + i of the source segment s names (host_rdm_flat.hpp RdmFlatSeg, whose
+// rdm_flat_segs_emulate is this kernel on the host): the shard's block, a rank's gathered halo block, or zeros.  One double
+// per thread, consecutive threads on consecutive doubles of the segment on both sides (vectors may be 8-byte aligned
+// only, heads have any length and offset); blockIdx.y = block x segment, blockIdx.z = vector: the segment is uniform.
+__global__ __launch_bounds__(kRdmFlatThreads) void rdm_flat_seg_kernel(const RdmFlatSeg* __restrict__ segs, int nseg, int nblk,
+                                                                       int cw, const double* __restrict__ v, int64_t vstride,
+                                                                       int64_t count, const double* __restrict__ halos, int64_t H,
+                                                                       int64_t rank_stride, double* __restrict__ dst, int64_t dlen) {
+  const int b = blockIdx.y / nseg, k = blockIdx.z;
+  const RdmFlatSeg s = segs[blockIdx.y - b * nseg];
+  const int64_t i = (int64_t)blockIdx.x * kRdmFlatThreads + threadIdx.x;
+  if (i >= s.len * cw) return;
+  double x = 0.0;
+  if (s.sel == 1) x = v[k * vstride + ((int64_t)b * count + s.src) * cw + i];
+  else if (s.sel == 2) x = halos[s.rank * rank_stride + (((int64_t)k * nblk + b) * H + s.src) * cw + i];
+  dst[(((int64_t)k * nblk + b) * dlen + s.dst) * cw + i] = x;
+}
+
 }  // namespace
 
 size_t rdm_flat_lds_bytes(const RdmFlatArgs& a) {
@@ -127,10 +148,8 @@ size_t rdm_flat_lds_bytes(const RdmFlatArgs& a) {
   return doubles * sizeof(double) + (((size_t)a.rel_max * sizeof(uint16_t) + 15) & ~(size_t)15);
 }
 
-int launch_imp_rdm_flat(const RdmFlatArgs& a, int nwork, const RdmGroup* groups, int ngroups, const double* v, int64_t vstride,
-                        int nvec, double* partial, int64_t pstride, double* out, int64_t ostride, hipStream_t st) {
-  EDIGPU_HIP(hipMemsetAsync(out, 0, (size_t)nvec * ostride * sizeof(double), st));  // classes the sector does not hold
-  if (nwork <= 0) return 0;
+static int launch_flat_tiles(const RdmFlatArgs& a, int nwork, const double* v, int64_t vstride, int nvec, double* partial,
+                             int64_t pstride, hipStream_t st) {
   const size_t lds = rdm_flat_lds_bytes(a);
   const dim3 grid((unsigned)nwork, (unsigned)nvec);
   if (a.cw == 2) {
@@ -141,12 +160,49 @@ int launch_imp_rdm_flat(const RdmFlatArgs& a, int nwork, const RdmGroup* groups,
     rdm_flat_tiles_kernel<1><<<grid, kRdmFlatThreads, lds, st>>>(a, v, vstride, partial, pstride);
   }
   EDIGPU_HIP(hipGetLastError());
+  return 0;
+}
+
+static int launch_flat_final(const RdmGroup* groups, int ngroups, int cw, int nvec, const double* partial, int64_t pstride,
+                             double* out, int64_t ostride, hipStream_t st) {
   for (int k = 0; k < ngroups; k++) {
-    const int n = (groups[k].e1 - groups[k].e0) * a.cw;
+    const int n = (groups[k].e1 - groups[k].e0) * cw;
     rdm_flat_final_kernel<<<dim3((unsigned)((n + 63) / 64), (unsigned)nvec), 64 * kRdmFlatFinalGroups, 0, st>>>(
-        partial, pstride, groups[k], a.cw, out, ostride);
+        partial, pstride, groups[k], cw, out, ostride);
     EDIGPU_HIP(hipGetLastError());
   }
+  return 0;
+}
+
+int launch_imp_rdm_flat(const RdmFlatArgs& a, int nwork, const RdmGroup* groups, int ngroups, const double* v, int64_t vstride,
+                        int nvec, double* partial, int64_t pstride, double* out, int64_t ostride, hipStream_t st) {
+  EDIGPU_HIP(hipMemsetAsync(out, 0, (size_t)nvec * ostride * sizeof(double), st));  // classes the sector does not hold
+  if (nwork <= 0) return 0;
+  if (launch_flat_tiles(a, nwork, v, vstride, nvec, partial, pstride, st)) return 1;
+  return launch_flat_final(groups, ngroups, a.cw, nvec, partial, pstride, out, ostride, st);
+}
+
+int launch_imp_rdm_flat_shard(const RdmFlatArgs& in, int nin, const double* v, int64_t vstride, const RdmFlatArgs& slab, int nslab,
+                              const double* vslab, int64_t sstride, const RdmGroup* groups, int ngroups, int nvec, double* partial,
+                              int64_t pstride, double* out, int64_t ostride, hipStream_t st) {
+  EDIGPU_HIP(hipMemsetAsync(out, 0, (size_t)nvec * ostride * sizeof(double), st));  // classes the elements do not hold
+  if (nin > 0 && launch_flat_tiles(in, nin, v, vstride, nvec, partial, pstride, st)) return 1;
+  if (nslab > 0 && launch_flat_tiles(slab, nslab, vslab, sstride, nvec, partial, pstride, st)) return 1;
+  return launch_flat_final(groups, ngroups, in.cw, nvec, partial, pstride, out, ostride, st);
+}
+
+int launch_rdm_flat_segs(const RdmFlatSeg* segs, int nseg, int64_t maxlen, int nblk, int cw, int nvec, const double* v,
+                         int64_t vstride, int64_t count, const double* halos, int64_t H, double* dst, int64_t dlen, hipStream_t st) {
+  if (nseg <= 0 || maxlen <= 0 || nblk <= 0 || nvec <= 0) return 0;
+  const int64_t gx = (maxlen * cw + kRdmFlatThreads - 1) / kRdmFlatThreads;
+  if (gx > 0x7fffffff || (int64_t)nseg * nblk > 65535 || nvec > 65535) {
+    set_error("rdm_flat_segs: the copy does not fit a grid");
+    return 1;
+  }
+  const dim3 grid((unsigned)gx, (unsigned)(nseg * nblk), (unsigned)nvec);
+  rdm_flat_seg_kernel<<<grid, kRdmFlatThreads, 0, st>>>(segs, nseg, nblk, cw, v, vstride, count, halos, H,
+                                                        (int64_t)nvec * nblk * H * cw, dst, dlen);
+  EDIGPU_HIP(hipGetLastError());
   return 0;
 }
 

@@ -317,6 +317,34 @@ class LibraryComm:
                                                                  self._capi.pd(nrm)), "edigpu_imp_rdm_sharded")
         return rho, nrm
 
+    def imp_rdm_flat(self, h, v_shard, nvec: int = 1):
+        """SectorHamiltonian.imp_rdm_flat of nvec vectors held as row shards of a superc / nonsu2 sector: (rho[nvec, D, D],
+        norm2[nvec]), D = 4^norb, the reference's fermionic sign, not normalised, complex on complex handles -- what
+        rdm_average, rdm_anomalous, rdm_magx and entanglement_entropy of edipack_amd.observables take.  The sums over all
+        ranks, the same bits on every rank.  Collective: a slab (the rows of one bath word down) that a rank boundary cuts
+        is completed by one all-gather of less than a slab per rank."""
+        import ctypes as C
+        import numpy as np
+        D = 4 ** (h.norb or self._capi.MAXORB)
+        rho = np.zeros((nvec, D, D), dtype=np.complex128 if h.is_complex else np.float64)
+        nrm = np.zeros(nvec)
+        p, _keep = self._shard_ptr(h, v_shard)
+        self._capi.check(self._capi.lib().edigpu_imp_rdm_flat_sharded(h._h, self._c, p, nvec,
+                                                                      rho.ctypes.data_as(C.POINTER(C.c_double)),
+                                                                      self._capi.pd(nrm)), "edigpu_imp_rdm_flat_sharded")
+        return rho, nrm
+
+    def imp_rdm_flat_info(self, h):
+        """The geometry of imp_rdm_flat on this rank, host only: dict(H = the padded halo in elements (the same on every
+        rank), gather_doubles = what this rank contributes to the all-gather per vector, slabs_in_place, tail_start (relative
+        to the rank's first element, -1: no tail slab), tail_len, tail_own)."""
+        import ctypes as C
+        import numpy as np
+        info = np.zeros(6, np.int64)
+        self._capi.check(self._capi.lib().edigpu_imp_rdm_flat_sharded_info(h._h, self._c, info.ctypes.data_as(C.POINTER(C.c_int64))),
+                         "edigpu_imp_rdm_flat_sharded_info")
+        return dict(zip(("H", "gather_doubles", "slabs_in_place", "tail_start", "tail_len", "tail_own"), (int(x) for x in info)))
+
     def bench(self, h, warmup: int, steps: int):
         """(ms per sharded Lanczos step, bytes this rank sends per product)."""
         import ctypes as C

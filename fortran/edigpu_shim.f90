@@ -478,6 +478,20 @@ module EDIGPU_SHIM
        real(c_double), intent(inout) :: rdm(*), norm2(*)
        integer(c_int) :: ierr
      end function edigpu_imp_rdm_sharded
+     function edigpu_imp_rdm_flat_sharded(h, c, v_shard, nvec, rdm, norm2) bind(C, name="edigpu_imp_rdm_flat_sharded") &
+          result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h, c, v_shard
+       integer(c_int), value :: nvec
+       real(c_double), intent(inout) :: rdm(*), norm2(*)
+       integer(c_int) :: ierr
+     end function edigpu_imp_rdm_flat_sharded
+     function edigpu_imp_rdm_flat_sharded_info(h, c, info) bind(C, name="edigpu_imp_rdm_flat_sharded_info") result(ierr)
+       import :: c_ptr, c_int, c_int64_t
+       type(c_ptr), value :: h, c
+       integer(c_int64_t), intent(inout) :: info(6)
+       integer(c_int) :: ierr
+     end function edigpu_imp_rdm_flat_sharded_info
      function edigpu_destroy(h) bind(C, name="edigpu_destroy") result(ierr)
        import :: c_ptr, c_int
        type(c_ptr), value :: h
@@ -512,7 +526,7 @@ module EDIGPU_SHIM
   public :: gpu_sp_eigh_mpi_d, gpu_sp_eigh_mpi_c, gpu_apply_op_mpi_d
   ! observables and the chi_spin / chi_dens / phonon seeds on the shards the MPI solve leaves
   public :: gpu_occ_moments_mpi, gpu_apply_op_N_mpi, gpu_apply_op_Sz_mpi, gpu_apply_xph_mpi, gpu_ph_rdm_mpi
-  public :: gpu_imp_rdm_mpi
+  public :: gpu_imp_rdm_mpi, gpu_imp_rdm_flat_mpi, gpu_imp_rdm_flat_mpi_info
   ! the Green's-function and pair seeds on those shards (phonon and complex sectors included)
   public :: gpu_apply_cops_mpi_d, gpu_apply_cops_mpi_c, gpu_apply_pairs_mpi
 
@@ -1375,6 +1389,32 @@ contains
     if (size(rho, 3) /= size(nrm) .or. size(rho, 1) /= size(rho, 2)) stop "gpu_imp_rdm_mpi: shapes"
     call gpu_check(edigpu_imp_rdm_sharded(h, gpu_comm, v_shard, int(size(nrm), c_int), rho, nrm), "gpu_imp_rdm_mpi")
   end subroutine gpu_imp_rdm_mpi
+
+  !> gpu_imp_rdm_flat of size(nrm) REAL vectors held as row shards of a superc / nonsu2 sector (imp_rdm_superc,
+  !! ED_RDM_SUPERC.f90:54-183, and imp_rdm_nonsu2, ED_RDM_NONSU2.f90:54-188, under -D_MPI without es_return_dvector_mpi):
+  !! rho(io, jo, k) as gpu_imp_rdm_flat returns it, the sums over all ranks, the same bits on every rank.  h: this rank's
+  !! row shard (gpu_build_flat with the first / count of gpu_shard_plan); v_shard: its elements, block after block on
+  !! phonon sectors, host or device, c_null_ptr on a rank without rows.  Complex handles return interleaved (re, im): call
+  !! edigpu_imp_rdm_flat_sharded.  Collective.
+  subroutine gpu_imp_rdm_flat_mpi(h, v_shard, rho, nrm)
+    type(c_ptr), intent(in) :: h, v_shard
+    real(8), intent(inout) :: rho(:, :, :), nrm(:)
+    if (.not. c_associated(gpu_comm)) stop "gpu_imp_rdm_flat_mpi: no communicator"
+    if (size(rho, 3) /= size(nrm) .or. size(rho, 1) /= size(rho, 2)) stop "gpu_imp_rdm_flat_mpi: shapes"
+    call gpu_check(edigpu_imp_rdm_flat_sharded(h, gpu_comm, v_shard, int(size(nrm), c_int), rho, nrm), "gpu_imp_rdm_flat_mpi")
+  end subroutine gpu_imp_rdm_flat_mpi
+
+  !> Its geometry on this rank, host only: info = (halo H in elements, doubles sent to the all-gather per vector, slabs
+  !! walked in place, first element of the tail slab relative to the rank's first or -1, its length, its elements held here)
+  subroutine gpu_imp_rdm_flat_mpi_info(h, info)
+    type(c_ptr), intent(in) :: h
+    integer(8), intent(out) :: info(6)
+    integer(c_int64_t) :: cinfo(6)
+    if (.not. c_associated(gpu_comm)) stop "gpu_imp_rdm_flat_mpi_info: no communicator"
+    cinfo = 0
+    call gpu_check(edigpu_imp_rdm_flat_sharded_info(h, gpu_comm, cinfo), "gpu_imp_rdm_flat_mpi_info")
+    info = cinfo
+  end subroutine gpu_imp_rdm_flat_mpi_info
 
   !> delete_Hv_sector_* counterpart (ED_NORMAL/ED_HAMILTONIAN_NORMAL.f90:212-279)
   subroutine gpu_delete_sector()

@@ -896,6 +896,31 @@ int edigpu_ph_rdm_sharded(edigpu_handle h, edigpu_comm c, const double *v_shard,
  */
 int edigpu_imp_rdm_sharded(edigpu_handle h, edigpu_comm c, const double *v_shard, int nvec, double *rdm_host,
                            double *norm2_host);
+/*
+ * edigpu_imp_rdm_flat on shards (imp_rdm_superc / imp_rdm_nonsu2 under -D_MPI, rdm_flag=T, without es_return_dvector_mpi):
+ * h is the rank's row shard of a superc or nonsu2 sector, stored (edigpu_flat_build) or on the fly (edigpu_direct_build),
+ * with the first / count of edigpu_shard_plan (over the electronic dimension when the handle has phonons); real or
+ * complex, phonon blocks traced, Norb <= 4.  v_shard: nvec consecutive shards in the layout of the sharded product,
+ * count (Nph + 1) elements each, block after block of the rank's rows, interleaved (re, im) on complex handles; host or
+ * device memory, read only; NULL on a rank that owns no row.  A tile needs the whole slab of a bath word down -- its 2^Norb
+ * consecutive rows, a contiguous range of elements -- and a rank boundary cuts anywhere in it: every rank sends the
+ * elements at the start of its range that belong to a slab begun on an earlier rank (fewer than one slab, the same padded
+ * count H on every rank, known without communication; one all-gather, skipped everywhere when H = 0), the rank a cut slab
+ * starts on completes it, and one all-reduce adds the packed triangles.  Collective.  Every rank receives nvec matrices
+ * and traces as edigpu_imp_rdm_flat returns them (D = 4^Norb, io = Iup + 2^Norb Idw, the reference's fermionic sign, not
+ * normalised, exactly Hermitian; norm2_host may be NULL), bit-identical on every rank and from call to call, the same
+ * bits from stored and on-the-fly shard handles; a world of one returns the bits of edigpu_imp_rdm_flat.  Refused before
+ * any collective, on every rank alike: normal-mode handles (use edigpu_imp_rdm_sharded), JZ_BASIS sectors, ed_total_ud=F
+ * and hand-over handles, Norb = 5, nvec <= 0, NULL arguments, a handle whose first / count are not this rank's range of
+ * the communicator, and what the sharded product refuses of a handle.
+ * _info runs the same checks and touches no device: info[0] = H, the padded halo in elements; info[1] = the doubles this
+ * rank contributes to the all-gather per call with nvec = 1 (0 when H = 0); info[2] = the slabs this rank walks in place;
+ * info[3] = the first element, relative to first, of the tail slab it completes, or -1; info[4] = that slab's length;
+ * info[5] = how many of its elements are the rank's own.
+ */
+int edigpu_imp_rdm_flat_sharded(edigpu_handle h, edigpu_comm c, const double *v_shard, int nvec, double *rdm_host,
+                                double *norm2_host);
+int edigpu_imp_rdm_flat_sharded_info(edigpu_handle h, edigpu_comm c, int64_t info[6]);
 /* bench.py --gpus N: `warmup` + `steps` sharded Lanczos steps on a seeded random vector; wall time per step between
  * two collectives that act as barriers, and the bytes this rank sends per product */
 int edigpu_lanczos_bench_sharded(edigpu_handle h, edigpu_comm c, int warmup, int steps, double *ms_per_step,

@@ -15,11 +15,12 @@ it (wall clock, once); for the flat sectors the restatement is tests/rdm_flat_ca
 
     python scripts/time_rdm.py [--workloads cfg2,cfg3_ns16 | cfg5,superc_ns13] [--steps 21]
 
---sharded (normal-mode sectors only) times edigpu_imp_rdm_sharded instead: a world of ONE rank on the RCCL communicator
-with its collectives forced (EDIGPU_FORCE_COLLECTIVES=1), the vector passed as a device pointer, against edigpu_imp_rdm
-on the same vector -- both as whole calls by the wall clock (kernels, the download of the packed result, its placement),
-medians of --steps calls after --warmup.  A one-GPU rehearsal of the calls, not a scaling measurement: the line goes
-into profiles/rdm.json under "sharded_rehearsal".
+--sharded times edigpu_imp_rdm_sharded instead (the flat workloads: edigpu_imp_rdm_flat_sharded): a world of ONE rank on
+the RCCL communicator with its collectives forced (EDIGPU_FORCE_COLLECTIVES=1), the vector passed as a device pointer,
+against edigpu_imp_rdm (edigpu_imp_rdm_flat) on the same vector -- both as whole calls by the wall clock (kernels, the
+download of the packed result, its placement), medians of --steps calls after --warmup.  A one-GPU rehearsal of the
+calls, not a scaling measurement: the line goes into profiles/rdm.json under "sharded_rehearsal" (the flat workloads:
+"flat_sharded_rehearsal").
 """
 import argparse
 import ctypes as C
@@ -73,25 +74,28 @@ def sharded_rehearsal(args):
     import torch
     from edipack_amd import capi
     from edipack_amd.sharding import LibraryComm
-    from edipack_amd.synthetic import WORKLOADS, build_workload
+    from edipack_amd.synthetic import WORKLOADS, Workload, build_workload
+    workloads = dict(WORKLOADS)
+    workloads["superc_ns13"] = SUPERC_NS13(Workload)
     capi.init(0)
     comm = LibraryComm(0, 1, unique_id=LibraryComm.unique_id())
     out = {"script": "scripts/time_rdm.py --sharded", "kernel_source_hash": capi.kernel_source_hash(), "steps": args.steps,
            "warmup": args.warmup, "world": 1, "collectives": "forced (RCCL)", "sectors": []}
     for name in args.workloads.split(","):
-        w = WORKLOADS[name]
-        if w.ed_mode != "normal":
-            raise SystemExit("time_rdm.py --sharded: normal-mode workloads only")
+        w = workloads[name]
+        flat = w.ed_mode != "normal"
         h = build_workload(w)
+        one, sharded, kernels = (h.imp_rdm_flat, comm.imp_rdm_flat, h.time_rdm_flat) if flat else (h.imp_rdm, comm.imp_rdm, h.time_rdm)
         gen = torch.Generator(device="cuda").manual_seed(1234)
         v = torch.randn(h.dim * (2 if h.is_complex else 1), dtype=torch.float64, device="cuda", generator=gen)
         torch.cuda.synchronize()
-        rho, n2 = h.imp_rdm(v.data_ptr())
-        rho_s, n2_s = comm.imp_rdm(h, v.data_ptr())
-        ms_one = wall_median_ms(lambda: h.imp_rdm(v.data_ptr()), args.warmup, args.steps)
-        ms_sh = wall_median_ms(lambda: comm.imp_rdm(h, v.data_ptr()), args.warmup, args.steps)
-        ms_kernels = h.time_rdm(v.data_ptr(), args.warmup, args.steps)
-        out["sectors"].append({"workload": name, "note": w.note, "dim": h.dim, "norb": h.norb,
+        rho, n2 = one(v.data_ptr())
+        rho_s, n2_s = sharded(h, v.data_ptr())
+        ms_one = wall_median_ms(lambda: one(v.data_ptr()), args.warmup, args.steps)
+        ms_sh = wall_median_ms(lambda: sharded(h, v.data_ptr()), args.warmup, args.steps)
+        ms_kernels = kernels(v.data_ptr(), args.warmup, args.steps)
+        out["sectors"].append({"workload": name, "entry": "edigpu_imp_rdm_flat_sharded" if flat else "edigpu_imp_rdm_sharded",
+                               "note": w.note, "dim": h.dim, "norb": h.norb,
                                "imp_rdm_call_ms": ms_one, "imp_rdm_sharded_call_ms": ms_sh, "ratio": ms_sh / ms_one,
                                "imp_rdm_kernels_ms": ms_kernels,
                                "same_bits": bool(np.array_equal(rho, rho_s) and np.array_equal(n2, n2_s))})
@@ -102,12 +106,16 @@ def sharded_rehearsal(args):
     print(json.dumps(out))
 
 
+def SUPERC_NS13(Workload):
+    return Workload("superc_ns13", 4, "superc", "hybrid", 2, 11, 0, "Ns=13, Sz=0, Dim=10 400 600, direct", True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="cfg2,cfg3_ns16")
     ap.add_argument("--steps", type=int, default=21)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--sharded", action="store_true", help="one-rank rehearsal of edigpu_imp_rdm_sharded against edigpu_imp_rdm")
+    ap.add_argument("--sharded", action="store_true", help="one-rank rehearsal of edigpu_imp_rdm[_flat]_sharded against edigpu_imp_rdm[_flat]")
     args = ap.parse_args()
     if args.sharded:
         return sharded_rehearsal(args)
@@ -115,7 +123,7 @@ def main():
     from edipack_amd import capi
     from edipack_amd.synthetic import WORKLOADS, Workload, build_workload, synthetic_model
     workloads = dict(WORKLOADS)
-    workloads["superc_ns13"] = Workload("superc_ns13", 4, "superc", "hybrid", 2, 11, 0, "Ns=13, Sz=0, Dim=10 400 600, direct", True)
+    workloads["superc_ns13"] = SUPERC_NS13(Workload)
     if capi.device_count() < 1:
         raise SystemExit("time_rdm.py: no HIP device (there is nothing to time on a CPU)")
     capi.init(0)
