@@ -133,6 +133,10 @@ SIGNATURES = {
     "edigpu_apply_pairs_normal": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _pd, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32, _vp]),
     "edigpu_time_pairs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _pd, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32, C.c_int,
                                     C.c_int, _pd]),
+    "edigpu_twin_sector": (C.c_int, [C.POINTER(EdigpuModel), C.c_int, C.c_int, C.c_int, _pint, _pint, _pint]),
+    "edigpu_apply_twin": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "edigpu_time_twin": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _pd]),
+    "edigpu_apply_twin_sharded": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "edigpu_vec_work_doubles": (C.c_int, []),
     "edigpu_vec_rotate": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
     "edigpu_vec_add_dot": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),

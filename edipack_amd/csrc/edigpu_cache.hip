@@ -43,8 +43,9 @@ static int64_t handle_bytes_estimate(int64_t free_before, edigpu_handle h) {
   int64_t info[10] = {0};
   (void)edigpu_info(h, info);
   // + the Lanczos workspace the first recurrence on the handle allocates (three vectors) and the tables the first
-  // edigpu_apply_occ / edigpu_occ_moments and the first edigpu_imp_rdm upload
-  return built + 3 * info[1] * (info[3] ? 16 : 8) + edigpu::occ_table_bytes(h) + edigpu::rdm_table_bytes(h);
+  // edigpu_apply_occ / edigpu_occ_moments, the first edigpu_imp_rdm and the first edigpu_apply_twin upload
+  return built + 3 * info[1] * (info[3] ? 16 : 8) + edigpu::occ_table_bytes(h) + edigpu::rdm_table_bytes(h) +
+         edigpu::twin_table_bytes(h);
 }
 
 extern "C" {

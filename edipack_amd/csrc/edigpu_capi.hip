@@ -319,6 +319,7 @@ int edigpu_destroy(edigpu_handle s) {
   free_rdm_flat(s);
   free_ph(s);
   free_axisop(s);
+  free_twin(s);
   free_batch(s);
   dev_free_all(s->d_vin, s->d_vout, s->d_tmp, s->d_partial, s->d_scal);
   delete s;

@@ -306,6 +306,17 @@ int pairs_shard_tables(const edigpu_sector* src, const edigpu_sector* dst, int n
 int pairs_shard_call(const edigpu_sector* src, const PairsTables& tab, const ShardWindow* win, int64_t rows, const double* v_src,
                      double* v_dst, hipStream_t st);
 
+// The table `order` of twin_sector_order of a library-built superc sector (host_twin.hpp; kernels_twin.hip), made and
+// uploaded by the first edigpu_apply_twin[_sharded] with the handle as SOURCE and kept until edigpu_destroy: n entries,
+// the electronic rows of the whole sector (also on a row shard: a rank's window of the destination reads any of them).
+struct TwinDev {
+  int64_t n = 0;
+  int32_t* order = nullptr;
+};
+void free_twin(edigpu_sector* s);
+// device bytes of that table (made lazily: the sector cache adds them like occ_table_bytes)
+int64_t twin_table_bytes(const edigpu_sector* s);
+
 // Interleaved workspace of edigpu_apply_multi_dev / edigpu_lanczos_tridiag_batch_dev (edigpu_batch.hip; kernels_multi.hip):
 // two buffers of W vectors, the per-column partial sums and scalars.  Allocated by the first batch call on the handle,
 // grown when a later call needs more, kept until edigpu_destroy.
@@ -433,6 +444,8 @@ struct edigpu_sector {
   edigpu::PhDev* ph_shard = nullptr;    // the view of a rank's rows
   // ---- c / c^+ along one axis: table scratch of calls with this handle as destination (lazily built) ----
   edigpu::AxisDev* axis = nullptr;
+  // ---- ED_TWIN=T reorder: the superc order table of calls with this handle as source (lazily built) ----
+  edigpu::TwinDev* twin = nullptr;
   // ---- interleaved vectors of the batched product and recurrence (lazily built) ----
   edigpu::BatchDev* batch = nullptr;
   int batch_force_w = 0;         // edigpu_batch_set_width: 2, 4, 8 = the widest group whatever the size (measurement hook)

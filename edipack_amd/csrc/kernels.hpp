@@ -313,6 +313,22 @@ int launch_apply_axisop(const AxisArgs& a, int cplx_coef, const double* src, dou
 int launch_apply_axisop_window(const AxisArgs& a, const ShardWindow& w, int cplx_coef, const double* src, double* dst,
                                hipStream_t st);
 
+// ---- the ED_TWIN=T reorder: a twin sector's vectors from the stored sector's (kernels_twin.hip; host_twin.hpp) ----
+// Elements are doubles, or (cplx) double2; src and dst may be 8-byte aligned only (16-byte accesses where they allow).
+// Enqueued on st, no synchronisation; dst must not overlap src; every element of dst is written once.
+// normal mode: nvec vectors [nblk][R][C] (C fastest) -> [nblk][C][R]
+int launch_twin_transpose(int cplx, int64_t R, int64_t C, int nblk, int nvec, const void* src, void* dst, hipStream_t st);
+// superc / nonsu2: dst[b n + i] = src[b n + order[i]], b over the nvec * nblk blocks; order == null: src[b n + n - 1 - i]
+int launch_twin_gather(int cplx, int64_t n, int nblk, int nvec, const int32_t* order, const void* src, void* dst, hipStream_t st);
+// The window + source forms (shard_src.hpp ShardWindow): dst = the rows [w.j_first, w.j_first + w.j_count) of the
+// destination (its down rows = the source's up columns; rows of superc / nonsu2) as [nvec][nblk][j_count][..]; src = the
+// all-gather of the ranks' parts, each nvec vectors of vstride = q unit_len nblk elements (w.s counted in elements, w.s.chunk
+// = nvec vstride, w.s.units = R / n, w.s.unit_len = C / 1)
+int launch_twin_transpose_window(int cplx, int64_t R, int64_t C, int nvec, const ShardWindow& w, int64_t vstride, const void* src,
+                                 void* dst, hipStream_t st);
+int launch_twin_gather_window(int cplx, int64_t n, int nvec, const ShardWindow& w, int64_t vstride, const int32_t* order,
+                              const void* src, void* dst, hipStream_t st);
+
 // ---- impurity reduced density matrix (kernels_rdm.hip; tables and work list: host_rdm.hpp) ----
 struct RdmArgs {  // the device copies of an RdmPlan
   int cw = 1, stride = 0, ld_max = 0, ept_max = 0, rel_max = 0;

@@ -183,6 +183,16 @@ def pairs_sector(model: "ImpurityModel", nup: int, ndw: int, terms):
     return a.value, b.value, bool(e.value)
 
 
+def twin_sector(model: "ImpurityModel", mode: int, q1: int, q2: int = 0):
+    """(tq1, tq2, self_twin) of get_twin_sector (ED_SECTOR.f90:1824-1843): mode 0 normal (Nup, Ndw) -> (Ndw, Nup),
+    1 superc Sz -> -Sz, 2 nonsu2 Ntot -> 2 Ns - Ntot (q2 ignored, tq2 = 0).  Host only."""
+    cm = model.to_c()
+    a, b, e = C.c_int(0), C.c_int(0), C.c_int(0)
+    capi.check(capi.lib().edigpu_twin_sector(C.byref(cm), int(mode), int(q1), int(q2), C.byref(a), C.byref(b), C.byref(e)),
+               "edigpu_twin_sector")
+    return a.value, b.value, bool(e.value)
+
+
 def _csr_args(rowptr, col, val, cplx=False):
     rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
     col = np.ascontiguousarray(col, dtype=np.int32)
@@ -549,6 +559,21 @@ class SectorHamiltonian:
         capi.check(capi.lib().edigpu_time_pairs(self._h, dst._h, v_src_ptr, v_dst_ptr, *_pairs_args(terms), warmup, steps, ms),
                    "edigpu_time_pairs")
         return float(ms[0]), float(ms[1])
+
+    # ---- ED_TWIN=T: the twin sector's vectors from this sector's (edigpu_apply_twin) -------------
+    def twin_to(self, dst: "SectorHamiltonian", v_src_ptr: int, v_dst_ptr: int, nvec: int = 1, stream: int = 0) -> None:
+        """es_return_dvector's reorder on device vectors: nvec consecutive vectors of this sector at v_src_ptr -> nvec of
+        its twin sector `dst` at v_dst_ptr (dst may be self for a self-twin sector; the vectors must not overlap).
+        Enqueued on `stream`, no synchronisation.  Pure data movement: the same bits."""
+        capi.check(capi.lib().edigpu_apply_twin(self._h, dst._h, v_src_ptr, v_dst_ptr, int(nvec), stream if stream else None),
+                   "edigpu_apply_twin")
+
+    def time_twin(self, dst: "SectorHamiltonian", v_src_ptr: int, v_dst_ptr: int, warmup: int, steps: int) -> float:
+        """ms of one twin_to of one vector: the median over `steps` runs, HIP events."""
+        ms = C.c_double(0.0)
+        capi.check(capi.lib().edigpu_time_twin(self._h, dst._h, v_src_ptr, v_dst_ptr, warmup, steps, C.byref(ms)),
+                   "edigpu_time_twin")
+        return float(ms.value)
 
     # ---- operators diagonal in the occupation basis (edigpu_apply_occ, edigpu_occ_moments) -----
     def apply_occ(self, v_src_ptr: int, v_dst_ptr: int, w_up, w_dw, stream: int = 0) -> None:

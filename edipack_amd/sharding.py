@@ -222,6 +222,15 @@ class LibraryComm:
                          "edigpu_apply_pairs_sharded_info")
         return int(info[0]), int(info[1])
 
+    def apply_twin(self, src, dst, v_src_shard, nloc_dst: int, nvec: int = 1, out=None):
+        """SectorHamiltonian.twin_to on shards (ED_TWIN=T): nvec vectors of this rank's shard of sector `src` ([nvec, nloc]
+        numpy, or a device pointer with `out`) -> this rank's shard of the twin sector `dst` ([nvec, nloc_dst]; nloc_dst = 0
+        on a rank that owns no destination row).  Normal mode (real, phonon, complex): whole-sector handles; superc /
+        nonsu2: row shards.  Collective: one all-gather of the source shards; the stitched shards are the single-GPU bits."""
+        res = self._seed_call(self._capi.lib().edigpu_apply_twin_sharded, "edigpu_apply_twin_sharded", src, dst, v_src_shard,
+                              nloc_dst * nvec, (int(nvec),), out)
+        return res if res is None else res.reshape(nvec, nloc_dst)
+
     # ---- occupation and phonon observables, impurity density matrix on shards (csrc/edigpu_shard_obs.hip) -----
     # A shard is a numpy array of this rank's elements (several vectors: [nvec, nloc]) or an int, the address of
     # the same on the device -- e.g. the evecs of eigh_multi uploaded, or a torch tensor's data_ptr().  The library

@@ -298,6 +298,25 @@ module EDIGPU_SHIM
        integer(c_int32_t), intent(in) :: create1(*), iorb1(*), ispin1(*), create2(*), iorb2(*), ispin2(*)
        integer(c_int) :: ierr
      end function edigpu_apply_pairs_normal
+     function edigpu_twin_sector(model, mode, q1, q2, tq1, tq2, self_twin) bind(C, name="edigpu_twin_sector") result(ierr)
+       import :: c_int, edigpu_model_t
+       type(edigpu_model_t), intent(in) :: model
+       integer(c_int), value :: mode, q1, q2
+       integer(c_int), intent(out) :: tq1, tq2, self_twin
+       integer(c_int) :: ierr
+     end function edigpu_twin_sector
+     function edigpu_apply_twin(src, dst, v_src_dev, v_dst_dev, nvec, stream) bind(C, name="edigpu_apply_twin") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: src, dst, v_src_dev, v_dst_dev, stream
+       integer(c_int), value :: nvec
+       integer(c_int) :: ierr
+     end function edigpu_apply_twin
+     function edigpu_apply_twin_sharded(src, dst, c, v_src, v_dst, nvec) bind(C, name="edigpu_apply_twin_sharded") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: src, dst, c, v_src, v_dst
+       integer(c_int), value :: nvec
+       integer(c_int) :: ierr
+     end function edigpu_apply_twin_sharded
      function edigpu_info(h, info) bind(C, name="edigpu_info") result(ierr)
        import :: c_ptr, c_int, c_int64_t
        type(c_ptr), value :: h
@@ -519,6 +538,7 @@ module EDIGPU_SHIM
   public :: gpu_sp_lanc_eigh_dev, gpu_apply_op, gpu_apply_cops, gpu_lanc_tridiag_dev, gpu_lanc_tridiag_batch_dev
   public :: gpu_apply_op_N, gpu_apply_op_Sz, gpu_occ_moments, gpu_imp_rdm, gpu_imp_rdm_flat
   public :: gpu_apply_pairs
+  public :: gpu_twin_sector, gpu_apply_twin, gpu_apply_twin_mpi
   public :: gpu_apply_cops_z
   ! N > 1: communicator + the MPI twins of the product and of the tridiagonalisation
   public :: gpu_comm_unique_id, gpu_comm_create, gpu_comm_create_shm, gpu_comm_destroy, gpu_shard_plan
@@ -1317,6 +1337,42 @@ contains
     call gpu_check(edigpu_apply_pairs_sharded(hsrc, hdst, gpu_comm, v_shard, vv_shard, int(size(Os1), c_int), coefs, o1, io1, &
          is1, o2, io2, is2), "gpu_apply_pairs_mpi")
   end subroutine gpu_apply_pairs_mpi
+
+  !> get_twin_sector (ED_SECTOR.f90:1824-1843) from the quantum numbers: mode 0 normal (Nup, Ndw) -> (Ndw, Nup), 1 superc
+  !! Sz -> -Sz, 2 nonsu2 Ntot -> 2 Ns - Ntot (q2 ignored, tq2 = 0); self_twin: the sector is its own twin.  Host only.
+  !! Compile-checked only.
+  subroutine gpu_twin_sector(m, mode, q1, q2, tq1, tq2, self_twin)
+    type(edigpu_model_t), intent(in) :: m
+    integer, intent(in) :: mode, q1, q2
+    integer, intent(out) :: tq1, tq2
+    logical, intent(out) :: self_twin
+    integer(c_int) :: a, b, e
+    call gpu_check(edigpu_twin_sector(m, int(mode, c_int), int(q1, c_int), int(q2, c_int), a, b, e), "gpu_twin_sector")
+    tq1 = int(a); tq2 = int(b); self_twin = e /= 0
+  end subroutine gpu_twin_sector
+
+  !> The loop vector(i) = twin%dvec(Order(i)) of es_return_dvector / es_return_cvector (ED_EIGENSPACE.f90:652-720) on
+  !! device vectors: nvec consecutive vectors of the stored sector hsrc at v_src_dev -> nvec of its twin sector hdst at
+  !! v_dst_dev (hdst may be hsrc for a self-twin sector; the vectors must not overlap).  Enqueued on the null stream, no
+  !! synchronisation: the calls that follow on the handles' streams wait for the device themselves only when they return
+  !! data, so a host that reads v_dst_dev next synchronises first (gpu_dev_download does).  Compile-checked only.
+  subroutine gpu_apply_twin(hsrc, hdst, v_src_dev, v_dst_dev, nvec)
+    type(c_ptr), intent(in) :: hsrc, hdst, v_src_dev, v_dst_dev
+    integer, intent(in) :: nvec
+    call gpu_check(edigpu_apply_twin(hsrc, hdst, v_src_dev, v_dst_dev, int(nvec, c_int), c_null_ptr), "gpu_apply_twin")
+  end subroutine gpu_apply_twin
+
+  !> gpu_apply_twin on shards, in place of the gather of es_return_dvector_mpi (ED_EIGENSPACE.f90:723-793): v_shard = this
+  !! rank's shard(s) of nvec vectors of sector hsrc, consecutive with stride Nloc (c_loc of eig_basis, or a device vector;
+  !! c_null_ptr on a rank without rows), vv_shard receives its shard(s) of the twin sector hdst.  Normal mode: whole-sector
+  !! handles; superc / nonsu2: row shards.  Collective: one all-gather.  Returns after the device has finished.
+  !! Compile-checked only.
+  subroutine gpu_apply_twin_mpi(hsrc, hdst, v_shard, vv_shard, nvec)
+    type(c_ptr), intent(in) :: hsrc, hdst, v_shard, vv_shard
+    integer, intent(in) :: nvec
+    if (.not. c_associated(gpu_comm)) stop "gpu_apply_twin_mpi: no communicator"
+    call gpu_check(edigpu_apply_twin_sharded(hsrc, hdst, gpu_comm, v_shard, vv_shard, int(nvec, c_int)), "gpu_apply_twin_mpi")
+  end subroutine gpu_apply_twin_mpi
 
   !> gpu_occ_moments on shards, on the module's communicator: v_shard = this rank's shard(s) of size(norm2) vectors of
   !! sector h, consecutive with stride Nloc as gpu_sp_eigh_mpi_* leaves eig_basis (c_loc of it, or a device vector;

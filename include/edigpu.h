@@ -682,6 +682,45 @@ int edigpu_time_pairs(edigpu_handle src, edigpu_handle dst, const double *v_src_
                       const int32_t *create2, const int32_t *iorb2, const int32_t *ispin2, int warmup, int steps, double *ms2);
 
 /*
+ * ED_TWIN=T: the vector of a twin sector from the vector of the stored sector, on the device.  With ed_twin=T the
+ * reference diagonalises one sector of each pair -- normal (Nup, Ndw) / (Ndw, Nup), superc Sz / -Sz, nonsu2 Ntot /
+ * 2 Ns - Ntot (get_twin_sector, ED_SECTOR.f90:1824-1843) -- and makes the partner's vector on demand
+ * (es_return_dvector, ED_EIGENSPACE.f90:652-720): vector(i) = twin%dvec(Order(i)), Order = twin_sector_order
+ * (ED_SECTOR.f90:1747-1776) = argsort(flip(state_A(.))), no sign, phonon block by phonon block.
+ *
+ *   v_dst[b n + i] = v_src[b n + order_src(i)],   b over the (Nph + 1) blocks of each of the nvec vectors
+ *
+ *   normal mode (ed_total_ud = T and F, real, phonon and complex): flip swaps the up and the down words, so the twin's
+ *       vector is the transpose of every phonon block [DimDw][DimUp] (ed_total_ud=F: DimUp, DimDw = the products of
+ *       the DimUps, DimDws).  No sector map is needed: hand-over handles (edigpu_normal_create, edigpu_orbs_create)
+ *       are served, the check is then on the dimensions alone.
+ *   superc: flip swaps the two Ns-bit halves of a state: a permutation.  Its table (int32[electronic rows]) is built
+ *       on the host by one counting pass over the sector map the first time a handle is the SOURCE of a call, kept
+ *       on the device until edigpu_destroy and counted by the sector cache.
+ *   nonsu2: flip complements every bit, which reverses the order: v_dst[i] = v_src[n - 1 - i], no table.
+ *
+ * edigpu_twin_sector (host only): (tq1, tq2) = the twin of sector (q1, q2) of `mode` (0 normal, 1 superc: q1 = Sz,
+ * 2 nonsu2: q1 = Ntot; q2 ignored and tq2 = 0 for 1, 2), self_twin = 1 when the sector is its own twin.
+ *
+ * edigpu_apply_twin: nvec consecutive vectors of src's dimension at v_src_dev -> nvec of dst's at v_dst_dev, enqueued
+ * on `stream` without synchronisation (as edigpu_apply_occ); complex handles: interleaved (re, im).  Pure data
+ * movement: the results are the source's bits.  src and dst are whole sectors of one kind, model, device and nph, dst
+ * the twin of src (the same handle for a self-twin sector); a stored and an on-the-fly handle of superc / nonsu2 go
+ * together.  Vectors may be 8-byte aligned only and must not overlap.  Refused, each message starting with the entry
+ * point's name: NULL arguments ("NULL argument"), nvec < 1 ("nvec must be at least 1"), shards ("must hold the whole
+ * sector"), JZ_BASIS handles ("JZ_BASIS sectors are not supported"), hand-over flat handles ("has no sector map"),
+ * handles of different kind ("different kind"), model ("sectors of different models"), device ("different devices")
+ * or nph ("different nph"), a dst that is not the twin ("is not the twin sector"), overlapping vectors ("overlaps").
+ *
+ * edigpu_time_twin: measurement helper for scripts/time_twin.py: `warmup` untimed and `steps` timed reorders of one
+ * vector on the source handle's stream, each between two HIP events; the median in milliseconds.
+ */
+int edigpu_twin_sector(const edigpu_model *model, int mode, int q1, int q2, int *tq1, int *tq2, int *self_twin);
+int edigpu_apply_twin(edigpu_handle src, edigpu_handle dst, const void *v_src_dev, void *v_dst_dev, int nvec, void *stream);
+int edigpu_time_twin(edigpu_handle src, edigpu_handle dst, const void *v_src_dev, void *v_dst_dev, int warmup, int steps,
+                     double *ms);
+
+/*
  * Lowest eigenpair by plain Lanczos (lanc_method="lanczos": sp_lanc_eigh call
  * sites ED_NORMAL/ED_DIAG_NORMAL.f90:206-214): iterate until the lowest Ritz value
  * moves by less than tol (checked every `check_every` steps) or nitermax, then
@@ -859,6 +898,24 @@ int edigpu_apply_pairs_sharded(edigpu_handle src, edigpu_handle dst, edigpu_comm
 int edigpu_apply_pairs_sharded_info(edigpu_handle src, edigpu_handle dst, edigpu_comm c, int nterms, const double *coef,
                                     const int32_t *create1, const int32_t *iorb1, const int32_t *ispin1,
                                     const int32_t *create2, const int32_t *iorb2, const int32_t *ispin2, int64_t info[2]);
+/*
+ * edigpu_apply_twin on shards: the twin's vectors where the sharded solve leaves the stored sector's, in place of the
+ * gather of es_return_dvector_mpi (ED_EIGENSPACE.f90:723-793).  v_src_shard: nvec vectors of this rank's shard of
+ * sector `src`, one after the other; v_dst_shard receives nvec of its shard of `dst`; the layout of the sharded product
+ * (phonon sectors: block after block of the rank's rows).  Handles as for the sharded product: normal mode (real,
+ * phonon, complex) the whole-sector handle on every rank, shards = edigpu_shard_plan over DimDw of each sector;
+ * superc / nonsu2 this rank's row shards from edigpu_flat_build / edigpu_direct_build, the plan over the electronic
+ * rows.  One all-gather of the ranks' padded source shards on the device, then the window + source form of the
+ * single-GPU kernel on the rank's destination rows: the stitched shards are bit-identical to edigpu_apply_twin.
+ * Host or device memory; a rank that owns no row passes NULL; device vectors must not overlap.  Collective; returns
+ * after the device has finished; buffers are kept by the communicator and only grow.  The refusals of
+ * edigpu_apply_twin but the shard one, each message starting with this entry's name; also ed_total_ud=F handles ("are
+ * not served on shards"), hand-over handles ("are not served on shards"), a normal-mode down-row shard handle
+ * ("through the whole-sector handle"), a superc / nonsu2 handle that is not this rank's shard ("does not hold this
+ * rank's shard").  (Normal mode could exchange by one all-to-all instead, 1/world of the traffic: not built.)
+ */
+int edigpu_apply_twin_sharded(edigpu_handle src, edigpu_handle dst, edigpu_comm c, const void *v_src_shard,
+                              void *v_dst_shard, int nvec);
 /*
  * Occupation and phonon observables on shards: edigpu_occ_moments, edigpu_apply_occ, edigpu_apply_xph and edigpu_ph_rdm
  * on this rank's shard of a vector, without gathering it (the -D_MPI host otherwise collects every state on one rank:
