@@ -159,6 +159,22 @@ SIGNATURES = {
     "edigpu_trl_filter": (C.c_int, [_pd, _i64, C.c_int32, C.c_double]),
     "edigpu_trl_rotate": (C.c_int, [_i64, C.c_int32, C.c_int32, _pd, _i64, _i64, _pd, C.c_int32, _i64, _pd, _i64, _i64]),
     "edigpu_trl_scale": (C.c_int, [_i64, _pd, _i64, C.c_double]),
+    "edigpu_lzk_norm_begin": (C.c_int, [_i64, _pd, _i64, _pd, _i64, _pd, _i64]),
+    "edigpu_lzk_rotate": (C.c_int, [C.c_int32, _i64, _pd, _i64, _pd, _i64, _pd, _i64]),
+    "edigpu_lzk_next_vector": (C.c_int, [C.c_int32, _i64, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _i64]),
+    "edigpu_lzk_alpha": (C.c_int, [_i64, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _i64, C.c_int32, C.c_int32]),
+    "edigpu_lzk_beta": (C.c_int, [_i64, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _i64, C.c_int32, C.c_int32]),
+    "edigpu_lzk_add_dot3": (C.c_int, [_i64, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _i64, _pi32]),
+    "edigpu_lzk_axpy": (C.c_int, [_i64, _pd, _i64, _pd, _i64, C.c_double, _pd, _i64, C.c_int32]),
+    "edigpu_lzk_blocked": (C.c_int, [C.c_int32, _i64, _i64, C.c_int32, _pd, _i64, _pd, _i64]),
+    "edigpu_lzk_shard_rotate3": (C.c_int, [C.c_int32, _i64, _i64, _i64, C.c_int32, _i64, C.c_int32, _pd, _i64, _pd, _i64, _pd, _pd, _pd, _i64]),
+    "edigpu_lzk_shard_add_dot3": (C.c_int, [_i64, _i64, _i64, C.c_int32, _i64, C.c_int32, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _pd, _i64, _pd, _i64]),
+    "edigpu_lzk_panel_rotate": (C.c_int, [_i64, _pd, _i64, _pd, _i64, _pd, _pd]),
+    "edigpu_lzk_panel_add_dot": (C.c_int, [_i64, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _i64, _pd, _pd, _pd, _i64, _pd, _i64]),
+    "edigpu_lzk_interleave": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _i64, C.c_int32, _pd, _i64, _pd, _i64]),
+    "edigpu_lzk_norm_begin_multi": (C.c_int, [C.c_int32, C.c_int32, _i64, _pd, _i64, _pd, _i64, _pd, _i64, _i64]),
+    "edigpu_lzk_rotate_lazy_multi": (C.c_int, [C.c_int32, C.c_int32, _i64, _pd, _i64, _pd, _i64, _pd, _i64, _i64]),
+    "edigpu_lzk_finalize_ab_multi": (C.c_int, [C.c_int32, C.c_int32, _i64, _pd, _i64, _pd, _i64, _pd, _i64, C.c_int32, _pd, _i64, _i64, C.c_int32]),
     "edigpu_membw": (C.c_int, [_i64, _pd]),
     "edigpu_sector_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _pi32, _pi64]),
     "edigpu_cache_create": (C.c_int, [C.POINTER(_vp), _i64]),

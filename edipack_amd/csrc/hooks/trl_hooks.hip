@@ -4,52 +4,12 @@
 // kernels.hpp as the solver does (trl_solve, edigpu_trl.hip) on the calling thread's current device, and downloads every
 // buffer the launcher may write, whole again: a test that surrounds its payload with sentinels sees every write.
 // No kernel lives here; the arguments are checked before the device is touched.
-#include "../dev_mem.hpp"
-#include "../kernels.hpp"
+#include "hook_util.hpp"
 
 namespace edigpu {
 namespace {
 
 constexpr int kGroup = 16;  // kTrlNC (kernels_trl.hip): basis vectors per launch; trl_msum writes 2 * kGroup slots per group
-
-struct DevBuf {
-  double* p = nullptr;
-  size_t n = 0;
-  ~DevBuf() { dev_free(p); }
-  int up(const double* h, int64_t len) {
-    n = (size_t)len;
-    EDIGPU_HIP(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(double)));
-    if (n) EDIGPU_HIP(hipMemcpy(p, h, n * sizeof(double), hipMemcpyHostToDevice));
-    return 0;
-  }
-  int alloc(size_t cnt) {  // scratch: never downloaded
-    EDIGPU_HIP(hipMalloc((void**)&p, std::max<size_t>(cnt, 1) * sizeof(double)));
-    return 0;
-  }
-  int down(double* h) const {
-    if (n) EDIGPU_HIP(hipMemcpy(h, p, n * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-  }
-};
-
-struct DevInt {
-  int* p = nullptr;
-  ~DevInt() { dev_free(p); }
-  int up(int v) {
-    EDIGPU_HIP(hipMalloc((void**)&p, sizeof(int)));
-    EDIGPU_HIP(hipMemcpy(p, &v, sizeof(int), hipMemcpyHostToDevice));
-    return 0;
-  }
-  int down(int* v) const {
-    EDIGPU_HIP(hipMemcpy(v, p, sizeof(int), hipMemcpyDeviceToHost));
-    return 0;
-  }
-};
-
-int refuse(const char* who, const char* what) {
-  set_error(std::string(who) + ": " + what);
-  return 1;
-}
 
 // columns 0 .. ncol-1 of `len` doubles at leading dimension ld inside a buffer of `total` doubles
 const char* bad_matrix(const double* p, int ncol, int64_t ld, int64_t total, int64_t len) {
@@ -58,16 +18,6 @@ const char* bad_matrix(const double* p, int ncol, int64_t ld, int64_t total, int
   if (ncol > 1 && ld < len) return "leading dimension below the vector length";
   if (total < len || (ncol > 1 && (int64_t)(ncol - 1) > (total - len) / ld)) return "matrix buffer too short";
   return nullptr;
-}
-
-int need_device() {
-  int n = 0;
-  return edigpu_device_count(&n);  // sets the message
-}
-
-int finish(const char* who) {
-  if (hipDeviceSynchronize() != hipSuccess) return refuse(who, "the kernel failed");
-  return 0;
 }
 
 int64_t dots_slots(int ndot) { return (int64_t)2 * kGroup * ((ndot + kGroup - 1) / kGroup); }

@@ -1097,6 +1097,69 @@ int edigpu_trl_rotate(int64_t len, int32_t m, int32_t k, const double *Q, int64_
 int edigpu_trl_scale(int64_t len, double *v, int64_t vlen, double f);
 
 /*
+ * Test hooks: one call of a launcher of the three-term recurrence's vector kernels (csrc/kernels_lanczos.hip,
+ * csrc/kernels_shard.hip, csrc/kernels_multi.hip), as the Lanczos loops call it, on host data and on the calling thread's
+ * current device (edigpu_init).  The conventions are those of the edigpu_trl_* hooks: every buffer is a pointer and a
+ * length in doubles, uploaded whole, and every buffer the launcher may write is downloaded whole; bad arguments are
+ * refused with a message before the device is used.  n counts doubles.  scal: the device scalars of a recurrence (alpha,
+ * beta, stop, steps done, norm, threshold, ..., from index 8 the nlanc alphas and nlanc betas); where no step is
+ * recorded 8 doubles are enough.  t / tprev: three reduced sums each, or NULL where the launcher takes a null pointer.
+ */
+/* lz_norm_begin: scal[4] = |v|, v /= |v| (a zero v sets the stop flag); partial: min(ceil(n / 256), 1024) doubles. */
+int edigpu_lzk_norm_begin(int64_t n, double *v, int64_t vlen, double *partial, int64_t plen, double *scal, int64_t slen);
+/* lazy = 0: lz_rotate, (vin, vout) <- (vout / beta, -beta vin); lazy != 0: lz_rotate_lazy, ((vout - alpha vin) / beta, -beta vin). */
+int edigpu_lzk_rotate(int32_t lazy, int64_t n, double *vin, int64_t vinlen, double *vout, int64_t voutlen, const double *scal,
+                      int64_t slen);
+/* lz_next_vector: X = (Q - alpha P) / beta, alpha = 0 unless lazy. */
+int edigpu_lzk_next_vector(int32_t lazy, int64_t n, const double *P, int64_t plen, const double *Q, int64_t qlen, double *X,
+                           int64_t xlen, const double *scal, int64_t slen);
+/* lz_alpha: vout += tmp, alpha = <vin|vout> recorded as step iter < nlanc; slen >= 8 + 2 nlanc. */
+int edigpu_lzk_alpha(int64_t n, const double *vin, int64_t vinlen, double *vout, int64_t voutlen, const double *tmp,
+                     int64_t tmplen, double *partial, int64_t plen, double *scal, int64_t slen, int32_t iter, int32_t nlanc);
+/* lz_beta: vout -= alpha vin, beta = |vout| recorded for step iter + 1 (or the stop flag set). */
+int edigpu_lzk_beta(int64_t n, const double *vin, int64_t vinlen, double *vout, int64_t voutlen, double *partial, int64_t plen,
+                    double *scal, int64_t slen, int32_t iter, int32_t nlanc);
+/* lz_add_dot3: Q += tmp and the per-workgroup partials [3][*np] of <P|Q>, sum (Q - scal[0] P)^2, <P|P>;
+ * partlen >= 3 * min(ceil(n / 256), 1024). */
+int edigpu_lzk_add_dot3(int64_t n, const double *P, int64_t plen, double *Q, int64_t qlen, const double *tmp, int64_t tmplen,
+                        const double *scal, int64_t slen, double *partial, int64_t partlen, int32_t *np);
+/* lz_axpy_coef: acc += coef vin while iter < scal[3]. */
+int edigpu_lzk_axpy(int64_t n, double *acc, int64_t acclen, const double *vin, int64_t vinlen, double coef, const double *scal,
+                    int64_t slen, int32_t iter);
+/* to != 0: vec_to_blocked (src: dim_dw rows of dim_up, dst: ceil(dim_up / 2^shift) panels of dim_dw * 2^shift); to = 0:
+ * vec_from_blocked, the way back. */
+int edigpu_lzk_blocked(int32_t to, int64_t dim_up, int64_t dim_dw, int32_t shift, const double *src, int64_t srclen, double *dst,
+                       int64_t dstlen);
+/* shard_rotate3; send may be NULL, else n = nrows * dim_up, nrows <= q, pcol * world >= dim_up and
+ * sendlen >= world * q * (pcol + 2 halo). */
+int edigpu_lzk_shard_rotate3(int32_t first, int64_t n, int64_t dim_up, int64_t q, int32_t world, int64_t pcol, int32_t halo,
+                             double *vin, int64_t vinlen, double *vout, int64_t voutlen, const double *t, const double *tprev,
+                             double *send, int64_t sendlen);
+/* shard_add_dot3; back may be NULL (else as send above); work: 3 * 1024 doubles, sums: 3. */
+int edigpu_lzk_shard_add_dot3(int64_t n, int64_t dim_up, int64_t q, int32_t world, int64_t pcol, int32_t halo, const double *vin,
+                              int64_t vinlen, double *vout, int64_t voutlen, const double *tmp, int64_t tmplen, const double *back,
+                              int64_t backlen, const double *tprev, double *work, int64_t worklen, double *sums, int64_t sumslen);
+/* shard_panel_rotate: x <- (x - alpha v) / beta on n2 pairs of doubles. */
+int edigpu_lzk_panel_rotate(int64_t n2, double *x, int64_t xlen, const double *v, int64_t vlen, const double *t,
+                            const double *tprev);
+/* shard_panel_add_dot: vdst <- rowhalf + colhalf (- beta vdst when t is given) and the three sums with x. */
+int edigpu_lzk_panel_add_dot(int64_t n2, const double *x, int64_t xlen, double *vdst, int64_t vdstlen, const double *rowhalf,
+                             int64_t rowlen, const double *colhalf, int64_t collen, const double *t, const double *tprev,
+                             double *work, int64_t worklen, double *sums, int64_t sumslen);
+/* to != 0: launch_interleave_multi (g <= W vectors of nrow elements -> W interleaved columns); to = 0: the way back. */
+int edigpu_lzk_interleave(int32_t to, int32_t W, int32_t cplx, int64_t nrow, int32_t g, const double *src, int64_t srclen,
+                          double *dst, int64_t dstlen);
+/* The per-column kernels of W recurrences in lock-step; column j keeps its scalars at scal + j * sstride. */
+int edigpu_lzk_norm_begin_multi(int32_t W, int32_t cplx, int64_t nrow, double *P, int64_t plen, double *partial, int64_t partlen,
+                                double *scal, int64_t slen, int64_t sstride);
+int edigpu_lzk_rotate_lazy_multi(int32_t W, int32_t cplx, int64_t nrow, double *P, int64_t plen, double *Q, int64_t qlen,
+                                 const double *scal, int64_t slen, int64_t sstride);
+/* partial: [(3 j + t) * np + i]; sstride >= 8 + 2 nlanc. */
+int edigpu_lzk_finalize_ab_multi(int32_t W, int32_t cplx, int64_t nrow, const double *P, int64_t plen, const double *Q,
+                                 int64_t qlen, const double *partial, int64_t partlen, int32_t np, double *scal, int64_t slen,
+                                 int64_t sstride, int32_t nlanc);
+
+/*
  * Measurement helper for bench.py: `warmup` + `steps` full Lanczos steps (H*v + the vector
  * recurrence) on a random unit start vector.  *ms_wall_per_step = host wall clock of the timed
  * steps (stream synchronised on both sides) / steps; *ms_hv_per_launch = average duration of the
